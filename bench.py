@@ -22,17 +22,23 @@ precision fp16x2 (default): the decoder's multiply-adds with every f32 operand a
         SDF value; the f32 pipe: 2.0e-7), parity-gated like the f32 tile (tests/test_gpu_split_precision.py: K / n_valid exact on
         every fixture, teacher-forced H, b, dx, next state inside the same bars; out-of-range decoders are refused or fail loudly).
         bf16x3: three bf16 terms, six products.  f32: the exact-f32 matrix pipe.  The other two pipes' step times are reported
-        beside `value` in every default run (`f32_mfma`, `bf16x3_mfma`).
+        beside `value` in every --full run (`f32_mfma`, `bf16x3_mfma`).
 
 screening (default with fp16x2, --screening-margin 0.01): the ray-sample forward pass of the refinement in two passes -- every
         sample on a one-product fp16 tile (sign and rough magnitude), the samples with |s1| < cut_off + margin again on the
         split-fp16 tile.  The render term clamps outside the band, so K, n_valid, H, b and every iterate are bit-identical to the
-        one-pass result (tests/test_gpu_screening.py); `fp16x2_unscreened` in the line is the same workload with one pass.
+        one-pass result (tests/test_gpu_screening.py); `fp16x2_unscreened` in the --full line is the same workload with one pass.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|c5] [--scaling strong|weak] [--precision fp16x2|bf16x3|f32]
-                  [--screening-margin M] [--no-sublines] [--no-cpu-baseline]
+                  [--screening-margin M] [--dump-outputs DIR] [--full [--no-sublines] [--no-cpu-baseline] [--no-extras]]
   N > 1: one rank per GPU under torch.distributed.run (the driver's launch line); `python bench.py --gpus N` without that
   environment starts it as a child process.
+
+A plain run times the workload and prints the headline line (`value`, `ms_per_step`, the roofline of the timed run's own
+kernels).  --full adds everything that takes runs of its own: the other pipes and screening variants, the C2 / C5 sublines,
+the large-graph linearisation, host buffers, the one-object latency block and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0's hypotheses, the kept result per object, the BA's state
+and chi2 trace) as DIR/<name>.npy in float32 / float64; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -282,9 +288,9 @@ class Ctx(object):
         return float(t.item())
 
 
-def run_workload(ctx, name, steps, warmup, detailed, precision=None, screening=None, audit=None, staging=None):
+def run_workload(ctx, name, steps, warmup, detailed, precision=None, screening=None, audit=None, staging=None, dump=False):
     """`steps` timed passes of workload `name` (after `warmup` untimed ones); every rank returns the same dict of whole-job
-    numbers (rank 0's kernel timings)."""
+    numbers (rank 0's kernel timings).  dump: res["outputs"] holds what the last timed step computed (see dump_outputs)."""
     from qsp_slam_amd import DeepSdfDecoder, parallel, synth
     from qsp_slam_amd.ba import BaProblem
     from qsp_slam_amd.reconstruct.optimizer import Optimizer, RefineBatch, _joint_cfg
@@ -342,6 +348,7 @@ def run_workload(ctx, name, steps, warmup, detailed, precision=None, screening=N
         ba.set_state(kf0, pt0, ob0)    # the caller's current estimates (float64 poses / points)
         t_a = time.perf_counter()
         t1, t2 = ba.local_joint_ba()
+        results["ba_traces"] = (t1, t2)
         if record:
             ba_stat["ms"] += 1e3 * (time.perf_counter() - t_a)
             ba_stat["iters"] += int(t1["iterations"] + t2["iterations"])
@@ -387,9 +394,20 @@ def run_workload(ctx, name, steps, warmup, detailed, precision=None, screening=N
     ctx.sync_all()
     dt = ctx.allreduce(time.perf_counter() - t0, "MAX")
     n_good = 0
+    outputs = {}
     if batch is not None:
-        _, _, _, good = batch.get()
+        T, code, loss, good = batch.get()
         n_good = int(good.sum())
+        if dump:
+            outputs.update(refine_t_cam_obj=T, refine_code=code, refine_loss=loss, refine_good=good.astype(np.float32))
+    if dump:
+        # the kept result per object (82 floats: T_cam_obj, code, loss, good): gathered over the ranks in a strong N > 1 run
+        outputs["objects_kept"] = (results["table"] if "table" in results else
+                                   select_flips(T, code, loss, good, len(objs), flips) if batch is not None
+                                   else np.zeros((0, 82), np.float32))
+        kf, pt, ob = ba.state()
+        t1, t2 = results["ba_traces"]
+        outputs.update(ba_kf_pose=kf, ba_pt_xyz=pt, ba_obj_pose=ob, ba_chi2_stage1=t1["chi2"], ba_chi2_stage2=t2["chi2"])
     n_good = int(ctx.allreduce(n_good, "SUM"))
     n_hyp_job = (w["n_obj"] * flips) if strong else int(ctx.allreduce(len(hyp), "SUM"))
     sdf_iters = n_hyp_job * w["n_iter"] * steps
@@ -455,6 +473,8 @@ def run_workload(ctx, name, steps, warmup, detailed, precision=None, screening=N
                  "ba_linearize_events_in": "timed steps" if lin_in_timed else "warm-up steps (no event records inside the timed BA)",
                  "ba_linearize_note": "launch-bound at the BASELINE sizes: 2 launches for a few MB; `ba_linearize_large` "
                                       "(N = 1 only) is the same code on a graph large enough to stream"})
+    if dump:
+        res["outputs"] = outputs
     if detailed:
         res["_objs"], res["_scene"], res["_hyp"], res["_T0"] = objs, scene, hyp, T0
         res["_dec"], res["_opt"] = dec, opt
@@ -536,6 +556,22 @@ def latency_block(dec):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """DIR/<name>.npy per array: float64 stays float64 (the BA's state and chi2), everything else is written as float32.
+    Every output of the BASELINE workloads fits the limit whole (C5, the largest: under 1 MB)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("outputs of %d bytes exceed the %d-byte dump limit" % (total, DUMP_LIMIT_BYTES))
+    for k, a in sorted(arrays.items()):
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -554,11 +590,18 @@ def main():
     ap.add_argument("--allow-hook-fallback", action="store_true",
                     help="N > 1, strong scaling: if the library's own RCCL communicator cannot be created, measure the "
                          "torch.distributed all-reduce hook instead of exiting with an error")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sublines", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: other pipes and screening variants, C2 / C5 "
+                         "sublines, large-graph linearisation, host buffers, latency block, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-sublines", action="store_true", help="--full without the other pipes, variants and sublines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the large-graph linearisation, host-buffer and latency measurements (for profiler runs)")
+                    help="--full without the large-graph linearisation, host-buffer and latency measurements")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # nothing has touched the GPU yet: start the ranks as a CHILD (never exec) and hand its exit code on
@@ -574,9 +617,12 @@ def main():
     if ctx.world != max(args.gpus, 1) and ctx.rank == 0:
         print("bench.py: --gpus %d but WORLD_SIZE=%d; using WORLD_SIZE" % (args.gpus, ctx.world), file=sys.stderr)
     world, rank = ctx.world, ctx.rank
-    main_res = run_workload(ctx, args.workload, args.steps, args.warmup, detailed=True)
+    main_res = run_workload(ctx, args.workload, args.steps, args.warmup, detailed=True, dump=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_res["outputs"])
+    sublines = args.full and not args.no_sublines
     other = {}
-    if not args.no_sublines:      # the other matrix pipes on the same workload, beside `value`
+    if sublines:                  # the other matrix pipes on the same workload, beside `value`
         for pr in ("f32", "bf16x3"):
             if pr != args.precision:
                 other[pr] = run_workload(ctx, args.workload, 3, 1, detailed=False, precision=pr)
@@ -587,7 +633,7 @@ def main():
             if not args.no_depth_staging:    # ... and screened in ONE depth stage: what the samples behind opaque ones cost
                 other["fp16x2_screened_one_depth_stage"] = run_workload(ctx, args.workload, 3, 1, detailed=False, precision="fp16x2", staging=False)
     subs = {}
-    if not args.no_sublines:
+    if sublines:
         for name in ("c2", "c5"):
             if name != args.workload:
                 r = run_workload(ctx, name, 2, 1, detailed=False)
@@ -692,7 +738,7 @@ def main():
                                   "ms_local_joint_ba": c5["ms_ba"],
                                   "note": "latency-bound at every BASELINE size (two launches for <= 30 MB); see "
                                           "kernels.ba_linearize_large for the streaming regime of the same kernels"}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             from qsp_slam_amd import synth
             from qsp_slam_amd.ba import BaProblem
             from qsp_slam_amd.reconstruct.optimizer import RefineBatch, _joint_cfg
@@ -736,7 +782,7 @@ def main():
             b2.close()
             ba2.close()
             out["latency"] = latency_block(dec)
-        if world == 1 and not args.no_cpu_baseline:      # rank 0 at N = 1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:      # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(w, m["_objs"], m["_scene"], len(m["_hyp"]))
         print(json.dumps(out))
         sys.stdout.flush()

@@ -7,9 +7,9 @@ set -e -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/refresh
 mkdir -p $O
-timeout -k 10 500 python3 bench.py > $O/bench_c4.json 2> $O/bench_c4.err
+timeout -k 10 500 python3 bench.py --full > $O/bench_c4.json 2> $O/bench_c4.err
 echo "bench done"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o c4 -- python3 bench.py --workload c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o c4 -- python3 bench.py --full --workload c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
 python3 tools/kstats.py $O/trace > $O/kernel_stats.txt
 cp "$(find $O/trace -name '*kernel_stats.csv' | head -1)" $O/c4_kernel_stats.csv
 echo "trace done"

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/refresh3
 mkdir -p $O
 if [ "$1" != "quick" ]; then
-  timeout -k 10 700 python3 bench.py > $O/r03_bench_c4.json 2> $O/bench.err
+  timeout -k 10 700 python3 bench.py --full > $O/r03_bench_c4.json 2> $O/bench.err
   echo "bench done"
 fi
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o c4 -- python3 bench.py --workload c4 --steps 2 --warmup 1 --no-cpu-baseline --no-sublines --no-extras > $O/trace.log 2>&1

@@ -13,7 +13,7 @@ QSP_PRECISION=fp16x2 QSP_SCREENING=0.01 QSP_MARGINS_OUT=$O/r04_test_margins_fp16
 tail -3 $O/tests_fp16x2.log
 QSP_PRECISION=fp16x2 QSP_SCREENING=0.01 QSP_DEPTH_STAGING=always QSP_MARGINS_OUT=$O/r04_test_margins_fp16x2_screened_staged_always.json timeout -k 10 900 python3 -m pytest tests -m gpu -q > $O/tests_fp16x2_staged.log 2>&1 || true
 tail -3 $O/tests_fp16x2_staged.log
-timeout -k 10 800 python3 bench.py > $O/r04_bench_c4.json 2> $O/bench.err
+timeout -k 10 800 python3 bench.py --full > $O/r04_bench_c4.json 2> $O/bench.err
 echo "bench done"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o c4 -- python3 bench.py --workload c4 --steps 2 --warmup 1 --no-cpu-baseline --no-sublines --no-extras > $O/trace.log 2>&1
 python3 tools/kstats.py $O/trace > $O/r04_c4_kernel_stats.txt
