@@ -64,10 +64,13 @@ typedef struct qsp_decoder qsp_decoder;
  * decoder -- qsp_decode_sdf*, qsp_sdf_value_grad, qsp_refine_batch_set_state / _run / _get, qsp_reconstruct_objects,
  * qsp_estimate_pose, qsp_refine_detections, qsp_mesh_extract / _from_volume, qsp_decoder_set_option -- takes the decoder's lock:
  * host threads may share a decoder and get correct results, one call at a time.  Threads that should overlap on the GPU use a
- * decoder each. */
+ * decoder each.  A call on a decoder GROUP (qsp_decoder_group_create below) -- the *_group entry points and the batch calls on a
+ * group's batch -- takes the lock of every member, always in the same order (by address), so it cannot deadlock against
+ * single-decoder calls or other group calls on other threads; it runs on its first member's stream. */
 int qsp_decoder_create(const qsp_decoder_desc* desc, int device, qsp_decoder** out);
 /* Batches and mesh extractors created from a decoder use it until they are destroyed: destroy them first.  (Destroying one of
- * them after its decoder only frees its own memory and is harmless; any other call on it is undefined.) */
+ * them after its decoder only frees its own memory and is harmless; any other call on it is undefined.)  With decoder groups:
+ * destroy the group's batches, then the group, then its decoders. */
 void qsp_decoder_destroy(qsp_decoder* dec);
 
 /* Decoder options.  QSP_DEC_OPT_FORWARD_PRECISION selects the arithmetic of the FORWARD-ONLY decoder passes (qsp_decode_sdf,
@@ -535,6 +538,47 @@ typedef struct {               /* any pointer may be NULL */
 
 int qsp_refine_detections(qsp_decoder* dec, const qsp_joint_cfg* cfg, const qsp_detections* det,
                           qsp_detection_results* out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Decoder groups: the objects of several classes in ONE batch.  QSP-SLAM builds one optimizer per class id, all with the same
+ * code length and optimiser parameters (src/LocalMapping.cc:33-69, the assumption stated at :47), and LocalMapping_util.cc
+ * picks the one of each detection's class.  A group is an ordered set of existing decoders, one per class; the group entry
+ * points take a class index in [0, n) per object / detection and advance the objects of all classes together, in the same
+ * launches per iteration as one decoder's batch: each work item of a decoder kernel reads the parameters of its object's
+ * class.  Every hypothesis's numbers are those of the same object in a batch of its own class's decoder alone (same slot
+ * count, i.e. same largest point set), bit for bit.
+ *   1..16 members, on one device.  Members may differ in weights, shape (any the single decoder accepts) and use_tanh; they
+ *   must agree on code_len, both precisions, tile points, narrow tile, render screening (margin, audit, minimum samples, depth
+ *   staging) and range fallback: QSP_ERR_UNSUPPORTED names the first option that differs.  Checked again at every group call
+ *   (options may change after creation).  A class index outside [0, n): QSP_ERR_INVALID.
+ *   Range fallback: when a split-fp16 pass of ANY member leaves fp16's range, the whole call is repeated on the f32 pipe for
+ *   every member (qsp_refine_profile.range_fallbacks, QSP_DEC_CNT_RANGE_FALLBACKS of member 0).
+ *   Threads and lifetime: see qsp_decoder_create. */
+enum { QSP_GROUP_MAX = 16 };
+typedef struct qsp_decoder_group qsp_decoder_group;
+int qsp_decoder_group_create(qsp_decoder* const* decs, int32_t n, qsp_decoder_group** out);
+void qsp_decoder_group_destroy(qsp_decoder_group* g);
+/* qsp_refine_batch_create over a group: obj_class[o] = member of object o.  The batch is an ordinary qsp_refine_batch: set_state,
+ * run, get, trace, trace_rot, rows and profile work on it unchanged. */
+int qsp_refine_batch_create_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, int32_t n_obj,
+                                  const float* const* pts, const int32_t* n_pts,
+                                  const float* const* rays, const int32_t* n_rays,
+                                  const float* const* depth, const int32_t* n_fg, const int32_t* obj_class,
+                                  int32_t n_hyp, const int32_t* hyp_obj, qsp_refine_batch** out);
+/* qsp_reconstruct_objects over a group, on a resident batch owned by the group (results do not depend on what it held before) */
+int qsp_reconstruct_objects_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, int32_t n_obj,
+                                  const float* const* pts, const int32_t* n_pts,
+                                  const float* const* rays, const int32_t* n_rays,
+                                  const float* const* depth, const int32_t* n_fg, const int32_t* obj_class,
+                                  int32_t n_hyp, const int32_t* hyp_obj, const float* t_cam_obj, const float* code,
+                                  float* t_cam_obj_out, float* code_out, float* loss_out, uint8_t* is_good_out);
+/* qsp_estimate_pose over a group: obj_class[i] = member of item i */
+int qsp_estimate_pose_group(qsp_decoder_group* g, int32_t n, const float* t_co_se3, const float* scale,
+                            const float* const* pts, const int32_t* n_pts, const float* code, const int32_t* obj_class,
+                            int32_t n_iter, float* t_co_out);
+/* qsp_refine_detections over a group: det_class[d] = member of detection d */
+int qsp_refine_detections_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, const qsp_detections* det,
+                                const int32_t* det_class, qsp_detection_results* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Single-ellipsoid fits, batched: EllipsoidExtractor::OptimizeEllipsoidUsingPlanes,

@@ -3,6 +3,6 @@
 Importing the package does not touch the GPU; the first call that needs libqsp_hip.so loads it and raises if it is
 missing -- there is no CPU fallback in the product path (the CPU restatement under oracle/ is test infrastructure)."""
 from . import _lib  # noqa: F401
-from .decoder import DeepSdfDecoder  # noqa: F401
+from .decoder import DecoderGroup, DeepSdfDecoder  # noqa: F401
 
-__all__ = ["DeepSdfDecoder", "_lib"]
+__all__ = ["DecoderGroup", "DeepSdfDecoder", "_lib"]

@@ -99,6 +99,8 @@ SYMBOLS = [
     "qsp_refine_batch_create", "qsp_refine_batch_destroy", "qsp_refine_batch_set_state", "qsp_refine_batch_run",
     "qsp_refine_batch_get", "qsp_refine_batch_trace", "qsp_refine_batch_trace_rot", "qsp_refine_batch_profile", "qsp_refine_batch_rows",
     "qsp_reconstruct_objects", "qsp_estimate_pose", "qsp_refine_detections",
+    "qsp_decoder_group_create", "qsp_decoder_group_destroy", "qsp_refine_batch_create_group", "qsp_reconstruct_objects_group",
+    "qsp_estimate_pose_group", "qsp_refine_detections_group",
     "qsp_mesh_extractor_create", "qsp_mesh_extractor_destroy", "qsp_mesh_extract", "qsp_mesh_from_volume", "qsp_mesh_fetch", "qsp_mesh_fetch_f64", "qsp_mesh_extractor_set_method",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
@@ -149,6 +151,17 @@ def lib():
     L.qsp_estimate_pose.argtypes = [vp, C.c_int32, c_float_p, c_float_p, pp_f, c_int32_p, c_float_p, C.c_int32,
                                     c_float_p]
     L.qsp_refine_detections.argtypes = [vp, C.POINTER(JointCfg), C.POINTER(Detections), C.POINTER(DetectionResults)]
+    L.qsp_decoder_group_create.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(vp)]
+    L.qsp_decoder_group_destroy.argtypes = [vp]
+    L.qsp_decoder_group_destroy.restype = None
+    L.qsp_refine_batch_create_group.argtypes = [vp, C.POINTER(JointCfg), C.c_int32, pp_f, c_int32_p, pp_f, c_int32_p, pp_f,
+                                                c_int32_p, c_int32_p, C.c_int32, c_int32_p, C.POINTER(vp)]
+    L.qsp_reconstruct_objects_group.argtypes = [vp, C.POINTER(JointCfg), C.c_int32, pp_f, c_int32_p, pp_f, c_int32_p, pp_f,
+                                                c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_float_p, c_float_p, c_float_p,
+                                                c_float_p, c_float_p, c_uint8_p]
+    L.qsp_estimate_pose_group.argtypes = [vp, C.c_int32, c_float_p, c_float_p, pp_f, c_int32_p, c_float_p, c_int32_p, C.c_int32,
+                                          c_float_p]
+    L.qsp_refine_detections_group.argtypes = [vp, C.POINTER(JointCfg), C.POINTER(Detections), c_int32_p, C.POINTER(DetectionResults)]
     L.qsp_mesh_extractor_create.argtypes = [vp, C.c_int32, c_float_p, C.POINTER(vp)]
     L.qsp_mesh_extractor_destroy.argtypes = [vp]
     L.qsp_mesh_extractor_destroy.restype = None

@@ -185,10 +185,10 @@ struct DevPool {            // the call's temporary device arrays
 }  // namespace det
 }  // namespace qsp
 
-extern "C" int qsp_refine_detections(qsp_decoder* dec, const qsp_joint_cfg* cfg, const qsp_detections* in,
-                                     qsp_detection_results* out) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (dec) lk_d = std::unique_lock<std::recursive_mutex>(dec->mu);
+// qsp_refine_detections on a decoder (grp == nullptr) or on a decoder group (dec = its first member, det_class = the member per
+// detection); the caller holds the locks
+static int refine_detections(qsp_decoder* dec, qsp_decoder_group* grp, const int32_t* det_class, const qsp_joint_cfg* cfg,
+                             const qsp_detections* in, qsp_detection_results* out) {
     using namespace qsp::det;
     if (!dec || !cfg || !in || !out) return qsp_fail(QSP_ERR_INVALID, "qsp_refine_detections: null argument");
     const int n = in->n_det;
@@ -235,7 +235,7 @@ extern "C" int qsp_refine_detections(qsp_decoder* dec, const qsp_joint_cfg* cfg,
     RefineCfg c{cfg->k1, cfg->k2, cfg->k3, cfg->k4, cfg->b1, cfg->b2, cfg->lr, cfg->s_damp, cfg->cut_off, cfg->n_depth, 0, 0,
                 dec->code_len};
     int rc = batch_create(dec, c, cfg->n_iter, n, nullptr, n_pts.data(), nullptr, n_rays.data(), nullptr, n_fg.data(), n_hyp,
-                          hyp_obj.data(), &b, true);
+                          hyp_obj.data(), &b, true, nullptr, grp, det_class);
     if (rc) return rc;
     struct Guard {
         qsp_refine_batch* b;
@@ -296,4 +296,20 @@ extern "C" int qsp_refine_detections(qsp_decoder* dec, const qsp_joint_cfg* cfg,
         }
     }
     return QSP_OK;
+}
+
+extern "C" int qsp_refine_detections(qsp_decoder* dec, const qsp_joint_cfg* cfg, const qsp_detections* in,
+                                     qsp_detection_results* out) {
+    const CallLock lk(dec);
+    return refine_detections(dec, nullptr, nullptr, cfg, in, out);
+}
+
+extern "C" int qsp_refine_detections_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, const qsp_detections* in,
+                                           const int32_t* det_class, qsp_detection_results* out) {
+    if (!g || !in) return qsp_fail(QSP_ERR_INVALID, "qsp_refine_detections_group: null argument");
+    const CallLock lk(g);
+    int rc = group_check(g);
+    if (!rc && in->n_det > 0) rc = group_classes(g, in->n_det, det_class);
+    if (rc) return rc;
+    return refine_detections(g->m[0], g, det_class, cfg, in, out);
 }

@@ -83,6 +83,20 @@ struct qsp_decoder {
     int64_t n_arena_reuse = 0, n_arena_create = 0;
 };
 
+// A decoder group (qsp_decoder_group_create): an ordered set of decoders, one per class, that the group entry points refine
+// together -- every object names its member (ObjView::dec) and the k_grp_* twins of the decoder kernels read that member's
+// MlpParams from Pd.  The members' options must agree (group_check); the first member lends the group its stream and its
+// option fields, and a range fallback / screening repeat of a group call overrides them there.
+struct qsp_decoder_group {
+    std::vector<qsp_decoder*> m;            // members, class order
+    std::vector<qsp_decoder*> lock_order;   // the distinct members by address: a group call takes their locks in this order
+    int device = 0;
+    MlpParams* Pd = nullptr;                // device copy of the members' MlpParams, class order
+    std::vector<MlpParams> Ph;              // what Pd holds (refreshed when a member's parameters change: use_tanh, narrow)
+    struct qsp_refine_batch* arena = nullptr;   // the resident batch of qsp_reconstruct_objects_group
+    int64_t n_arena_reuse = 0, n_arena_create = 0;
+};
+
 // Runs the enclosed call with every decoder pass on the exact-f32 pipe (the range fallback of the split-fp16 modes).
 struct F32Override {
     qsp_decoder* d;
@@ -612,6 +626,21 @@ static int mlp_attr_once() {
     QSP_HIP(hipFuncSetAttribute((const void*)k_decode<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     QSP_HIP(hipFuncSetAttribute((const void*)k_decode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     QSP_HIP(hipFuncSetAttribute((const void*)k_decode<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    // the decoder-group twins of the refinement's decoder kernels
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h2<2, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h2<2, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h1<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h1<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<2, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<1, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<2, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<1, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<1, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     done = true;
     return QSP_OK;
 }
@@ -855,7 +884,8 @@ extern "C" int qsp_sdf_value_grad(qsp_decoder* d, const float* code, const float
 // refinement batch
 // ---------------------------------------------------------------------------------------------------------------
 struct qsp_refine_batch {
-    qsp_decoder* dec = nullptr;
+    qsp_decoder* dec = nullptr;     // a group's batch: its first member (stream, options -- the same for every member, group_check)
+    qsp_decoder_group* grp = nullptr;   // set: the decoder kernels look up each object's decoder (ObjView::dec) in grp->Pd
     int device = 0;                 // of the decoder, cached: destroy must not touch a decoder that may already be gone
     RefineCfg cfg{};
     int code_len = CODE_LEN;        // dec->code_len, cached like `device`
@@ -913,6 +943,76 @@ struct qsp_refine_batch {
 };
 
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The locks of a call: its decoder's, or every member's of its group in one fixed order (by address), so that a group call
+// cannot deadlock against single-decoder calls or other group calls on other threads.
+struct CallLock {
+    std::vector<std::unique_lock<std::recursive_mutex>> l;
+    explicit CallLock(qsp_decoder* d) {
+        if (d) l.emplace_back(d->mu);
+    }
+    explicit CallLock(qsp_decoder_group* g) {
+        if (g)
+            for (qsp_decoder* d : g->lock_order) l.emplace_back(d->mu);
+    }
+    explicit CallLock(qsp_refine_batch* b) {
+        if (b && b->grp) *this = CallLock(b->grp);
+        else if (b && b->dec) l.emplace_back(b->dec->mu);
+    }
+};
+
+// Checks, at every group call, that the members still agree on everything the group's launches share, and brings the device
+// copy of their parameters up to date.  Callers hold the group's locks.
+static int group_options(const qsp_decoder_group* g) {
+    const qsp_decoder* a = g->m[0];
+    for (size_t i = 1; i < g->m.size(); ++i) {
+        const qsp_decoder* d = g->m[i];
+        const char* what = nullptr;
+        if (d->device != a->device) what = "device";
+        else if (d->code_len != a->code_len) what = "code_len";
+        else if (d->fwd_bf3 != a->fwd_bf3) what = "QSP_DEC_OPT_FORWARD_PRECISION";
+        else if (d->jac_bf3 != a->jac_bf3) what = "QSP_DEC_OPT_JACOBIAN_PRECISION";
+        else if (d->tile_p != a->tile_p) what = "QSP_DEC_OPT_TILE_POINTS";
+        else if (d->P.narrow != a->P.narrow) what = "QSP_DEC_OPT_NARROW_TILE";
+        else if (d->screen_margin != a->screen_margin) what = "QSP_DEC_OPT_RENDER_SCREENING";
+        else if (d->screen_audit != a->screen_audit) what = "QSP_DEC_OPT_SCREEN_AUDIT";
+        else if (d->screen_min_samples != a->screen_min_samples) what = "QSP_DEC_OPT_SCREENING_MIN_SAMPLES";
+        else if (d->depth_staging != a->depth_staging) what = "QSP_DEC_OPT_DEPTH_STAGING";
+        else if (d->range_fallback != a->range_fallback) what = "QSP_DEC_OPT_RANGE_FALLBACK";
+        if (what) {
+            const std::string msg = std::string("decoder group: member ") + std::to_string(i) + " differs from member 0 in " + what +
+                                    " (the members of a group share it)";
+            return qsp_fail(QSP_ERR_UNSUPPORTED, msg.c_str());
+        }
+    }
+    return QSP_OK;
+}
+static int group_check(qsp_decoder_group* g) {
+    const int rc = group_options(g);
+    if (rc) return rc;
+    bool stale = g->Ph.size() != g->m.size();
+    g->Ph.resize(g->m.size());
+    for (size_t i = 0; i < g->m.size(); ++i)
+        if (memcmp(&g->Ph[i], &g->m[i]->P, sizeof(MlpParams)) != 0) {
+            memcpy(&g->Ph[i], &g->m[i]->P, sizeof(MlpParams));
+            stale = true;
+        }
+    if (stale) {
+        QSP_HIP(hipSetDevice(g->device));
+        QSP_HIP(hipStreamSynchronize(g->m[0]->stream));
+        QSP_HIP(hipMemcpy(g->Pd, g->Ph.data(), sizeof(MlpParams) * g->m.size(), hipMemcpyHostToDevice));
+    }
+    return QSP_OK;
+}
+
+// a group call's class index per object: [0, n) of the group
+static int group_classes(const qsp_decoder_group* g, int32_t n_obj, const int32_t* cls) {
+    if (!cls) return qsp_fail(QSP_ERR_INVALID, "decoder group: class index array is null");
+    for (int o = 0; o < n_obj; ++o)
+        if (cls[o] < 0 || cls[o] >= (int32_t)g->m.size())
+            return qsp_fail(QSP_ERR_INVALID, "decoder group: class index out of range [0, number of members)");
+    return QSP_OK;
+}
 
 // uploads what fill / set_state left in the mirror (one copy; nothing when nothing changed)
 static int batch_upload(qsp_refine_batch* b) {
@@ -972,7 +1072,7 @@ static int batch_validate(const RefineCfg& cfg, int32_t n_obj, const int32_t* n_
 // and buffer sizes stay those of the capacities; every per-object quantity the kernels use comes from the ObjView table.
 static int batch_fill(qsp_refine_batch* b, int32_t n_obj, const float* const* pts, const int32_t* n_pts, const float* const* rays,
                       const int32_t* n_rays, const float* const* depth, const int32_t* n_fg, int32_t n_hyp, const int32_t* hyp_obj,
-                      bool device_fill) {
+                      bool device_fill, const int32_t* obj_class = nullptr) {
     const RefineCfg& cfg = b->cfg;
     b->n_obj = n_obj;
     b->n_hyp = n_hyp;
@@ -981,7 +1081,7 @@ static int batch_fill(qsp_refine_batch* b, int32_t n_obj, const float* const* pt
     for (int o = 0; o < n_obj; ++o) {
         const int nr = cfg.pose_only ? 0 : n_rays[o];
         const int nf = cfg.pose_only ? 0 : n_fg[o];
-        b->objs_h[o] = ObjView{po, ro, n_pts[o], nr, nf, 0};
+        b->objs_h[o] = ObjView{po, ro, n_pts[o], nr, nf, obj_class ? obj_class[o] : 0};
         po += n_pts[o];
         ro += nr;
     }
@@ -1026,7 +1126,8 @@ static bool batch_fits(const qsp_refine_batch* b, const BatchCaps& need) {
 static int batch_create(qsp_decoder* dec, const RefineCfg& cfg, int n_iter, int32_t n_obj, const float* const* pts,
                         const int32_t* n_pts, const float* const* rays, const int32_t* n_rays,
                         const float* const* depth, const int32_t* n_fg, int32_t n_hyp, const int32_t* hyp_obj,
-                        qsp_refine_batch** out, bool device_fill = false, const BatchCaps* caps_in = nullptr) {
+                        qsp_refine_batch** out, bool device_fill = false, const BatchCaps* caps_in = nullptr,
+                        qsp_decoder_group* grp = nullptr, const int32_t* obj_class = nullptr) {
     // device_fill: only the extents are given, the observation arrays are written by a kernel (detections.hpp)
     if (!dec || !out || n_obj <= 0 || n_hyp <= 0 || (!pts && !device_fill) || !n_pts || !hyp_obj)
         return qsp_fail(QSP_ERR_INVALID, "refine batch: bad argument");
@@ -1046,6 +1147,7 @@ static int batch_create(qsp_decoder* dec, const RefineCfg& cfg, int n_iter, int3
     QSP_HIP(hipSetDevice(dec->device));
     qsp_refine_batch* b = new qsp_refine_batch();
     b->dec = dec;
+    b->grp = grp;
     b->device = dec->device;
     b->code_len = dec->code_len;
     b->cfg = cfg;
@@ -1120,7 +1222,7 @@ static int batch_create(qsp_decoder* dec, const RefineCfg& cfg, int n_iter, int3
         if (e == hipSuccess) e = hipMemset(b->trrot, 0, sizeof(float) * (size_t)cap_hyp * 4);
         if (e != hipSuccess) rc = qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
     }
-    if (!rc) rc = batch_fill(b, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, device_fill);
+    if (!rc) rc = batch_fill(b, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, device_fill, obj_class);
     if (rc) {
         batch_free(b);
         return rc;
@@ -1143,8 +1245,7 @@ extern "C" int qsp_refine_batch_create(qsp_decoder* dec, const qsp_joint_cfg* cf
 extern "C" void qsp_refine_batch_destroy(qsp_refine_batch* b) { batch_free(b); }
 
 extern "C" int qsp_refine_batch_set_state(qsp_refine_batch* b, const float* t_cam_obj, const float* code) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (b && b->dec) lk_d = std::unique_lock<std::recursive_mutex>(b->dec->mu);
+    const CallLock lk(b);
     if (!b || !t_cam_obj) return qsp_fail(QSP_ERR_INVALID, "set_state: bad argument");
     QSP_HIP(hipSetDevice(b->dec->device));
     HypState* hs = (HypState*)b->in_host;      // (the mirror; uploaded by the next run / get)
@@ -1177,9 +1278,14 @@ constexpr float SCREEN_TRUST = 0.5f;
 
 // one pass over n_iter Gauss-Newton iterations on the decoder's current pipes; *hit = a split-fp16 kernel left fp16's range,
 // *screen_hit = the screened forward saw |s1 - s3| above half its margin on a band sample (the margin's premise is in doubt)
+// the kernel a launch of a batch uses: the decoder-group twin for a group's batch
+template <class F>
+static F pick(const qsp_refine_batch* b, F single, F group) { return b->grp ? group : single; }
+
 static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen_hit) {
     bool screened_any = false;
     hipStream_t s = b->dec->stream;
+    const MlpParams* Pm = b->grp ? b->grp->Pd : b->dec->Pd;      // (a group's: one entry per member)
     const int nH = b->n_hyp;
     const int nw_total = b->nw_sdf + (b->cfg.pose_only ? 0 : NW_REND);
     size_t cur = 0;
@@ -1195,7 +1301,8 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
         if (b->dec->jac_bf3 != 2) cfg.tile_p = TILE_P;      // (32-point tiles exist on the split-fp16 pipe only: the f32 repeat of a
                                                             //  batch created for them runs 64-point tiles over the same slots)
         hipEvent_t a = nullptr;
-        if (cfg.pose_only) hipLaunchKernelGGL(k_c0, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->dec->Pd, b->c0_all);
+        if (cfg.pose_only && b->grp) hipLaunchKernelGGL(k_grp_c0, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->objs, Pm, b->c0_all);
+        else if (cfg.pose_only) hipLaunchKernelGGL(k_c0, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->dec->Pd, b->c0_all);
         if (!cfg.pose_only) {      // (k_sample also forms the bias vectors k_c0 forms in pose-only mode)
             if (b->prof) a = next_event(b, cur);
             // Two passes pay when the one-pass kernel would need more than one round of 64-point tiles over the chip; a batch that
@@ -1216,8 +1323,8 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
                                 (b->dec->depth_staging == 2 || (b->dec->depth_staging == 1 && ub_samples > 64 * (int64_t)b->n_cu * H1_ROWS));
             const PlanTail pt_fwd{staged ? nullptr : b->work_fwd, b->qctl, b->qctl + 4, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                   screen ? H1_ROWS : TILE_P, 0};
-            hipLaunchKernelGGL(k_sample, dim3(nH), dim3(SAMPLE_THREADS), 0, s, b->st, b->objs, b->rays, cfg, b->valid_rk, b->rk_stride,
-                               b->ray_voff, b->ray_stride, b->dec->Pd, b->c0_all, pt_fwd);
+            hipLaunchKernelGGL(pick(b, k_sample, k_grp_sample), dim3(nH), dim3(SAMPLE_THREADS), 0, s, b->st, b->objs, b->rays, cfg,
+                               b->valid_rk, b->rk_stride, b->ray_voff, b->ray_stride, Pm, b->c0_all, pt_fwd);
             if (b->prof) spans.push_back({a, next_event(b, cur), 2});
             if (b->prof) a = next_event(b, cur);
             if (screen) {
@@ -1236,34 +1343,34 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
                         stage_list = b->stage_idx;
                     }
                     if (screen_waves() == 8)
-                        hipLaunchKernelGGL(k_mlp_fwd_h1<8>, dim3(b->n_cu), dim3(512), sizeof(MlpSmemH1), s, b->st, b->objs, b->rays,
-                                           cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
+                        hipLaunchKernelGGL(pick(b, k_mlp_fwd_h1<8>, k_grp_mlp_fwd_h1<8>), dim3(b->n_cu), dim3(512), sizeof(MlpSmemH1), s,
+                                           b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                            b->band_idx, cfg.cut_off + b->dec->screen_margin, b->dec->screen_audit, stage_list);
                     else
-                        hipLaunchKernelGGL(k_mlp_fwd_h1<4>, dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmemH1), s, b->st, b->objs, b->rays,
-                                           cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
+                        hipLaunchKernelGGL(pick(b, k_mlp_fwd_h1<4>, k_grp_mlp_fwd_h1<4>), dim3(b->n_cu), dim3(H2_THREADS),
+                                           sizeof(MlpSmemH1), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                            b->band_idx, cfg.cut_off + b->dec->screen_margin, b->dec->screen_audit, stage_list);
                     hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, 2, b->st, b->objs, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                        b->work_fwd, b->qctl, TILE_P);
-                    hipLaunchKernelGGL((k_mlp_fwd_h2<2, false, 4>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, b->st, b->objs, b->rays,
-                                       cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
-                                       (const int32_t*)b->band_idx, (unsigned int*)(b->counters + 5));
+                    hipLaunchKernelGGL(pick(b, k_mlp_fwd_h2<2, false, 4>, k_grp_mlp_fwd_h2<2, false, 4>), dim3(b->n_cu), dim3(H2_THREADS),
+                                       sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid,
+                                       b->work_fwd, b->qctl, b->c0_all, (const int32_t*)b->band_idx, (unsigned int*)(b->counters + 5));
                 }
                 screened_any = true;
             } else if (b->dec->fwd_bf3 == 2 && b->dec->P.narrow)
-                hipLaunchKernelGGL((k_mlp_fwd_h2<2, true, 8>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, b->st, b->objs, b->rays,
-                                   cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
+                hipLaunchKernelGGL(pick(b, k_mlp_fwd_h2<2, true, 8>, k_grp_mlp_fwd_h2<2, true, 8>), dim3(b->n_cu), dim3(512),
+                                   sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                    (const int32_t*)nullptr, (unsigned int*)nullptr);
             else if (b->dec->fwd_bf3 == 2)
-                hipLaunchKernelGGL((k_mlp_fwd_h2<2, false, 4>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, b->st, b->objs, b->rays,
-                                   cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
+                hipLaunchKernelGGL(pick(b, k_mlp_fwd_h2<2, false, 4>, k_grp_mlp_fwd_h2<2, false, 4>), dim3(b->n_cu), dim3(H2_THREADS),
+                                   sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                    (const int32_t*)nullptr, (unsigned int*)nullptr);
             else if (b->dec->fwd_bf3)
-                hipLaunchKernelGGL(k_mlp_fwd<true>, dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s, b->st, b->objs, b->rays,
-                                   cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
+                hipLaunchKernelGGL(pick(b, k_mlp_fwd<true>, k_grp_mlp_fwd<true>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
+                                   s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
             else
-                hipLaunchKernelGGL(k_mlp_fwd<false>, dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s, b->st, b->objs, b->rays,
-                                   cfg, b->dec->Pd, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
+                hipLaunchKernelGGL(pick(b, k_mlp_fwd<false>, k_grp_mlp_fwd<false>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
+                                   s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
             if (b->prof) spans.push_back({a, next_event(b, cur), 1});
             if (b->prof) a = next_event(b, cur);
             // (the Jacobian kernel's item list is built in k_scan's tail)
@@ -1277,33 +1384,33 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
             hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, 1, b->st, b->objs, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                b->work_jtj, b->qctl, cfg.tile_p);
         if (b->dec->jac_bf3 == 2) {
-            const JtjArgs ja{b->st, b->objs, b->pts, b->rays, cfg, b->dec->Pd, b->nw_sdf, nw_total, b->rend_rk, b->rend_deds, b->rend_res,
+            const JtjArgs ja{b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, nw_total, b->rend_rk, b->rend_deds, b->rend_res,
                              b->rk_stride, b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, b->work_jtj,
                              b->qctl, b->c0_all};
             // eight waves of 256 registers (two per SIMD) or four of 512 (one per SIMD): same arithmetic, same bits; jtj_waves()
             // (32-point tiles are the latency option -- one tile deep: there the four-wave form is the shorter chain, 180 us
             //  against 248 per tile; QSP_JTJ_WAVES_T32=8 selects the other for measurements)
             if (b->dec->P.narrow && cfg.tile_p == 32)      // narrow decoders: eight waves, so that the column blocks that exist
-                hipLaunchKernelGGL((k_mlp_jtj_h2<1, 8, true>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);   // spread over all SIMDs
+                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<1, 8, true>, k_grp_mlp_jtj_h2<1, 8, true>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);   // spread over all SIMDs
             else if (b->dec->P.narrow)
-                hipLaunchKernelGGL((k_mlp_jtj_h2<2, 8, true>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<2, 8, true>, k_grp_mlp_jtj_h2<2, 8, true>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
             else if (cfg.tile_p == 32 && jtj_waves_t32() == 8)
-                hipLaunchKernelGGL((k_mlp_jtj_h2<1, 8>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<1, 8>, k_grp_mlp_jtj_h2<1, 8, false>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
             else if (cfg.tile_p == 32)
-                hipLaunchKernelGGL((k_mlp_jtj_h2<1, 4>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<1, 4>, k_grp_mlp_jtj_h2<1, 4, false>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
             else if (jtj_waves() == 8)
-                hipLaunchKernelGGL((k_mlp_jtj_h2<2, 8>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<2, 8>, k_grp_mlp_jtj_h2<2, 8, false>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
             else
-                hipLaunchKernelGGL((k_mlp_jtj_h2<2, 4>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<2, 4>, k_grp_mlp_jtj_h2<2, 4, false>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
         }
         else if (b->dec->jac_bf3)
-            hipLaunchKernelGGL(k_mlp_jtj<true>, dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s, b->st, b->objs, b->pts,
-                               b->rays, cfg, b->dec->Pd, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
+            hipLaunchKernelGGL(pick(b, k_mlp_jtj<true>, k_grp_mlp_jtj<true>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
+                               b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
                                b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
                                b->work_jtj, b->qctl, b->c0_all);
         else
-            hipLaunchKernelGGL(k_mlp_jtj<false>, dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s, b->st, b->objs, b->pts,
-                               b->rays, cfg, b->dec->Pd, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
+            hipLaunchKernelGGL(pick(b, k_mlp_jtj<false>, k_grp_mlp_jtj<false>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
+                               b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
                                b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
                                b->work_jtj, b->qctl, b->c0_all);
         if (b->prof) spans.push_back({a, next_event(b, cur), 0});
@@ -1361,9 +1468,12 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
 }
 
 extern "C" int qsp_refine_batch_run(qsp_refine_batch* b, int32_t n_iter) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (b && b->dec) lk_d = std::unique_lock<std::recursive_mutex>(b->dec->mu);
+    const CallLock lk(b);
     if (!b) return qsp_fail(QSP_ERR_INVALID, "run: null batch");
+    if (b->grp) {      // (a member's options may have changed since the batch was created)
+        const int rc_g = group_check(b->grp);
+        if (rc_g) return rc_g;
+    }
     QSP_HIP(hipSetDevice(b->dec->device));
     if (n_iter <= 0) n_iter = b->n_iter_cfg;
     qsp_decoder* d = b->dec;
@@ -1455,8 +1565,7 @@ static int batch_states(qsp_refine_batch* b, const HypState** out) {
 
 extern "C" int qsp_refine_batch_get(qsp_refine_batch* b, float* t_cam_obj_out, float* code_out, float* loss_out,
                                     uint8_t* is_good_out) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (b && b->dec) lk_d = std::unique_lock<std::recursive_mutex>(b->dec->mu);
+    const CallLock lk(b);
     if (!b) return qsp_fail(QSP_ERR_INVALID, "get: null batch");
     QSP_HIP(hipSetDevice(b->dec->device));
     const HypState* hs = nullptr;
@@ -1478,8 +1587,7 @@ extern "C" int qsp_refine_batch_get(qsp_refine_batch* b, float* t_cam_obj_out, f
 
 extern "C" int qsp_refine_batch_trace(qsp_refine_batch* b, float* H, float* rhs, float* dx, int32_t* n_valid,
                                       int32_t* n_render, float* loss_terms) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (b && b->dec) lk_d = std::unique_lock<std::recursive_mutex>(b->dec->mu);
+    const CallLock lk(b);
     if (!b) return qsp_fail(QSP_ERR_INVALID, "trace: null batch");
     QSP_HIP(hipSetDevice(b->dec->device));
     if (H) QSP_HIP(hipMemcpy(H, b->trH, sizeof(float) * (size_t)b->n_hyp * NH * NH, hipMemcpyDeviceToHost));
@@ -1511,8 +1619,7 @@ extern "C" int qsp_refine_batch_trace_rot(qsp_refine_batch* b, float* rot4) {
 }
 
 extern "C" int qsp_refine_batch_rows(qsp_refine_batch* b, int enable, int32_t hyp, float* rows_sdf, float* rows_render) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (b && b->dec) lk_d = std::unique_lock<std::recursive_mutex>(b->dec->mu);
+    const CallLock lk(b);
     if (!b) return qsp_fail(QSP_ERR_INVALID, "rows: null batch");
     QSP_HIP(hipSetDevice(b->dec->device));
     if (enable && !b->rows) {
@@ -1541,13 +1648,13 @@ extern "C" int qsp_refine_batch_rows(qsp_refine_batch* b, int enable, int32_t hy
     return QSP_OK;
 }
 
-extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cfg, int32_t n_obj, const float* const* pts,
-                                       const int32_t* n_pts, const float* const* rays, const int32_t* n_rays,
-                                       const float* const* depth, const int32_t* n_fg, int32_t n_hyp,
-                                       const int32_t* hyp_obj, const float* t_cam_obj, const float* code,
-                                       float* t_cam_obj_out, float* code_out, float* loss_out, uint8_t* is_good_out) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (dec) lk_d = std::unique_lock<std::recursive_mutex>(dec->mu);
+// qsp_reconstruct_objects on a decoder (grp == nullptr, the decoder's resident batch) or on a decoder group (dec = its first
+// member, the group's resident batch; obj_class = the member per object).  The caller holds the locks.
+static int reconstruct_objects(qsp_decoder* dec, qsp_decoder_group* grp, const int32_t* obj_class, const qsp_joint_cfg* cfg,
+                               int32_t n_obj, const float* const* pts, const int32_t* n_pts, const float* const* rays,
+                               const int32_t* n_rays, const float* const* depth, const int32_t* n_fg, int32_t n_hyp,
+                               const int32_t* hyp_obj, const float* t_cam_obj, const float* code, float* t_cam_obj_out,
+                               float* code_out, float* loss_out, uint8_t* is_good_out) {
     if (!dec || !cfg) return qsp_fail(QSP_ERR_INVALID, "qsp_reconstruct_objects: null argument");
     if (cfg->code_len != dec->code_len) return qsp_fail(QSP_ERR_INVALID, "code_len of the optimizer config differs from the decoder's");
     if (n_obj <= 0 || n_hyp <= 0 || !pts || !n_pts || !rays || !n_rays || !depth || !n_fg || !hyp_obj)
@@ -1561,7 +1668,10 @@ extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cf
     // (depth samples, tile size) are the same; the weights of the cost terms are launch arguments and simply replaced.  Otherwise
     // it is rebuilt with a quarter of head-room over the larger of (this call, what it held): a high-water mark, so a sequence
     // of objects of varying size settles after a few calls.  Results do not depend on the capacities (tests/test_gpu_latency.py).
-    qsp_refine_batch* b = dec->arena;
+    qsp_refine_batch*& arena = grp ? grp->arena : dec->arena;
+    int64_t& n_arena_create = grp ? grp->n_arena_create : dec->n_arena_create;
+    int64_t& n_arena_reuse = grp ? grp->n_arena_reuse : dec->n_arena_reuse;
+    qsp_refine_batch* b = arena;
     if (b && (b->cfg.n_depth != c.n_depth || b->tile_p_created != dec->tile_p || b->cfg.pose_only || !batch_fits(b, need))) {
         BatchCaps grow = need;
         grow.obj = std::max(need.obj, b->cap_obj);
@@ -1572,7 +1682,7 @@ extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cf
         grow.rays_total = std::max(need.rays_total, b->cap_rays_total);
         need = grow;
         batch_free(b);
-        b = dec->arena = nullptr;
+        b = arena = nullptr;
     }
     if (!b) {
         BatchCaps caps = need;
@@ -1583,10 +1693,11 @@ extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cf
         caps.rays_total += caps.rays_total / 4;
         caps.pts_total = std::max<int64_t>(caps.pts_total, (int64_t)caps.max_pts);
         caps.rays_total = std::max<int64_t>(caps.rays_total, (int64_t)caps.max_rays);
-        rc = batch_create(dec, c, cfg->n_iter, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, &b, false, &caps);
+        rc = batch_create(dec, c, cfg->n_iter, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, &b, false, &caps, grp,
+                          obj_class);
         if (rc) return rc;
-        dec->arena = b;
-        dec->n_arena_create++;
+        arena = b;
+        n_arena_create++;
     } else {
         QSP_HIP(hipSetDevice(dec->device));
         const int tile_p = b->cfg.tile_p;
@@ -1594,9 +1705,9 @@ extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cf
         b->cfg.code_len = dec->code_len;
         b->cfg.tile_p = tile_p;
         b->n_iter_cfg = cfg->n_iter;
-        rc = batch_fill(b, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, false);
+        rc = batch_fill(b, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, false, obj_class);
         if (rc) return rc;
-        dec->n_arena_reuse++;
+        n_arena_reuse++;
     }
     rc = qsp_refine_batch_set_state(b, t_cam_obj, code);
     if (!rc) rc = qsp_refine_batch_run(b, 0);
@@ -1604,11 +1715,20 @@ extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cf
     return rc;
 }
 
-extern "C" int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_se3, const float* scale,
-                                 const float* const* pts, const int32_t* n_pts, const float* code, int32_t n_iter,
-                                 float* t_co_out) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (dec) lk_d = std::unique_lock<std::recursive_mutex>(dec->mu);
+extern "C" int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cfg, int32_t n_obj, const float* const* pts,
+                                       const int32_t* n_pts, const float* const* rays, const int32_t* n_rays,
+                                       const float* const* depth, const int32_t* n_fg, int32_t n_hyp,
+                                       const int32_t* hyp_obj, const float* t_cam_obj, const float* code,
+                                       float* t_cam_obj_out, float* code_out, float* loss_out, uint8_t* is_good_out) {
+    const CallLock lk(dec);
+    return reconstruct_objects(dec, nullptr, nullptr, cfg, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, t_cam_obj,
+                               code, t_cam_obj_out, code_out, loss_out, is_good_out);
+}
+
+// qsp_estimate_pose on a decoder or a decoder group (see reconstruct_objects); the caller holds the locks
+static int estimate_pose(qsp_decoder* dec, qsp_decoder_group* grp, const int32_t* obj_class, int32_t n, const float* t_co_se3,
+                         const float* scale, const float* const* pts, const int32_t* n_pts, const float* code, int32_t n_iter,
+                         float* t_co_out) {
     if (!dec || n <= 0 || !t_co_se3 || !scale || !pts || !n_pts || !code || !t_co_out)
         return qsp_fail(QSP_ERR_INVALID, "qsp_estimate_pose: bad argument");
     if (n_iter <= 0) n_iter = 5;
@@ -1618,7 +1738,8 @@ extern "C" int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_
     std::vector<int32_t> hyp(n);
     for (int i = 0; i < n; ++i) hyp[i] = i;
     qsp_refine_batch* b = nullptr;
-    int rc = batch_create(dec, c, n_iter, n, pts, n_pts, nullptr, nullptr, nullptr, nullptr, n, hyp.data(), &b);
+    int rc = batch_create(dec, c, n_iter, n, pts, n_pts, nullptr, nullptr, nullptr, nullptr, n, hyp.data(), &b, false, nullptr, grp,
+                          obj_class);
     if (rc) return rc;
     // bake the scale into the pose: t_cam_obj[:3,:3] *= scale   (optimizer.py:57-58)
     std::vector<float> T((size_t)n * 16);
@@ -1639,6 +1760,96 @@ extern "C" int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_
         }
     qsp_refine_batch_destroy(b);
     return rc;
+}
+
+extern "C" int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_se3, const float* scale,
+                                 const float* const* pts, const int32_t* n_pts, const float* code, int32_t n_iter,
+                                 float* t_co_out) {
+    const CallLock lk(dec);
+    return estimate_pose(dec, nullptr, nullptr, n, t_co_se3, scale, pts, n_pts, code, n_iter, t_co_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// decoder groups
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int qsp_decoder_group_create(qsp_decoder* const* decs, int32_t n, qsp_decoder_group** out) {
+    if (!decs || !out) return qsp_fail(QSP_ERR_INVALID, "qsp_decoder_group_create: null argument");
+    if (n < 1 || n > QSP_GROUP_MAX) return qsp_fail(QSP_ERR_INVALID, "decoder group: 1..16 members");
+    for (int i = 0; i < n; ++i)
+        if (!decs[i]) return qsp_fail(QSP_ERR_INVALID, "decoder group: null member");
+    qsp_decoder_group* g = new qsp_decoder_group();
+    g->m.assign(decs, decs + n);
+    g->lock_order = g->m;
+    std::sort(g->lock_order.begin(), g->lock_order.end(), std::less<qsp_decoder*>());
+    g->lock_order.erase(std::unique(g->lock_order.begin(), g->lock_order.end()), g->lock_order.end());
+    g->device = decs[0]->device;
+    int rc = QSP_OK;
+    {
+        const CallLock lk(g);
+        rc = group_options(g);
+        if (!rc) {
+            hipError_t e = hipSetDevice(g->device);
+            if (e == hipSuccess) e = hipMalloc((void**)&g->Pd, sizeof(MlpParams) * n);
+            if (e != hipSuccess) rc = qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
+        }
+        if (!rc) rc = group_check(g);
+    }
+    if (rc) {
+        qsp_decoder_group_destroy(g);
+        return rc;
+    }
+    *out = g;
+    return QSP_OK;
+}
+
+extern "C" void qsp_decoder_group_destroy(qsp_decoder_group* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    if (g->arena) batch_free(g->arena);
+    if (g->Pd) (void)hipFree(g->Pd);
+    delete g;
+}
+
+extern "C" int qsp_refine_batch_create_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, int32_t n_obj, const float* const* pts,
+                                             const int32_t* n_pts, const float* const* rays, const int32_t* n_rays,
+                                             const float* const* depth, const int32_t* n_fg, const int32_t* obj_class, int32_t n_hyp,
+                                             const int32_t* hyp_obj, qsp_refine_batch** out) {
+    if (!g || !cfg) return qsp_fail(QSP_ERR_INVALID, "qsp_refine_batch_create_group: null argument");
+    const CallLock lk(g);
+    int rc = group_check(g);
+    if (!rc && n_obj > 0) rc = group_classes(g, n_obj, obj_class);
+    if (rc) return rc;
+    qsp_decoder* dec = g->m[0];
+    if (cfg->code_len != dec->code_len) return qsp_fail(QSP_ERR_INVALID, "code_len of the optimizer config differs from the decoders'");
+    RefineCfg c{cfg->k1, cfg->k2, cfg->k3, cfg->k4, cfg->b1, cfg->b2, cfg->lr, cfg->s_damp, cfg->cut_off, cfg->n_depth, 0, 0,
+                dec->code_len};
+    return batch_create(dec, c, cfg->n_iter, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, out, false, nullptr, g,
+                        obj_class);
+}
+
+extern "C" int qsp_reconstruct_objects_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, int32_t n_obj, const float* const* pts,
+                                             const int32_t* n_pts, const float* const* rays, const int32_t* n_rays,
+                                             const float* const* depth, const int32_t* n_fg, const int32_t* obj_class, int32_t n_hyp,
+                                             const int32_t* hyp_obj, const float* t_cam_obj, const float* code,
+                                             float* t_cam_obj_out, float* code_out, float* loss_out, uint8_t* is_good_out) {
+    if (!g) return qsp_fail(QSP_ERR_INVALID, "qsp_reconstruct_objects_group: null group");
+    const CallLock lk(g);
+    int rc = group_check(g);
+    if (!rc && n_obj > 0) rc = group_classes(g, n_obj, obj_class);
+    if (rc) return rc;
+    return reconstruct_objects(g->m[0], g, obj_class, cfg, n_obj, pts, n_pts, rays, n_rays, depth, n_fg, n_hyp, hyp_obj, t_cam_obj,
+                               code, t_cam_obj_out, code_out, loss_out, is_good_out);
+}
+
+extern "C" int qsp_estimate_pose_group(qsp_decoder_group* g, int32_t n, const float* t_co_se3, const float* scale,
+                                       const float* const* pts, const int32_t* n_pts, const float* code, const int32_t* obj_class,
+                                       int32_t n_iter, float* t_co_out) {
+    if (!g) return qsp_fail(QSP_ERR_INVALID, "qsp_estimate_pose_group: null group");
+    const CallLock lk(g);
+    int rc = group_check(g);
+    if (!rc && n > 0) rc = group_classes(g, n, obj_class);
+    if (rc) return rc;
+    return estimate_pose(g->m[0], g, obj_class, n, t_co_se3, scale, pts, n_pts, code, n_iter, t_co_out);
 }
 
 #if (QSP_EXP_VARIANT & 16)

@@ -252,3 +252,34 @@ class DeepSdfDecoder(object):
         _lib.check(_lib.lib().qsp_sdf_value_grad(self.handle, _lib.fptr(code), _lib.fptr(x), x.shape[0], _lib.fptr(y),
                                                  _lib.fptr(g)))
         return y, g
+
+
+class DecoderGroup(object):
+    """Owns a qsp_decoder_group*: an ordered set of decoders, one per class (include/qsp_hip.h, "Decoder groups").  The
+    group entry points refine the objects of all classes in one batch; member i is class index i.  The members must
+    outlive the group (it keeps references to them)."""
+
+    def __init__(self, decoders):
+        decoders = list(decoders)
+        if not decoders:
+            raise ValueError("a decoder group needs at least one decoder")
+        self.decoders = decoders
+        self.code_len = decoders[0].code_len
+        hs = (C.c_void_p * len(decoders))(*[d.handle for d in decoders])
+        h = C.c_void_p()
+        _lib.check(_lib.lib().qsp_decoder_group_create(C.cast(hs, C.POINTER(C.c_void_p)), len(decoders), C.byref(h)))
+        self.handle = h
+
+    def __len__(self):
+        return len(self.decoders)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.lib().qsp_decoder_group_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

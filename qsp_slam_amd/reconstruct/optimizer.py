@@ -3,7 +3,8 @@ types and failure behaviour; the numerics are batched HIP launches behind the C-
 
 Added on top of the reference interface (not replacing it): `reconstruct_objects_batched`, which runs many objects x
 yaw-flip hypotheses in one resident batch -- what src/LocalMapping_util.cc:705-760 does as 4 serial Python calls per
-object."""
+object -- and `OptimizerGroup`, the reference's per-class optimizers (src/LocalMapping.cc:33-69) refining the objects of
+all classes in one batch over a decoder group."""
 import ctypes as C
 import math
 import time
@@ -36,9 +37,26 @@ def _flip_rotation(T, k, flip_angle):
     return Tk
 
 
-def _reconstruct_objects(decoder, cfg, pts, rays, depth, hyp_obj, t_cam_obj, code):
+def _is_group(decoder):
+    from ..decoder import DecoderGroup
+    return isinstance(decoder, DecoderGroup)
+
+
+def _classes(decoder, n, obj_class):
+    """the int32 class index array of a group call (None for a single decoder); range checks are the library's"""
+    if not _is_group(decoder):
+        if obj_class is not None:
+            raise ValueError("obj_class needs a DecoderGroup")
+        return None
+    if obj_class is None or len(obj_class) != n:
+        raise ValueError("a DecoderGroup needs one class index per object")
+    return np.ascontiguousarray(obj_class, dtype=np.int32)
+
+
+def _reconstruct_objects(decoder, cfg, pts, rays, depth, hyp_obj, t_cam_obj, code, obj_class=None):
     """qsp_reconstruct_objects: one call = fill + set_state + run + get on the batch that stays resident with the decoder (no device
-    allocation per call once its capacities have settled) -- the reference's call pattern, src/LocalMapping_util.cc:705-760"""
+    allocation per call once its capacities have settled) -- the reference's call pattern, src/LocalMapping_util.cc:705-760.
+    decoder may be a DecoderGroup: then obj_class gives each object's class (qsp_reconstruct_objects_group)."""
     n_hyp = len(hyp_obj)
     L = decoder.code_len
     pts = [_lib.f32c(p).reshape(-1, 3) for p in pts]
@@ -55,18 +73,23 @@ def _reconstruct_objects(decoder, cfg, pts, rays, depth, hyp_obj, t_cam_obj, cod
     c = np.empty((n_hyp, L), np.float32)
     loss = np.empty(n_hyp, np.float32)
     good = np.empty(n_hyp, np.uint8)
-    _lib.check(_lib.lib().qsp_reconstruct_objects(
-        decoder.handle, C.byref(cfg), len(pts), C.cast(pp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_pts),
-        C.cast(rp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_rays), C.cast(dp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_fg),
-        n_hyp, _lib.i32ptr(hyp), _lib.fptr(T0), _lib.fptr(c0) if c0 is not None else _lib.c_float_p(), _lib.fptr(T), _lib.fptr(c),
-        _lib.fptr(loss), _lib.u8ptr(good)))
+    cls = _classes(decoder, len(pts), obj_class)
+    head = (decoder.handle, C.byref(cfg), len(pts), C.cast(pp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_pts),
+            C.cast(rp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_rays), C.cast(dp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_fg))
+    tail = (n_hyp, _lib.i32ptr(hyp), _lib.fptr(T0), _lib.fptr(c0) if c0 is not None else _lib.c_float_p(), _lib.fptr(T), _lib.fptr(c),
+            _lib.fptr(loss), _lib.u8ptr(good))
+    if cls is None:
+        _lib.check(_lib.lib().qsp_reconstruct_objects(*(head + tail)))
+    else:
+        _lib.check(_lib.lib().qsp_reconstruct_objects_group(*(head + (_lib.i32ptr(cls),) + tail)))
     return T, c, loss, good.astype(bool)
 
 
 class RefineBatch(object):
-    """Thin owner of a qsp_refine_batch* (resident device batch)."""
+    """Thin owner of a qsp_refine_batch* (resident device batch).  `decoder` may be a DecoderGroup: obj_class[o] is then the
+    class (member index) of object o (qsp_refine_batch_create_group)."""
 
-    def __init__(self, decoder, cfg, pts, rays, depth, hyp_obj):
+    def __init__(self, decoder, cfg, pts, rays, depth, hyp_obj, obj_class=None):
         L = _lib.lib()
         self.n_obj = len(pts)
         self.n_hyp = len(hyp_obj)
@@ -80,11 +103,13 @@ class RefineBatch(object):
         hyp = np.ascontiguousarray(hyp_obj, dtype=np.int32)
         pp, rp, dp = _lib.ptr_array(self._pts), _lib.ptr_array(self._rays), _lib.ptr_array(self._depth)
         h = C.c_void_p()
-        _lib.check(L.qsp_refine_batch_create(decoder.handle, C.byref(cfg), self.n_obj,
-                                             C.cast(pp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_pts),
-                                             C.cast(rp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_rays),
-                                             C.cast(dp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_fg),
-                                             self.n_hyp, _lib.i32ptr(hyp), C.byref(h)))
+        cls = _classes(decoder, self.n_obj, obj_class)
+        head = (decoder.handle, C.byref(cfg), self.n_obj, C.cast(pp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_pts),
+                C.cast(rp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_rays), C.cast(dp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_fg))
+        if cls is None:
+            _lib.check(L.qsp_refine_batch_create(*(head + (self.n_hyp, _lib.i32ptr(hyp), C.byref(h)))))
+        else:
+            _lib.check(L.qsp_refine_batch_create_group(*(head + (_lib.i32ptr(cls), self.n_hyp, _lib.i32ptr(hyp), C.byref(h)))))
         self.handle = h
         self.decoder = decoder
 
@@ -191,40 +216,7 @@ class Optimizer(object):
         select=True  -> list (per object) of the result the reference's selection rule keeps
                         (LocalMapping_util.cc:748-752: replace if the kept one is not good, or if the new one is good
                         and has a smaller loss)."""
-        n_obj = len(objects)
-        hyp_obj, T0, codes = [], [], []
-        any_code = any(o.get("code") is not None for o in objects)
-        for i, o in enumerate(objects):
-            T = np.asarray(o["t_cam_obj"], dtype=np.float32).reshape(4, 4)
-            for k in range(flip_sample_num):
-                Tk = _flip_rotation(T, k, 2.0 * math.pi / flip_sample_num)
-                hyp_obj.append(i)
-                T0.append(Tk)
-                c0 = o.get("code")
-                codes.append(np.zeros(self.code_len, np.float32) if c0 is None
-                             else np.asarray(c0, np.float32)[: self.code_len])
-        T, code, loss, good = _reconstruct_objects(self.decoder, _joint_cfg(self), [o["pts"] for o in objects],
-                                                   [o["rays"] for o in objects], [o["depth"] for o in objects], hyp_obj,
-                                                   np.stack(T0), np.stack(codes) if any_code else None)
-        out = []
-        for i in range(n_obj):
-            res = []
-            for k in range(flip_sample_num):
-                h = i * flip_sample_num + k
-                if good[h]:
-                    res.append(ForceKeyErrorDict(t_cam_obj=T[h].copy(), code=code[h].copy(), is_good=True,
-                                                 loss=float(loss[h])))
-                else:
-                    res.append(ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[h])))
-            if select:
-                best = res[0]
-                for r in res[1:]:
-                    if (not best.is_good) or (r.is_good and r.loss < best.loss):
-                        best = r
-                out.append(best)
-            else:
-                out.append(res)
-        return out
+        return _reconstruct_batched(self, self.decoder, objects, flip_sample_num, select, None)
 
     # ---- the caller's loop around reconstruct_object, on the device (SURVEY.md 8f row 3) ---------------------------------
     def refine_detections(self, detections, flip_sample_num=4, taps=False):
@@ -236,81 +228,197 @@ class Optimizer(object):
             bg_rays (B,3), found_good_orientation (bool, default False -> flip_sample_num hypotheses, else one).
         Returns per detection the object the reference keeps in pyMapObjectLeastLoss (t_cam_obj None when not good), with
         the extra keys kept_flip and losses; taps=True adds the assembled pts / rays / depth / initial poses."""
-        n = len(detections)
-        f = _lib.f32c
-
-        def cat(key, width):
-            arrs = [f(d[key]).reshape(-1, width) for d in detections]
-            off = np.zeros(n + 1, np.int32)
-            off[1:] = np.cumsum([a.shape[0] for a in arrs])
-            flat = np.concatenate(arrs, axis=0) if off[-1] else np.zeros((1, width), np.float32)
-            return off, np.ascontiguousarray(flat)
-
-        pts_off, pts_world = cat("pts_world", 3)
-        fg_off, fg_px = cat("fg_px", 2)
-        fg_off2, fg_world = cat("fg_world", 3)
-        if not np.array_equal(fg_off, fg_off2):
-            raise ValueError("fg_px and fg_world must have one row per feature point")
-        bg_off, bg_rays = cat("bg_rays", 3)
-        T_cw = f(np.stack([np.asarray(d["T_cw"], np.float32).reshape(4, 4) for d in detections]))
-        T_wo = f(np.stack([np.asarray(d["T_wo"], np.float32).reshape(4, 4) for d in detections]))
-        K = f(np.stack([np.asarray(d["K"], np.float32).reshape(4) for d in detections]))
-        any_code = any(d.get("code") is not None for d in detections)
-        code = f(np.stack([np.zeros(self.code_len, np.float32) if d.get("code") is None
-                           else np.asarray(d["code"], np.float32)[: self.code_len] for d in detections]))
-        n_flip = np.array([1 if d.get("found_good_orientation") else int(flip_sample_num) for d in detections], np.int32)
-        n_hyp = int(n_flip.sum())
-        inp = _lib.Detections(n, _lib.fptr(T_cw), _lib.fptr(K), _lib.fptr(T_wo),
-                              _lib.fptr(code) if any_code else _lib.c_float_p(), _lib.i32ptr(n_flip),
-                              2.0 * math.pi / float(flip_sample_num), _lib.i32ptr(pts_off), _lib.fptr(pts_world),
-                              _lib.i32ptr(fg_off), _lib.fptr(fg_px), _lib.fptr(fg_world), _lib.i32ptr(bg_off),
-                              _lib.fptr(bg_rays))
-        T = np.empty((n, 4, 4), np.float32)
-        c_out = np.empty((n, self.code_len), np.float32)
-        loss = np.empty(n, np.float32)
-        good = np.empty(n, np.uint8)
-        kept = np.empty(n, np.int32)
-        losses = np.empty(n_hyp, np.float32)
-        res = _lib.DetectionResults(_lib.fptr(T), _lib.fptr(c_out), _lib.fptr(loss), _lib.u8ptr(good), _lib.i32ptr(kept),
-                                    _lib.fptr(losses))
-        if taps:
-            t_pts = np.empty((max(int(pts_off[-1]), 1), 3), np.float32)
-            t_rays = np.empty((max(int(fg_off[-1] + bg_off[-1]), 1), 3), np.float32)
-            t_depth = np.empty(max(int(fg_off[-1]), 1), np.float32)
-            t_init = np.empty((n_hyp, 4, 4), np.float32)
-            res.pts_cam, res.rays, res.depth_obs, res.t_cam_obj_init = (_lib.fptr(t_pts), _lib.fptr(t_rays),
-                                                                        _lib.fptr(t_depth), _lib.fptr(t_init))
-        _lib.check(_lib.lib().qsp_refine_detections(self.decoder.handle, C.byref(_joint_cfg(self)), C.byref(inp),
-                                                    C.byref(res)))
-        out = []
-        hyp_off = np.concatenate([[0], np.cumsum(n_flip)])
-        ray_off = fg_off + bg_off
-        for i in range(n):
-            r = ForceKeyErrorDict(t_cam_obj=T[i].copy() if good[i] else None, code=c_out[i].copy() if good[i] else None,
-                                  is_good=bool(good[i]), loss=float(loss[i]), kept_flip=int(kept[i]),
-                                  losses=losses[hyp_off[i]:hyp_off[i + 1]].copy())
-            if taps:
-                r["pts"] = t_pts[pts_off[i]:pts_off[i + 1]].copy()
-                r["rays"] = t_rays[ray_off[i]:ray_off[i + 1]].copy()
-                r["depth"] = t_depth[fg_off[i]:fg_off[i + 1]].copy()
-                r["t_cam_obj_init"] = t_init[hyp_off[i]:hyp_off[i + 1]].copy()
-            out.append(r)
-        return out
+        return _refine_detections(self, self.decoder, detections, flip_sample_num, taps, None)
 
     def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code):
         """reconstruct/optimizer.py:47-93 -> (4,4) float32 SE3 (the reference returns a torch tensor that C++ casts to
         Eigen::Matrix4f, src/LocalMapping_util.cc:139-140; a numpy array casts the same way)."""
-        T = _lib.f32c(t_co_se3).reshape(1, 16)
-        sc = np.array([scale], np.float32)
-        p = _lib.f32c(pts).reshape(-1, 3)
-        n = np.array([p.shape[0]], np.int32)
-        c = _lib.f32c(np.asarray(code)[: self.code_len]).reshape(1, -1)
-        out = np.empty((1, 4, 4), np.float32)
-        pp = _lib.ptr_array([p])
-        _lib.check(_lib.lib().qsp_estimate_pose(self.decoder.handle, 1, _lib.fptr(T), _lib.fptr(sc),
-                                                C.cast(pp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n), _lib.fptr(c),
-                                                int(getattr(self, "num_iterations_pose_only", 5)), _lib.fptr(out)))
-        return out[0]
+        return _estimate_pose(self, self.decoder, [dict(t_co_se3=t_co_se3, scale=scale, pts=pts, code=code)], None)[0]
+
+
+def _reconstruct_batched(self, target, objects, flip_sample_num, select, classes):
+    """Optimizer.reconstruct_objects_batched on `target` (a decoder, or a DecoderGroup with one class per object)"""
+    n_obj = len(objects)
+    hyp_obj, T0, codes = [], [], []
+    any_code = any(o.get("code") is not None for o in objects)
+    for i, o in enumerate(objects):
+        T = np.asarray(o["t_cam_obj"], dtype=np.float32).reshape(4, 4)
+        for k in range(flip_sample_num):
+            Tk = _flip_rotation(T, k, 2.0 * math.pi / flip_sample_num)
+            hyp_obj.append(i)
+            T0.append(Tk)
+            c0 = o.get("code")
+            codes.append(np.zeros(self.code_len, np.float32) if c0 is None
+                         else np.asarray(c0, np.float32)[: self.code_len])
+    T, code, loss, good = _reconstruct_objects(target, _joint_cfg(self), [o["pts"] for o in objects],
+                                               [o["rays"] for o in objects], [o["depth"] for o in objects], hyp_obj,
+                                               np.stack(T0), np.stack(codes) if any_code else None, classes)
+    out = []
+    for i in range(n_obj):
+        res = []
+        for k in range(flip_sample_num):
+            h = i * flip_sample_num + k
+            if good[h]:
+                res.append(ForceKeyErrorDict(t_cam_obj=T[h].copy(), code=code[h].copy(), is_good=True,
+                                             loss=float(loss[h])))
+            else:
+                res.append(ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(loss[h])))
+        if select:
+            best = res[0]
+            for r in res[1:]:
+                if (not best.is_good) or (r.is_good and r.loss < best.loss):
+                    best = r
+            out.append(best)
+        else:
+            out.append(res)
+    return out
+
+
+def _refine_detections(self, target, detections, flip_sample_num, taps, classes):
+    """Optimizer.refine_detections on `target` (a decoder, or a DecoderGroup with one class per detection)"""
+    n = len(detections)
+    f = _lib.f32c
+
+    def cat(key, width):
+        arrs = [f(d[key]).reshape(-1, width) for d in detections]
+        off = np.zeros(n + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in arrs])
+        flat = np.concatenate(arrs, axis=0) if off[-1] else np.zeros((1, width), np.float32)
+        return off, np.ascontiguousarray(flat)
+
+    pts_off, pts_world = cat("pts_world", 3)
+    fg_off, fg_px = cat("fg_px", 2)
+    fg_off2, fg_world = cat("fg_world", 3)
+    if not np.array_equal(fg_off, fg_off2):
+        raise ValueError("fg_px and fg_world must have one row per feature point")
+    bg_off, bg_rays = cat("bg_rays", 3)
+    T_cw = f(np.stack([np.asarray(d["T_cw"], np.float32).reshape(4, 4) for d in detections]))
+    T_wo = f(np.stack([np.asarray(d["T_wo"], np.float32).reshape(4, 4) for d in detections]))
+    K = f(np.stack([np.asarray(d["K"], np.float32).reshape(4) for d in detections]))
+    any_code = any(d.get("code") is not None for d in detections)
+    code = f(np.stack([np.zeros(self.code_len, np.float32) if d.get("code") is None
+                       else np.asarray(d["code"], np.float32)[: self.code_len] for d in detections]))
+    n_flip = np.array([1 if d.get("found_good_orientation") else int(flip_sample_num) for d in detections], np.int32)
+    n_hyp = int(n_flip.sum())
+    inp = _lib.Detections(n, _lib.fptr(T_cw), _lib.fptr(K), _lib.fptr(T_wo),
+                          _lib.fptr(code) if any_code else _lib.c_float_p(), _lib.i32ptr(n_flip),
+                          2.0 * math.pi / float(flip_sample_num), _lib.i32ptr(pts_off), _lib.fptr(pts_world),
+                          _lib.i32ptr(fg_off), _lib.fptr(fg_px), _lib.fptr(fg_world), _lib.i32ptr(bg_off),
+                          _lib.fptr(bg_rays))
+    T = np.empty((n, 4, 4), np.float32)
+    c_out = np.empty((n, self.code_len), np.float32)
+    loss = np.empty(n, np.float32)
+    good = np.empty(n, np.uint8)
+    kept = np.empty(n, np.int32)
+    losses = np.empty(n_hyp, np.float32)
+    res = _lib.DetectionResults(_lib.fptr(T), _lib.fptr(c_out), _lib.fptr(loss), _lib.u8ptr(good), _lib.i32ptr(kept),
+                                _lib.fptr(losses))
+    if taps:
+        t_pts = np.empty((max(int(pts_off[-1]), 1), 3), np.float32)
+        t_rays = np.empty((max(int(fg_off[-1] + bg_off[-1]), 1), 3), np.float32)
+        t_depth = np.empty(max(int(fg_off[-1]), 1), np.float32)
+        t_init = np.empty((n_hyp, 4, 4), np.float32)
+        res.pts_cam, res.rays, res.depth_obs, res.t_cam_obj_init = (_lib.fptr(t_pts), _lib.fptr(t_rays),
+                                                                    _lib.fptr(t_depth), _lib.fptr(t_init))
+    if classes is None:
+        _lib.check(_lib.lib().qsp_refine_detections(target.handle, C.byref(_joint_cfg(self)), C.byref(inp), C.byref(res)))
+    else:
+        cls = _classes(target, n, classes)
+        _lib.check(_lib.lib().qsp_refine_detections_group(target.handle, C.byref(_joint_cfg(self)), C.byref(inp),
+                                                          _lib.i32ptr(cls), C.byref(res)))
+    out = []
+    hyp_off = np.concatenate([[0], np.cumsum(n_flip)])
+    ray_off = fg_off + bg_off
+    for i in range(n):
+        r = ForceKeyErrorDict(t_cam_obj=T[i].copy() if good[i] else None, code=c_out[i].copy() if good[i] else None,
+                              is_good=bool(good[i]), loss=float(loss[i]), kept_flip=int(kept[i]),
+                              losses=losses[hyp_off[i]:hyp_off[i + 1]].copy())
+        if taps:
+            r["pts"] = t_pts[pts_off[i]:pts_off[i + 1]].copy()
+            r["rays"] = t_rays[ray_off[i]:ray_off[i + 1]].copy()
+            r["depth"] = t_depth[fg_off[i]:fg_off[i + 1]].copy()
+            r["t_cam_obj_init"] = t_init[hyp_off[i]:hyp_off[i + 1]].copy()
+        out.append(r)
+    return out
+
+
+def _estimate_pose(self, target, items, classes):
+    """Optimizer.estimate_pose_cam_obj over a list of dicts(t_co_se3, scale, pts, code) in one call on `target` (a decoder, or
+    a DecoderGroup with one class per item) -> list of (4,4) float32"""
+    n = len(items)
+    T = _lib.f32c(np.stack([np.asarray(it["t_co_se3"], np.float32).reshape(16) for it in items]))
+    sc = np.array([it["scale"] for it in items], np.float32)
+    ps = [_lib.f32c(it["pts"]).reshape(-1, 3) for it in items]
+    n_pts = np.array([p.shape[0] for p in ps], np.int32)
+    c = _lib.f32c(np.stack([np.asarray(it["code"], np.float32).reshape(-1)[: self.code_len] for it in items]))
+    out = np.empty((n, 4, 4), np.float32)
+    pp = _lib.ptr_array(ps)
+    head = (target.handle, n, _lib.fptr(T), _lib.fptr(sc), C.cast(pp, C.POINTER(_lib.c_float_p)), _lib.i32ptr(n_pts), _lib.fptr(c))
+    tail = (int(getattr(self, "num_iterations_pose_only", 5)), _lib.fptr(out))
+    if classes is None:
+        _lib.check(_lib.lib().qsp_estimate_pose(*(head + tail)))
+    else:
+        cls = _classes(target, n, classes)
+        _lib.check(_lib.lib().qsp_estimate_pose_group(*(head + (_lib.i32ptr(cls),) + tail)))
+    return [out[i] for i in range(n)]
+
+
+class OptimizerGroup(object):
+    """The reference's per-class optimizers (src/LocalMapping.cc:33-69: one Optimizer per class id of pSys->mmPyDecoders)
+    refining the objects of ALL classes in one batch over a decoder group (include/qsp_hip.h, "Decoder groups") instead of
+    one call per class.  `optimizers` = {class_id: Optimizer}; every object / detection dict carries a "class_id".  The
+    reference assumes that all class decoders have the same code length and optimiser parameters (LocalMapping.cc:47): so
+    does this class -- optimizers whose joint configs differ raise ValueError.  Results come back in input order."""
+
+    def __init__(self, optimizers):
+        if not optimizers:
+            raise ValueError("OptimizerGroup needs at least one optimizer")
+        self.class_ids = sorted(optimizers)
+        self.optimizers = dict(optimizers)
+        first = self.optimizers[self.class_ids[0]]
+
+        def key(o):
+            return (tuple(getattr(_joint_cfg(o), f[0]) for f in _lib.JointCfg._fields_),
+                    int(getattr(o, "num_iterations_pose_only", 5)))
+        for cid in self.class_ids[1:]:
+            if key(self.optimizers[cid]) != key(first):
+                raise ValueError("OptimizerGroup: the joint config of class %r differs from that of class %r (the classes of a "
+                                 "group share code length and optimiser parameters)" % (cid, self.class_ids[0]))
+        self._cfg = first
+        self.code_len = first.code_len
+        self._index = {cid: i for i, cid in enumerate(self.class_ids)}
+        from ..decoder import DecoderGroup
+        self.group = DecoderGroup([self.optimizers[cid].decoder for cid in self.class_ids])
+
+    def _class_index(self, items, what):
+        idx = []
+        for i, it in enumerate(items):
+            if "class_id" not in it:
+                raise ValueError("%s %d has no \"class_id\"" % (what, i))
+            cid = it["class_id"]
+            if cid not in self._index:
+                raise ValueError("%s %d: class_id %r has no optimizer in this group" % (what, i, cid))
+            idx.append(self._index[cid])
+        return np.array(idx, np.int32)
+
+    def reconstruct_objects_batched(self, objects, flip_sample_num=1, select=True):
+        """Optimizer.reconstruct_objects_batched over objects of several classes in one call"""
+        cls = self._class_index(objects, "object")
+        return _reconstruct_batched(self._cfg, self.group, objects, flip_sample_num, select, cls)
+
+    def refine_detections(self, detections, flip_sample_num=4, taps=False):
+        """Optimizer.refine_detections over the detections of several classes in one call: what LocalMapping_util.cc:585-760
+        does per detection with the optimizer of its class"""
+        cls = self._class_index(detections, "detection")
+        return _refine_detections(self._cfg, self.group, detections, flip_sample_num, taps, cls)
+
+    def estimate_pose_cam_obj(self, items):
+        """Optimizer.estimate_pose_cam_obj for a list of dicts(t_co_se3, scale, pts, code, class_id) in one call -> list of (4,4)"""
+        cls = self._class_index(items, "item")
+        return _estimate_pose(self._cfg, self.group, items, cls)
+
+    def close(self):
+        self.group.close()
 
 
 def create_voxel_grid(vol_dim=128):
