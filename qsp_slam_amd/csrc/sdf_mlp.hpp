@@ -1188,7 +1188,9 @@ __device__ __forceinline__ void ringh_prime(WRingH<PF, NCB>& R, const float4* __
 // acc / acc2 [r][c] += image rows [32 r, 32 r + 32) x slabs [0, KS) * W for NCB column blocks; w = base of the first column
 // block, consecutive column blocks `cs` float4 apart, nw / ncs the same for the next GEMM (its first PF slabs are fetched by
 // this one's last iterations).  img = the first row of row block 0.
-template <int KS, int PF, int NCB, int NR, bool HAND = true, bool PRIMED = false, bool RT = false>
+// ONE: the image holds a single exact fp16 plane (the 0/1 backward seed, lo' = 0): two products per term, w_hi m into acc and
+// w_lo' m into acc2; the lo' plane of the image is never read.
+template <int KS, int PF, int NCB, int NR, bool HAND = true, bool PRIMED = false, bool RT = false, bool ONE = false>
 __device__ __forceinline__ void gemm_h2(const _Float16* __restrict__ img, const float4* __restrict__ w_, int cs,
                                         const float4* __restrict__ nw_, int ncs, WRingH<PF, NCB>& R, f32x16 (&acc)[NR][NCB],
                                         f32x16 (&acc2)[NR][NCB], int lane, int ks_run = KS) {
@@ -1219,7 +1221,7 @@ __device__ __forceinline__ void gemm_h2(const _Float16* __restrict__ img, const 
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         bh[0][r] = *reinterpret_cast<const f16x8*>(b_row + r * 32 * LDH);
-        bl[0][r] = *reinterpret_cast<const f16x8*>(b_row + r * 32 * LDH + 8);
+        if (!ONE) bl[0][r] = *reinterpret_cast<const f16x8*>(b_row + r * 32 * LDH + 8);
     }
     // The order below is the issue order (pinned with scheduling barriers: one wave per SIMD, nobody else fills the gaps):
     // a fragment register is refilled right after the last MFMA that reads it -- no second register set, no copies -- and the
@@ -1260,12 +1262,16 @@ __device__ __forceinline__ void gemm_h2(const _Float16* __restrict__ img, const 
                     QSP_LDW(R.q[d][c - 1][0], fb + (c - 1) * fcs + (d * 2 + 0) * 64 * 16, voff);
                 }
                 QSP_PIN
+                if (!ONE) {
 #pragma unroll
-                for (int r = 0; r < NR; ++r) QSP_MFMA_H(acc2[r][c], wh, bl[d & 1][r]);
+                    for (int r = 0; r < NR; ++r) QSP_MFMA_H(acc2[r][c], wh, bl[d & 1][r]);
+                }
                 QSP_PIN
                 if (c == 0) {
+                    if (!ONE) {
 #pragma unroll
-                    for (int r = 0; r < NR; ++r) bl[(d & 1) ^ 1][r] = *reinterpret_cast<const f16x8*>(nb + r * 32 * LDH + 8);
+                        for (int r = 0; r < NR; ++r) bl[(d & 1) ^ 1][r] = *reinterpret_cast<const f16x8*>(nb + r * 32 * LDH + 8);
+                    }
                 } else {
                     QSP_LDW(R.q[d][c - 1][1], fb + (c - 1) * fcs + (d * 2 + 1) * 64 * 16, voff);
                 }
@@ -1576,7 +1582,11 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
     if (threadIdx.x == 0 && blockIdx.x == 0) qsp_h2_nts = hts_n;
 #endif
     if constexpr (BWD) {
-        // ---- backward seed: d y / d a7 = (1 - y^2) * w8[unit] * [a7 > 0] ---------------------------------------------
+        // ---- backward seed: d y / d a7 = dy * w8[unit] * [a7 > 0].  The packed backward matrix of layer 7 is (diag(w8) W7)^T,
+        // so the seed is the mask itself, 1 or 0 in the hi plane (exact: no lo' plane, two products instead of three), and the
+        // per-point factor dy is applied in layer 7's backward write-out.  A narrow decoder whose layer 7 is an identity slot has
+        // no such product: its seed is the gradient itself, split like any activation ----------------------------------------
+        const bool seed_full = NARROW && P.skip[7];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             const int p = 32 * r + (lane & 31);
@@ -1586,13 +1596,18 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int u0 = 32 * NCB * wave + 32 * c + 8 * g + 4 * h;
-                    const f32x4 wv = lds4(s.w8 + u0);
-                    f32x4 v;
+                    if (seed_full) {
+                        const f32x4 wv = lds4(s.w8 + u0);
+                        f32x4 v;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        v[q] = h2_mask_sel(dy * wv[q], mk[7][r][c >> 1], (c & 1) * 16 + 4 * g + q);
+                        for (int q = 0; q < 4; ++q) v[q] = h2_mask_sel(dy * wv[q], mk[7][r][c >> 1], (c & 1) * 16 + 4 * g + q);
+                        h2_store4(img, p, u0, v, amax);
+                    } else {
+                        f16x4 m;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) m[q] = (_Float16)h2_mask_sel(1.f, mk[7][r][c >> 1], (c & 1) * 16 + 4 * g + q);
+                        *reinterpret_cast<f16x4*>(img + h2_at(p, u0)) = m;
                     }
-                    h2_store4(img, p, u0, v, amax);
                 }
         }
         if (!NARROW) ringh_prime(ring, QSP_WBH(7), CS, lane);
@@ -1604,19 +1619,22 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
     _Pragma("unroll") for (int r_ = 0; r_ < NR; ++r_) _Pragma("unroll") for (int c_ = 0; c_ < NCB; ++c_)                 \
         _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) { acc[r_][c_][i_] = 0.f; acc2[r_][c_][i_] = 0.f; }             \
     if constexpr (NARROW)                                                                                                \
-        gemm_h2<KS_, PF, NCB, NR, false, false, true>(img, QSP_WBH(L), CS, QSP_WBH(L), CS, ring, acc, acc2, lane,             \
-                                                      act_ ? min((int)P.ks_out[L], KS_) : 0);                            \
+        gemm_h2<KS_, PF, NCB, NR, false, false, true, (L) == 7>(img, QSP_WBH(L), CS, QSP_WBH(L), CS, ring, acc, acc2, lane,    \
+                                                                act_ ? min((int)P.ks_out[L], KS_) : 0);                  \
     else                                                                                                                 \
-        gemm_h2<KS_, PF, NCB, NR, HAND, true>(img, QSP_WBH(L), CS, NWB, CS, ring, acc, acc2, lane);                        \
+        gemm_h2<KS_, PF, NCB, NR, HAND, true, false, (L) == 7>(img, QSP_WBH(L), CS, NWB, CS, ring, acc, acc2, lane);       \
     QSP_PIN_ACC()                                                                                                        \
     __syncthreads();                                                                                                     \
+    float dyr_[NR];                      /* layer 7: the per-point factor of the 0/1 seed */                             \
+    _Pragma("unroll") for (int r_ = 0; r_ < NR; ++r_) dyr_[r_] = (L) == 7 ? s.dy[32 * r_ + (lane & 31)] : 1.f;           \
     _Pragma("unroll") for (int c_ = 0; c_ < NCB; ++c_) _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) {                \
         const int u0_ = 32 * NCB * wave + 32 * c_ + 8 * g_ + 4 * h;                                                      \
         _Pragma("unroll") for (int r_ = 0; r_ < NR; ++r_) {                                                              \
             const int p_ = 32 * r_ + (lane & 31);                                                                      \
             f32x4 v_;                                                                                                    \
             _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                                           \
-                const float x_ = fmaf(acc2[r_][c_][4 * g_ + q_], 0.00048828125f, acc[r_][c_][4 * g_ + q_]);             \
+                float x_ = fmaf(acc2[r_][c_][4 * g_ + q_], 0.00048828125f, acc[r_][c_][4 * g_ + q_]);                   \
+                if ((L) == 7) x_ *= dyr_[r_];                                                                            \
                 const float m_ = h2_mask_sel(x_, mk[(L) - 1][r_][c_ >> 1], (c_ & 1) * 16 + 4 * g_ + q_);                       \
                 v_[q_] = m_;                                                                                             \
             }                                                                                                            \

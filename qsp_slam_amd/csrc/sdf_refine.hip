@@ -484,7 +484,10 @@ static int pack_weights(qsp_decoder* d, const qsp_decoder_desc* desc) {
             QSP_HIP(hipMemcpy(p3d, p3.data(), p3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
             d->P.wb3[l] = (const float4*)p3d;
         }
-        {   // split-fp16 planes of the same matrix: [col block over inputs k][slab of 16 outputs o][hi | lo'][lane][8 fp16]
+        {   // split-fp16 planes of the same matrix: [col block over inputs k][slab of 16 outputs o][hi | lo'][lane][8 fp16].
+            // Layer 7's is diag(w8) W7: the split tile's backward seed is then the 0/1 ReLU mask of layer 7 (mlp_tile_h2).  (The gain
+            // equalisation scales W7's rows by c and w8 by 1 / c, so this product is what it was; small products may land among
+            // fp16 subnormals, where the split still bounds the absolute error by ~2^-36.)
             const int KS = HID / 16;
             std::vector<_Float16> ph((size_t)NCB * KS * 2 * 64 * 8, (_Float16)0.f);
             for (int cb = 0; cb < NCB; ++cb)
@@ -494,7 +497,7 @@ static int pack_weights(qsp_decoder* d, const qsp_decoder_desc* desc) {
                             const int k = 32 * cb + (lane & 31);
                             const int o = 16 * ks + 8 * (lane >> 5) + j;
                             float v = 0.f;
-                            if (o < out && k < in) v = W[l][(size_t)o * in + k];
+                            if (o < out && k < in) v = l == 7 ? (float)((double)W[8][o] * W[l][(size_t)o * in + k]) : W[l][(size_t)o * in + k];
                             if (!(fabsf(v) < 65000.f)) d->fp16_ok = false;
                             const _Float16 hi = (_Float16)v;
                             const size_t base = (((size_t)cb * KS + ks) * 2) * 64 * 8 + (size_t)lane * 8 + j;
