@@ -10,7 +10,7 @@ SRCS="sdf_refine.hip c_abi.cpp comm_rccl.cpp"
 OBJDIR=../../build/obj
 [ -n "$*" ] && OBJDIR=../../build/obj_variant      # (extra compiler flags = an experiment build: never mixed with the plain objects)
 mkdir -p $OBJDIR
-newest_header=$(ls -t *.hpp *.inc ../../include/*.h build.sh | head -1)
+newest_header=$(ls -t *.hpp ../../include/*.h build.sh | head -1)
 pids=()
 objs=""
 for src in $SRCS; do

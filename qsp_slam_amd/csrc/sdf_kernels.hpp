@@ -81,7 +81,7 @@ struct ObjView {            // per-object observation extents inside the concate
     int64_t pts_off;        // in points
     int64_t ray_off;        // in rays
     int32_t n_pts, n_rays, n_fg;
-    int32_t dec;            // decoder of the object within its decoder group (0 outside a group; read by the k_grp_* kernels only)
+    int32_t dec;            // decoder of the object within its decoder group (0 outside a group; read by the GRP = true kernels only)
 };
 
 struct RefineCfg {
@@ -345,8 +345,11 @@ __device__ __forceinline__ void stage_code_T(MlpSmem& s, const HypState& S, floa
 //   qctl[0] = #items forward, qctl[1] = next forward item, qctl[2] = #items jtj, qctl[3] = next jtj item
 // ---------------------------------------------------------------------------------------------------------------
 // c0[h][u] = b0[u] + sum_k W0[u][k] code_h[k]: layer 0 without its xyz columns (see mlp_prepare), once per hypothesis
-__global__ __launch_bounds__(MLP_THREADS) void k_c0(const HypState* __restrict__ st, const MlpParams* __restrict__ Pm,
-                                                    float* __restrict__ c0_all) {
+// GRP: Pm is a decoder group's parameter array and the hypothesis uses the entry of its object's decoder (ObjView::dec);
+// otherwise objs is not read
+template <bool GRP>
+__global__ __launch_bounds__(MLP_THREADS) void k_c0(const HypState* __restrict__ st, const ObjView* __restrict__ objs,
+                                                    const MlpParams* __restrict__ Pm, float* __restrict__ c0_all) {
     __shared__ float code[CODE_LEN];
     const HypState& S = st[blockIdx.x];
     if (!S.alive) return;
@@ -354,24 +357,10 @@ __global__ __launch_bounds__(MLP_THREADS) void k_c0(const HypState* __restrict__
     __syncthreads();
     const int u = threadIdx.x;
     float a, a4;
-    code_bias(Pm, u, code, a, a4);
+    if constexpr (GRP) code_bias(Pm + objs[S.obj].dec, u, code, a, a4);
+    else code_bias(Pm, u, code, a, a4);
     c0_all[(size_t)blockIdx.x * 2 * HID + u] = a;
     c0_all[(size_t)blockIdx.x * 2 * HID + HID + u] = a4;     // layer 4's bias with the skip connection's code part
-}
-
-// ... for a decoder group: the entry of the hypothesis's decoder (ObjView::dec) of the group's parameter array
-__global__ __launch_bounds__(MLP_THREADS) void k_grp_c0(const HypState* __restrict__ st, const ObjView* __restrict__ objs,
-                                                        const MlpParams* __restrict__ Pg, float* __restrict__ c0_all) {
-    __shared__ float code[CODE_LEN];
-    const HypState& S = st[blockIdx.x];
-    if (!S.alive) return;
-    if (threadIdx.x < CODE_LEN) code[threadIdx.x] = S.code[threadIdx.x];
-    __syncthreads();
-    const int u = threadIdx.x;
-    float a, a4;
-    code_bias(Pg + objs[S.obj].dec, u, code, a, a4);
-    c0_all[(size_t)blockIdx.x * 2 * HID + u] = a;
-    c0_all[(size_t)blockIdx.x * 2 * HID + HID + u] = a4;
 }
 
 // mode 0: forward items (h, tile) over the valid ray samples; mode 1: jtj items (h, slot), surface slots then render slots;
@@ -501,51 +490,92 @@ __global__ __launch_bounds__(1024) void k_plan(int mode, const HypState* __restr
                                                int tile_p) {
     plan_body<1024>(mode, st, objs, n_hyp, nw_sdf, nw_rend, work, qctl, tile_p);
 }
+// GRP: the bias vectors from the hypothesis's decoder (ObjView::dec) of the decoder group's parameter array Pm (the phase
+// marks are the single-decoder form's)
+template <bool GRP>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(HypState* __restrict__ st, const ObjView* __restrict__ objs,
                                                 const float* __restrict__ rays, RefineCfg cfg,
                                                 int32_t* __restrict__ valid_rk, int64_t rk_stride,
                                                 int32_t* __restrict__ ray_voff, int64_t ray_stride,
                                                 const MlpParams* __restrict__ Pm, float* __restrict__ c0_all, PlanTail pt) {
-    PHASE_MARK(0, 0);
-    sample_body(st, objs, rays, cfg, valid_rk, rk_stride, ray_voff, ray_stride, Pm, c0_all);
-    PHASE_MARK(0, 7);
-    plan_tail<SAMPLE_THREADS>(pt, st, objs);        // the forward kernel's item list (k_plan mode 0)
-    PHASE_END(0, 8);
-}
-// ... for a decoder group: the bias vectors from the hypothesis's decoder (ObjView::dec) of the group's parameter array Pm
-__global__ __launch_bounds__(SAMPLE_THREADS) void k_grp_sample(HypState* __restrict__ st, const ObjView* __restrict__ objs,
-                                                    const float* __restrict__ rays, RefineCfg cfg,
-                                                    int32_t* __restrict__ valid_rk, int64_t rk_stride,
-                                                    int32_t* __restrict__ ray_voff, int64_t ray_stride,
-                                                    const MlpParams* __restrict__ Pm, float* __restrict__ c0_all, PlanTail pt) {
-    sample_body(st, objs, rays, cfg, valid_rk, rk_stride, ray_voff, ray_stride, Pm + objs[st[blockIdx.x].obj].dec, c0_all);
-    plan_tail<SAMPLE_THREADS>(pt, st, objs);
+    if constexpr (GRP) {
+        sample_body(st, objs, rays, cfg, valid_rk, rk_stride, ray_voff, ray_stride, Pm + objs[st[blockIdx.x].obj].dec, c0_all);
+        plan_tail<SAMPLE_THREADS>(pt, st, objs);
+    } else {
+        PHASE_MARK(0, 0);
+        sample_body(st, objs, rays, cfg, valid_rk, rk_stride, ray_voff, ray_stride, Pm, c0_all);
+        PHASE_MARK(0, 7);
+        plan_tail<SAMPLE_THREADS>(pt, st, objs);        // the forward kernel's item list (k_plan mode 0)
+        PHASE_END(0, 8);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // k_mlp_fwd: decoder forward on the valid ray samples (loss.py:78)
 // ---------------------------------------------------------------------------------------------------------------
-template <bool BF3>
+// GRP (here and on the four kernels below): P is a decoder group's parameter array and every work item uses the entry of its
+// object's decoder (ObjView::dec).  The flag sits on the kernel itself and the body reads the kernel's own parameters: the
+// single-decoder form compiles to the code it had before there were groups ("Decoder groups").
+template <bool BF3, bool GRP = false>
 __global__ __launch_bounds__(MLP_THREADS, 2) void k_mlp_fwd(const HypState* __restrict__ st,
                                                             const ObjView* __restrict__ objs,
                                                             const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
                                                             const int32_t* __restrict__ valid_rk, int64_t rk_stride,
                                                             float* __restrict__ sdf_valid, const int2* __restrict__ work,
                                                             int* __restrict__ qctl, const float* __restrict__ c0_all) {
-#define QSP_GRP 0
-#include "sdf_body_mlp_fwd.inc"
-#undef QSP_GRP
-}
-template <bool BF3>
-__global__ __launch_bounds__(MLP_THREADS, 2) void k_grp_mlp_fwd(const HypState* __restrict__ st,
-                                                            const ObjView* __restrict__ objs,
-                                                            const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
-                                                            const int32_t* __restrict__ valid_rk, int64_t rk_stride,
-                                                            float* __restrict__ sdf_valid, const int2* __restrict__ work,
-                                                            int* __restrict__ qctl, const float* __restrict__ c0_all) {
-#define QSP_GRP 1
-#include "sdf_body_mlp_fwd.inc"
-#undef QSP_GRP
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
+    __shared__ float Tsh[16];
+    __shared__ int s_item;
+    const int n_items = qctl[0];
+    int h_cached = -1;
+    for (;;) {
+        if (threadIdx.x == 0) s_item = atomicAdd(&qctl[1], 1);
+        __syncthreads();                       // also: everybody is done with the previous item's LDS
+        const int item = s_item;
+        if (item >= n_items) break;            // the queue only grows towards n_items: every workgroup gets here
+        const int h = work[item].x, t = work[item].y;
+        const HypState& S = st[h];
+        const int n = S.n_valid;
+        const ObjView ov = objs[S.obj];
+        const float* R = rays + 3 * ov.ray_off;
+        const int32_t* rk = valid_rk + h * rk_stride;
+        float* out = sdf_valid + h * rk_stride;
+        if (h != h_cached) {                   // per-hypothesis staging: code, pose, layer-0 code part
+            stage_code_T(s, S, Tsh);
+            s.c0[threadIdx.x] = c0_all[(size_t)h * 2 * HID + threadIdx.x];
+            s.c4[threadIdx.x] = c0_all[(size_t)h * 2 * HID + HID + threadIdx.x];
+            h_cached = h;
+        }
+        const float d_min = S.d_min, d_max = S.d_max;
+        __syncthreads();
+        if (threadIdx.x < TILE_P) {
+            const int v = t * TILE_P + threadIdx.x;
+            float x = 0, y = 0, z = 0;
+            if (v < n) {
+                const int e = rk[v];
+                const int r = e >> 6, k = e & 63;
+                const float d = depth_at(d_min, d_max, k, cfg.n_depth);
+                xform(Tsh, R[3 * r] * d, R[3 * r + 1] * d, R[3 * r + 2] * d, x, y, z);
+            }
+            s.xin[4 * threadIdx.x + 0] = x;
+            s.xin[4 * threadIdx.x + 1] = y;
+            s.xin[4 * threadIdx.x + 2] = z;
+            s.xin[4 * threadIdx.x + 3] = 0.f;
+        }
+        __syncthreads();
+        if constexpr (GRP) {
+            if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, P + ov.dec);      // (the item's decoder)
+            else mlp_tile<false, 4>(s, P + ov.dec);
+        } else {
+            if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, P);
+            else mlp_tile<false, 4>(s, P);
+        }
+        if (threadIdx.x < TILE_P) {
+            const int v = t * TILE_P + threadIdx.x;
+            if (v < n) out[v] = s.y[threadIdx.x];
+        }
+    }
 }
 
 // The out-of-band AUDIT of the screened forward (QSP_DEC_OPT_SCREEN_AUDIT).  The band pass only ever sees the
@@ -566,7 +596,7 @@ __device__ __forceinline__ bool screen_audit_pick(int h, int v, int iter, int on
 
 // the same work queue on the split-fp16 tile: four waves per workgroup (mlp_tile_h2)
 // NARROW: mlp_tile_h2's form for small decoders, run with NW = 8 waves so that the column blocks that exist spread over all SIMDs
-template <int NR, bool NARROW = false, int NW = 4>      // NR point blocks of 32 per tile (QSP_DEC_OPT_TPOINTS)
+template <int NR, bool NARROW = false, int NW = 4, bool GRP = false>      // NR point blocks of 32 per tile (QSP_DEC_OPT_TPOINTS)
 __global__ __launch_bounds__(64 * NW) void k_mlp_fwd_h2(const HypState* __restrict__ st,
                                                             const ObjView* __restrict__ objs,
                                                             const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
@@ -574,28 +604,102 @@ __global__ __launch_bounds__(64 * NW) void k_mlp_fwd_h2(const HypState* __restri
                                                             float* __restrict__ sdf_valid, const int2* __restrict__ work,
                                                             int* __restrict__ qctl, const float* __restrict__ c0_all,
                                                             const int32_t* __restrict__ band_idx, unsigned int* __restrict__ screen_dmax) {
-#define QSP_GRP 0
-#include "sdf_body_mlp_fwd_h2.inc"
-#undef QSP_GRP
-}
-template <int NR, bool NARROW, int NW>
-__global__ __launch_bounds__(64 * NW) void k_grp_mlp_fwd_h2(const HypState* __restrict__ st,
-                                                            const ObjView* __restrict__ objs,
-                                                            const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
-                                                            const int32_t* __restrict__ valid_rk, int64_t rk_stride,
-                                                            float* __restrict__ sdf_valid, const int2* __restrict__ work,
-                                                            int* __restrict__ qctl, const float* __restrict__ c0_all,
-                                                            const int32_t* __restrict__ band_idx, unsigned int* __restrict__ screen_dmax) {
-#define QSP_GRP 1
-#include "sdf_body_mlp_fwd_h2.inc"
-#undef QSP_GRP
+    // band_idx != nullptr: second pass of the screened forward -- the tiles run over the hypothesis's band list (indices into
+    // its valid-sample list written by k_mlp_fwd_h1) and overwrite those samples' screening values.  On the way the largest
+    // |s1 - s3| over the band samples is kept (*screen_dmax, the bits of a non-negative float): the quantity the screening margin
+    // has to cover, measured on every run -- the host repeats a run unscreened if it ever comes near the margin.  Entries flagged
+    // BAND_AUDIT_BIT are out-of-band samples under audit (above): screen_dmax[1] counts those the screening pass clamped wrongly,
+    // (unsigned long long*)(screen_dmax + 2) how many were audited.
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
+    __shared__ float Tsh[16];
+    __shared__ int s_item;
+    const int n_items = qctl[0];
+    constexpr int TP = 32 * NR;
+    [[maybe_unused]] bool staged = false;
+    float amax = 0.f, dmax = 0.f;
+    int h_cached = -1;
+    [[maybe_unused]] int dec_staged = -1;  // (GRP) the decoder whose constants the tile has staged
+    for (;;) {
+        if (threadIdx.x == 0) s_item = atomicAdd(&qctl[1], 1);
+        __syncthreads();                       // also: everybody is done with the previous item's LDS
+        const int item = s_item;
+        if (item >= n_items) break;            // the queue only grows towards n_items: every workgroup gets here
+        const int h = work[item].x, t = work[item].y;
+        const HypState& S = st[h];
+        const int n = band_idx ? S.n_band : S.n_valid;
+        const ObjView ov = objs[S.obj];
+        const float* R = rays + 3 * ov.ray_off;
+        const int32_t* rk = valid_rk + h * rk_stride;
+        const int32_t* sel = band_idx ? band_idx + h * rk_stride : nullptr;
+        float* out = sdf_valid + h * rk_stride;
+        if (h != h_cached) {                   // per-hypothesis staging: code, pose, layer-0 code part
+            stage_code_T(s, S, Tsh);
+            for (int i = threadIdx.x; i < HID; i += 64 * NW) {
+                s.c0[i] = c0_all[(size_t)h * 2 * HID + i];
+                s.c4[i] = c0_all[(size_t)h * 2 * HID + HID + i];
+            }
+            h_cached = h;
+        }
+        const float d_min = S.d_min, d_max = S.d_max;
+        __syncthreads();
+        if (threadIdx.x < TP) {
+            const int v = t * TP + threadIdx.x;
+            float x = 0, y = 0, z = 0;
+            if (v < n) {
+                const int e = rk[sel ? (sel[v] & ~BAND_AUDIT_BIT) : v];
+                const int r = e >> 6, k = e & 63;
+                const float d = depth_at(d_min, d_max, k, cfg.n_depth);
+                xform(Tsh, R[3 * r] * d, R[3 * r + 1] * d, R[3 * r + 2] * d, x, y, z);
+            }
+            s.xin[4 * threadIdx.x + 0] = x;
+            s.xin[4 * threadIdx.x + 1] = y;
+            s.xin[4 * threadIdx.x + 2] = z;
+            s.xin[4 * threadIdx.x + 3] = 0.f;
+        }
+        __syncthreads();
+        if constexpr (GRP) {
+            mlp_tile_h2<false, 2, !NARROW, NR, NW, NARROW>(s, P + ov.dec, amax, ov.dec != dec_staged);   // (constants: again when the decoder changes)
+            dec_staged = ov.dec;
+        } else {
+            mlp_tile_h2<false, 2, !NARROW, NR, NW, NARROW>(s, P, amax, !staged);      // (the decoder's constants: staged by the first tile of the workgroup)
+            staged = true;
+        }
+        if (threadIdx.x < TP) {
+            const int v = t * TP + threadIdx.x;
+            bool audited = false, wrong = false;
+            if (v < n) {
+                const int ent = sel ? sel[v] : v;
+                const int idx = ent & ~BAND_AUDIT_BIT;
+                const float y = s.y[threadIdx.x];
+                if (sel) {
+                    const float s1 = out[idx];                         // (out[idx] still holds the screening value s1)
+                    dmax = fmaxf(dmax, fabsf(s1 - y));
+                    audited = (ent & BAND_AUDIT_BIT) != 0;
+                    wrong = audited && (!(fabsf(y) >= cfg.cut_off) || (s1 < 0.f) != (y < 0.f));
+                }
+                out[idx] = y;
+            }
+            if (sel && screen_dmax && threadIdx.x < 64) {              // (counted per tile: nothing stays live across the tile loop)
+                const unsigned long long ma = __ballot(audited), mw = __ballot(wrong);
+                if (threadIdx.x == 0 && ma) atomicAdd(reinterpret_cast<unsigned long long*>(screen_dmax + 2), (unsigned long long)__popcll(ma));
+                if (threadIdx.x == 0 && mw) atomicAdd(screen_dmax + 1, (unsigned int)__popcll(mw));
+            }
+        }
+    }
+    if (band_idx && screen_dmax && threadIdx.x < 64) {      // the first wave holds every row's difference (TP <= 64)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64));
+        if (threadIdx.x == 0 && dmax > 0.f) atomicMax(screen_dmax, __float_as_uint(dmax));
+    }
+    if (!(amax <= H2_MAX)) *P->range_flag = 1;
 }
 
 // First pass of the screened forward (mlp_tile_h1, sdf_mlp.hpp): every valid ray sample on the one-product tile, 128 points per
 // work item; writes the screening value and appends the samples with |s1| < band_th (or NaN) to the hypothesis's band list.
 // The order of a band list depends on which workgroup finished first; nothing downstream does: the second pass writes each
 // listed sample's value to its own slot, and a sample's value does not depend on its position in a tile.
-template <int NW>      // waves per workgroup: 4 x 512 registers or 8 x 256 (mlp_tile_h1)
+template <int NW, bool GRP = false>      // waves per workgroup: 4 x 512 registers or 8 x 256 (mlp_tile_h1)
 __global__ __launch_bounds__(64 * NW) void k_mlp_fwd_h1(HypState* __restrict__ st, const ObjView* __restrict__ objs,
                                                             const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
                                                             const int32_t* __restrict__ valid_rk, int64_t rk_stride,
@@ -603,21 +707,91 @@ __global__ __launch_bounds__(64 * NW) void k_mlp_fwd_h1(HypState* __restrict__ s
                                                             int* __restrict__ qctl, const float* __restrict__ c0_all,
                                                             int32_t* __restrict__ band_idx, float band_th, int audit_one_in,
                                                             const int32_t* __restrict__ stage_idx) {
-#define QSP_GRP 0
-#include "sdf_body_mlp_fwd_h1.inc"
-#undef QSP_GRP
-}
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_grp_mlp_fwd_h1(HypState* __restrict__ st, const ObjView* __restrict__ objs,
-                                                            const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
-                                                            const int32_t* __restrict__ valid_rk, int64_t rk_stride,
-                                                            float* __restrict__ sdf_valid, const int2* __restrict__ work,
-                                                            int* __restrict__ qctl, const float* __restrict__ c0_all,
-                                                            int32_t* __restrict__ band_idx, float band_th, int audit_one_in,
-                                                            const int32_t* __restrict__ stage_idx) {
-#define QSP_GRP 1
-#include "sdf_body_mlp_fwd_h1.inc"
-#undef QSP_GRP
+    // stage_idx != nullptr: the tiles run over the hypothesis's stage list (positions in its valid-sample list, k_stage_list)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmemH1& s = *reinterpret_cast<MlpSmemH1*>(smem_raw);
+    __shared__ float Tsh[16];
+    __shared__ int s_item;
+    const int n_items = qctl[0];
+    float amax = 0.f;
+    int h_cached = -1;
+    [[maybe_unused]] int dec_staged = -1;  // (GRP) the decoder whose constants are in LDS (staged per item, below)
+    if constexpr (!GRP) {   // the decoder's constants, once per workgroup
+        const MlpParams& Pp = *P;
+        for (int i = threadIdx.x; i < HID; i += 64 * NW) s.w8[i] = Pp.w8[i];
+#pragma unroll
+        for (int l = 1; l < 8; ++l)
+            for (int i = threadIdx.x; i < HID; i += 64 * NW) s.bias[(l - 1) * HID + i] = Pp.bias[l][i];
+    }
+    for (;;) {
+        if (threadIdx.x == 0) s_item = atomicAdd(&qctl[1], 1);
+        __syncthreads();                       // also: everybody is done with the previous item's LDS
+        const int item = s_item;
+        if (item >= n_items) break;            // the queue only grows towards n_items: every workgroup gets here
+        const int h = work[item].x, t = work[item].y;
+        HypState& S = st[h];
+        const int n = stage_idx ? S.n_stage : S.n_valid;
+        const int32_t* stg = stage_idx ? stage_idx + h * rk_stride : nullptr;
+        const ObjView ov = objs[S.obj];
+        const float* R = rays + 3 * ov.ray_off;
+        const int32_t* rk = valid_rk + h * rk_stride;
+        float* out = sdf_valid + h * rk_stride;
+        if (h != h_cached) {                   // per-hypothesis staging: pose, code parts of layers 0 and 4
+            if (threadIdx.x >= 64 && threadIdx.x < 80) Tsh[threadIdx.x - 64] = S.T_oc[threadIdx.x - 64];
+            for (int i = threadIdx.x; i < HID; i += 64 * NW) {
+                s.c0[i] = c0_all[(size_t)h * 2 * HID + i];
+                s.c4[i] = c0_all[(size_t)h * 2 * HID + HID + i];
+            }
+            h_cached = h;
+        }
+        if constexpr (GRP) {
+            if (ov.dec != dec_staged) {        // the item's decoder's constants (everybody is done with the previous item's LDS)
+                const MlpParams& Pp = P[ov.dec];
+                for (int i = threadIdx.x; i < HID; i += 64 * NW) s.w8[i] = Pp.w8[i];
+#pragma unroll
+                for (int l = 1; l < 8; ++l)
+                    for (int i = threadIdx.x; i < HID; i += 64 * NW) s.bias[(l - 1) * HID + i] = Pp.bias[l][i];
+                dec_staged = ov.dec;
+            }
+        }
+        const float d_min = S.d_min, d_max = S.d_max;
+        __syncthreads();
+        if (threadIdx.x < H1_ROWS) {
+            const int v = t * H1_ROWS + threadIdx.x;
+            float x = 0, y = 0, z = 0;
+            if (v < n) {
+                const int e = rk[stg ? stg[v] : v];
+                const int r = e >> 6, k = e & 63;
+                const float d = depth_at(d_min, d_max, k, cfg.n_depth);
+                xform(Tsh, R[3 * r] * d, R[3 * r + 1] * d, R[3 * r + 2] * d, x, y, z);
+            }
+            s.xin[4 * threadIdx.x + 0] = x;
+            s.xin[4 * threadIdx.x + 1] = y;
+            s.xin[4 * threadIdx.x + 2] = z;
+            s.xin[4 * threadIdx.x + 3] = 0.f;
+        }
+        __syncthreads();
+        if constexpr (GRP) mlp_tile_h1<2, NW>(s, P + ov.dec, amax);
+        else mlp_tile_h1<2, NW>(s, P, amax);
+        if (threadIdx.x < H1_ROWS) {           // (waves 0 and 1, all lanes)
+            int v = t * H1_ROWS + threadIdx.x;
+            bool in = false, audit = false;
+            if (v < n) {
+                if (stg) v = stg[v];           // (from here on v is the sample's position in the valid list)
+                const float y = s.y[threadIdx.x];
+                out[v] = y;
+                in = !(fabsf(y) >= band_th);   // (a NaN goes to the second pass as well)
+                audit = !in && screen_audit_pick(h, v, cfg.iter, audit_one_in);      // a sample of the OUT-of-band ones (above)
+            }
+            const unsigned long long m = __ballot(in || audit);
+            const int lane = threadIdx.x & 63;
+            int base = 0;
+            if (lane == 0 && m) base = atomicAdd(&S.n_band, __popcll(m));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (in || audit) band_idx[h * rk_stride + base + __popcll(m & ((1ull << lane) - 1ull))] = audit ? (v | BAND_AUDIT_BIT) : v;
+        }
+    }
+    if (!(amax <= H2_MAX)) *P->range_flag = 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -770,7 +944,7 @@ __global__ __launch_bounds__(SCAN_RAYS) void k_scan(HypState* __restrict__ st, c
 // ---------------------------------------------------------------------------------------------------------------
 // k_mlp_jtj: surface points + kept render rows -> Jacobian rows -> J~^T J~ tile partials
 // ---------------------------------------------------------------------------------------------------------------
-template <bool B3>
+template <bool B3, bool GRP = false>
 __global__ __launch_bounds__(MLP_THREADS, 2) void k_mlp_jtj(const HypState* __restrict__ st,
                                                             const ObjView* __restrict__ objs,
                                                             const float* __restrict__ pts,
@@ -783,26 +957,136 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void k_mlp_jtj(const HypState* __re
                                                             float* __restrict__ partials, int nw_total,
                                                             const int2* __restrict__ work, int* __restrict__ qctl,
                                                             const float* __restrict__ c0_all) {
-#define QSP_GRP 0
-#include "sdf_body_mlp_jtj.inc"
-#undef QSP_GRP
-}
-template <bool B3>
-__global__ __launch_bounds__(MLP_THREADS, 2) void k_grp_mlp_jtj(const HypState* __restrict__ st,
-                                                            const ObjView* __restrict__ objs,
-                                                            const float* __restrict__ pts,
-                                                            const float* __restrict__ rays, RefineCfg cfg, const MlpParams* __restrict__ P,
-                                                            int nw_sdf, const int32_t* __restrict__ rend_rk,
-                                                            const float* __restrict__ rend_deds,
-                                                            const float* __restrict__ rend_res, int64_t rk_stride,
-                                                            const uint8_t* __restrict__ pt_active, int64_t act_stride,
-                                                            float* __restrict__ res_out, float* __restrict__ rows_out, int64_t rows_stride,
-                                                            float* __restrict__ partials, int nw_total,
-                                                            const int2* __restrict__ work, int* __restrict__ qctl,
-                                                            const float* __restrict__ c0_all) {
-#define QSP_GRP 1
-#include "sdf_body_mlp_jtj.inc"
-#undef QSP_GRP
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
+    __shared__ float Tsh[16];
+    __shared__ int s_item;
+    const int n_items = qctl[2];
+    bool tsk_first = true;
+    (void)tsk_first;
+  for (;;) {                                   // work queue, see k_plan
+    QSP_TSK(0)
+    if (threadIdx.x == 0) s_item = atomicAdd(&qctl[3], 1);
+    __syncthreads();                           // also: everybody is done with the previous item's LDS
+    const int item = s_item;
+    if (item >= n_items) break;                // the queue only grows towards n_items: every workgroup gets here
+    QSP_TSK(1)
+    const int h = work[item].x, slot = work[item].y;
+    const HypState& S = st[h];
+    const ObjView ov = objs[S.obj];
+    const bool is_sdf = slot < nw_sdf;
+    const int stride = is_sdf ? nw_sdf : nw_total - nw_sdf;
+    const int j0 = is_sdf ? slot : slot - nw_sdf;
+    const int n = is_sdf ? ov.n_pts : S.n_render;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+
+    // J~^T J~ accumulator of this wave's upper-triangular tile (waves 0..5)
+    f32x16 hacc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) hacc[i] = 0.f;
+    const int ta = (wave < 3) ? 0 : (wave < 5 ? 1 : 2);
+    const int tb = (wave < 3) ? wave : (wave < 5 ? wave - 2 : 2);
+
+    stage_code_T(s, S, Tsh);
+    s.c0[threadIdx.x] = c0_all[(size_t)h * 2 * HID + threadIdx.x];
+    s.c4[threadIdx.x] = c0_all[(size_t)h * 2 * HID + HID + threadIdx.x];
+    const float* Pc = pts + 3 * ov.pts_off;
+    const float* R = rays + 3 * ov.ray_off;
+    const int32_t* rk = rend_rk + h * rk_stride;
+    const float* deds = rend_deds + h * rk_stride;
+    const float* rres = rend_res + h * rk_stride;
+    const uint8_t* active = pt_active ? pt_active + h * act_stride : nullptr;
+    const float d_min = S.d_min, d_max = S.d_max;
+    const float hub = is_sdf ? cfg.b2 : cfg.b1;
+
+    for (int t = j0; t * TILE_P < n; t += stride) {
+        __syncthreads();
+        if (tid < TILE_P) {
+            const int v = t * TILE_P + tid;
+            float x = 0, y = 0, z = 0, sc = 0.f, rr = 0.f;
+            if (v < n) {
+                if (is_sdf) {
+                    xform(Tsh, Pc[3 * v], Pc[3 * v + 1], Pc[3 * v + 2], x, y, z);
+                    sc = (active && !active[v]) ? 0.f : 1.f;
+                } else {
+                    const int e = rk[v];
+                    const int r = e >> 6, k = e & 63;
+                    const float d = depth_at(d_min, d_max, k, cfg.n_depth);
+                    xform(Tsh, R[3 * r] * d, R[3 * r + 1] * d, R[3 * r + 2] * d, x, y, z);
+                    sc = deds[v];
+                    rr = rres[v];
+                }
+            }
+            s.xin[4 * tid + 0] = x;
+            s.xin[4 * tid + 1] = y;
+            s.xin[4 * tid + 2] = z;
+            s.xin[4 * tid + 3] = (v < n) ? 1.f : 0.f;   // row-valid flag
+            s.rscale[tid] = sc;
+            s.rres[tid] = rr;
+        }
+        __syncthreads();
+        QSP_TSK(2)
+        if constexpr (GRP) mlp_tile<true, 4, !B3, B3>(s, P + ov.dec);      // (the item's decoder)
+        else mlp_tile<true, 4, !B3, B3>(s, P);      // (AccVGPR accumulators leave the split-bf16 tile too few ArchVGPRs)
+        QSP_TSK(3)
+        // ---- Jacobian rows: J~[p] = [ s*(g_x . [I | -x^ | x]) (7) | s*g_z (64) | r~ ] -------------------------------
+        // G (gradient w.r.t. [code | xyz]) sits in s.act with row stride LDG; J~ goes behind it.
+        float* G = s.act;
+        float* Jt = s.act + TILE_P * LDG;     // [64][LDJ]
+        {
+            const int p = tid >> 3, sub = tid & 7;
+            const float valid = s.xin[4 * p + 3];
+            const float sc = s.rscale[p] * valid;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int c = sub + 8 * q;           // code column 0..63
+                Jt[p * LDJ + 7 + c] = cfg.pose_only ? 0.f : sc * G[p * LDG + c];
+            }
+            if (sub == 0) {
+                const float gx = sc * G[p * LDG + 64], gy = sc * G[p * LDG + 65], gz = sc * G[p * LDG + 66];
+                const float x = s.xin[4 * p], y = s.xin[4 * p + 1], z = s.xin[4 * p + 2];
+                // [I | -x^ | x]: columns t(3), omega(3), scale(1)   (loss_utils.py:166-185)
+                Jt[p * LDJ + 0] = gx;
+                Jt[p * LDJ + 1] = gy;
+                Jt[p * LDJ + 2] = gz;
+                Jt[p * LDJ + 3] = gz * y - gy * z;
+                Jt[p * LDJ + 4] = gx * z - gz * x;
+                Jt[p * LDJ + 5] = gy * x - gx * y;
+                Jt[p * LDJ + 6] = cfg.pose_only ? 0.f : (gx * x + gy * y + gz * z);
+                float r = is_sdf ? s.y[p] : s.rres[p];
+                float w = cfg.pose_only ? 1.f : huber_w(r, hub);
+                if (is_sdf && s.rscale[p] == 0.f) w = 0.f;      // filtered-out point (pose-only inlier mask)
+                Jt[p * LDJ + 71] = valid * (w * r);
+                if (res_out && is_sdf && valid != 0.f) res_out[h * act_stride + t * TILE_P + p] = r;
+            }
+            if (sub == 1) {
+#pragma unroll
+                for (int c = NJ; c < LDJ; ++c) Jt[p * LDJ + c] = 0.f;
+            }
+        }
+        __syncthreads();
+        if (rows_out) {   // parity-test tap: the augmented Jacobian rows exactly as the MFMA below consumes them
+            float* ro = rows_out + (int64_t)h * rows_stride * NJ + (int64_t)(is_sdf ? 0 : ov.n_pts) * NJ;
+            for (int e = tid; e < TILE_P * NJ; e += MLP_THREADS) {
+                const int p = e / NJ, c = e - p * NJ;
+                const int v = t * TILE_P + p;
+                if (v < n) ro[(int64_t)v * NJ + c] = Jt[p * LDJ + c];
+            }
+        }
+        if (wave < 6) {
+            const float* A = Jt + (lane >> 5) * LDJ + 32 * ta + (lane & 31);
+            const float* B = Jt + (lane >> 5) * LDJ + 32 * tb + (lane & 31);
+#pragma unroll 8
+            for (int ks = 0; ks < TILE_P / 2; ++ks) hacc = mfma32t<!B3>(A[2 * ks * LDJ], B[2 * ks * LDJ], hacc);
+            mfma_acc_settle<!B3>(hacc);
+        }
+        QSP_TSK(4)
+    }
+    // partial slot [h][slot][packed upper triangle of 72 x 72]
+    if (wave < 6) part_store(partials + ((int64_t)h * nw_total + slot) * PART_FLOATS, ta, tb, lane, hacc);
+    QSP_TSK(5)
+    tsk_first = false;
+  }
 }
 
 // the same kernel on the split-fp16 tile: four waves per workgroup (mlp_tile_h2<true>); the six J~^T J~ tiles on waves 0..3
@@ -849,17 +1133,187 @@ __device__ __forceinline__ jtj_kargs_t jtj_kernargs() {
 }
 
 // NW = 4: one wave of 512 registers per SIMD; NW = 8: two of 256 (mlp_tile_h2), the six J~^T J~ tiles on waves 0..5.
-template <int NR, int NW = 4, bool NARROW = false>      // NR point blocks of 32 per tile (QSP_DEC_OPT_TPOINTS)
+template <int NR, int NW = 4, bool NARROW = false, bool GRP = false>      // NR point blocks of 32 per tile (QSP_DEC_OPT_TPOINTS)
 __global__ __launch_bounds__(64 * NW) void k_mlp_jtj_h2(JtjArgs /* read through jtj_kernargs() only */) {
-#define QSP_GRP 0
-#include "sdf_body_mlp_jtj_h2.inc"
-#undef QSP_GRP
-}
-template <int NR, int NW, bool NARROW>
-__global__ __launch_bounds__(64 * NW) void k_grp_mlp_jtj_h2(JtjArgs /* read through jtj_kernargs() only */) {
-#define QSP_GRP 1
-#include "sdf_body_mlp_jtj_h2.inc"
-#undef QSP_GRP
+    constexpr int NT = 64 * NW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
+    __shared__ float Tsh[16];
+    __shared__ int s_item;
+    constexpr int TP = 32 * NR, SUBS = NT / TP;      // threads per Jacobian row
+    [[maybe_unused]] bool staged = false;
+    float amax = 0.f;
+    int item = -1, t = 0;       // the work item in hand and its current tile; item < 0: pop the next one (see k_plan)
+    // (GRP) the item's decoder (one scalar more across the tile), the decoder whose constants are in LDS
+    [[maybe_unused]] int dec = 0, dec_staged = -1;
+    for (;;) {
+        // ---- phase 1: pop / stage.  Nothing computed here is used behind the tile. ------------------------------------------
+        {
+            const jtj_kargs_t A = jtj_kernargs();
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));     // opaque per phase: otherwise every LDS address that depends on the lane is computed once
+                                              // per kernel, ahead of the item loop, and held (spilled) across the tile
+            const bool fresh = item < 0;
+            if (fresh) {
+                if (tid == 0) s_item = atomicAdd(&A->qctl[3], 1);
+                __syncthreads();                       // also: everybody is done with the previous item's LDS
+                item = __builtin_amdgcn_readfirstlane(s_item);
+                if (item >= A->qctl[2]) break;         // the queue only grows towards its length: every workgroup gets here
+            } else {
+                __syncthreads();                       // the previous tile's epilogue has read its Jacobian rows
+            }
+            const int2 wk = A->work[item];
+            const int h = wk.x, slot = wk.y;
+            const HypState& S = A->st[h];
+            const ObjView ov = A->objs[S.obj];
+            const int nw_sdf = A->nw_sdf;
+            const bool is_sdf = slot < nw_sdf;
+            const int n = is_sdf ? ov.n_pts : S.n_render;
+            if constexpr (GRP) dec = __builtin_amdgcn_readfirstlane(ov.dec);
+            if (fresh) {
+                t = is_sdf ? slot : slot - nw_sdf;
+                if (tid < CODE_LEN) s.code[tid] = S.code[tid];
+                if (tid >= 64 && tid < 80) Tsh[tid - 64] = S.T_oc[tid - 64];
+                const float* c0 = A->c0_all + (size_t)h * 2 * HID;
+                for (int i = tid; i < HID; i += NT) {
+                    s.c0[i] = c0[i];
+                    s.c4[i] = c0[HID + i];
+                }
+                __syncthreads();                       // Tsh is read below
+            }
+            if (tid < TP) {
+                const int v = t * TP + tid;
+                float x = 0, y = 0, z = 0, sc = 0.f, rr = 0.f;
+                if (v < n) {
+                    if (is_sdf) {
+                        const float* Pc = A->pts + 3 * ov.pts_off;
+                        const uint8_t* active = A->pt_active ? A->pt_active + h * A->act_stride : nullptr;
+                        xform(Tsh, Pc[3 * v], Pc[3 * v + 1], Pc[3 * v + 2], x, y, z);
+                        sc = (active && !active[v]) ? 0.f : 1.f;
+                    } else {
+                        const float* R = A->rays + 3 * ov.ray_off;
+                        const int64_t ro = h * A->rk_stride;
+                        const int e = A->rend_rk[ro + v];
+                        const int r = e >> 6, k = e & 63;
+                        const float d = depth_at(S.d_min, S.d_max, k, A->cfg.n_depth);
+                        xform(Tsh, R[3 * r] * d, R[3 * r + 1] * d, R[3 * r + 2] * d, x, y, z);
+                        sc = A->rend_deds[ro + v];
+                        rr = A->rend_res[ro + v];
+                    }
+                }
+                s.xin[4 * tid + 0] = x;
+                s.xin[4 * tid + 1] = y;
+                s.xin[4 * tid + 2] = z;
+                s.xin[4 * tid + 3] = (v < n) ? 1.f : 0.f;   // row-valid flag
+                s.rscale[tid] = sc;
+                s.rres[tid] = rr;
+            }
+            __syncthreads();
+        }
+        // ---- the tile: live across it are item, t, staged (scalars) and amax ---------------------------------------------------
+        {
+            if constexpr (GRP) {
+                const MlpParams* Pm = jtj_kernargs()->P + dec;
+                mlp_tile_h2<true, 2, false, NR, NW, NARROW>(s, Pm, amax, dec != dec_staged);    // (constants: again when the decoder changes)
+                dec_staged = dec;
+            } else {
+                const MlpParams* Pm = jtj_kernargs()->P;
+                mlp_tile_h2<true, 2, false, NR, NW, NARROW>(s, Pm, amax, !staged);
+                staged = true;
+            }
+        }
+        // ---- phase 2: Jacobian rows  J~[p] = [ s*(g_x . [I | -x^ | x]) (7) | s*g_z (64) | r~ ],  J~^T J~ -----------------------
+        // G (gradient w.r.t. [code | xyz]) sits in s.act with row stride LDG; J~ goes behind it.
+        {
+            asm volatile("" : "+s"(item), "+s"(t));
+            const jtj_kargs_t A = jtj_kernargs();
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+            const int2 wk = A->work[item];
+            const int h = wk.x, slot = wk.y;
+            const HypState& S = A->st[h];
+            const ObjView ov = A->objs[S.obj];
+            const int nw_sdf = A->nw_sdf, nw_total = A->nw_total;
+            const bool is_sdf = slot < nw_sdf;
+            const int n = is_sdf ? ov.n_pts : S.n_render;
+            const int j0 = is_sdf ? slot : slot - nw_sdf;
+            const int stride = is_sdf ? nw_sdf : nw_total - nw_sdf;
+            const int pose_only = A->cfg.pose_only;
+            const float hub = is_sdf ? A->cfg.b2 : A->cfg.b1;
+            float* G = s.act;
+            float* Jt = s.act + TILE_P * LDG;   /* (behind the 64-row G image whatever the tile size) */     // [64][LDJ]
+            {
+                const int p = tid / SUBS, sub = tid % SUBS;
+                const float valid = s.xin[4 * p + 3];
+                const float sc = s.rscale[p] * valid;
+#pragma unroll
+                for (int q = 0; q < CODE_LEN / SUBS; ++q) {
+                    const int c = sub + SUBS * q;        // code column 0..63
+                    Jt[p * LDJ + 7 + c] = pose_only ? 0.f : sc * G[p * LDG + c];
+                }
+                if (sub == 0) {
+                    const float gx = sc * G[p * LDG + 64], gy = sc * G[p * LDG + 65], gz = sc * G[p * LDG + 66];
+                    const float x = s.xin[4 * p], y = s.xin[4 * p + 1], z = s.xin[4 * p + 2];
+                    // [I | -x^ | x]: columns t(3), omega(3), scale(1)   (loss_utils.py:166-185)
+                    Jt[p * LDJ + 0] = gx;
+                    Jt[p * LDJ + 1] = gy;
+                    Jt[p * LDJ + 2] = gz;
+                    Jt[p * LDJ + 3] = gz * y - gy * z;
+                    Jt[p * LDJ + 4] = gx * z - gz * x;
+                    Jt[p * LDJ + 5] = gy * x - gx * y;
+                    Jt[p * LDJ + 6] = pose_only ? 0.f : (gx * x + gy * y + gz * z);
+                    float r = is_sdf ? s.y[p] : s.rres[p];
+                    float w = pose_only ? 1.f : huber_w(r, hub);
+                    if (is_sdf && s.rscale[p] == 0.f) w = 0.f;      // filtered-out point (pose-only inlier mask)
+                    Jt[p * LDJ + 71] = valid * (w * r);
+                    float* res_out = A->res_out;
+                    if (res_out && is_sdf && valid != 0.f) res_out[h * A->act_stride + t * TP + p] = r;
+                }
+                if (sub == 1) {
+#pragma unroll
+                    for (int c = NJ; c < LDJ; ++c) Jt[p * LDJ + c] = 0.f;
+                }
+            }
+            __syncthreads();
+            if (A->rows_out) {   // parity-test tap: the augmented Jacobian rows exactly as the MFMA below consumes them
+                float* ro = A->rows_out + (int64_t)h * A->rows_stride * NJ + (int64_t)(is_sdf ? 0 : ov.n_pts) * NJ;
+                for (int e = tid; e < TP * NJ; e += NT) {
+                    const int p = e / NJ, c = e - p * NJ;
+                    const int v = t * TP + p;
+                    if (v < n) ro[(int64_t)v * NJ + c] = Jt[p * LDJ + c];
+                }
+            }
+            // upper-triangular 32x32 tiles in the order (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).  Four waves: tile w on every wave, tile
+            // w + 4 on waves 0, 1; eight waves: tile w on waves 0..5.  Partial slot [h][slot][packed upper triangle].
+            float* out = A->partials + ((int64_t)h * nw_total + slot) * PART_FLOATS;
+            const bool first = t == j0;
+            if (NW == 4 || wave < 6) {
+                const int ta0 = wave < 3 ? 0 : (wave < 5 ? 1 : 2), tb0 = wave < 3 ? wave : (wave < 5 ? wave - 2 : 2);
+                f32x16 hacc;
+                part_load(out, ta0, tb0, lane, first, hacc);
+                const float* Aj = Jt + (lane >> 5) * LDJ + 32 * ta0 + (lane & 31);
+                const float* Bj = Jt + (lane >> 5) * LDJ + 32 * tb0 + (lane & 31);
+#pragma unroll 8
+                for (int ks = 0; ks < TP / 2; ++ks) hacc = mfma32t<false>(Aj[2 * ks * LDJ], Bj[2 * ks * LDJ], hacc);
+                part_store(out, ta0, tb0, lane, hacc);
+            }
+            if (NW == 4 && wave < 2) {
+                const int ta1 = wave == 0 ? 1 : 2, tb1 = 2;
+                f32x16 hacc;
+                part_load(out, ta1, tb1, lane, first, hacc);
+                const float* Aj = Jt + (lane >> 5) * LDJ + 32 * ta1 + (lane & 31);
+                const float* Bj = Jt + (lane >> 5) * LDJ + 32 * tb1 + (lane & 31);
+#pragma unroll 8
+                for (int ks = 0; ks < TP / 2; ++ks) hacc = mfma32t<false>(Aj[2 * ks * LDJ], Bj[2 * ks * LDJ], hacc);
+                part_store(out, ta1, tb1, lane, hacc);
+            }
+            // the item's next tile (more than nw_sdf x TP surface points, or more than 16 x TP render rows), or the next item
+            t += stride;
+            if (t * TP >= n) item = -1;
+        }
+    }
+    if (!(amax <= H2_MAX)) *jtj_kernargs()->P->range_flag = 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -84,7 +84,7 @@ struct qsp_decoder {
 };
 
 // A decoder group (qsp_decoder_group_create): an ordered set of decoders, one per class, that the group entry points refine
-// together -- every object names its member (ObjView::dec) and the k_grp_* twins of the decoder kernels read that member's
+// together -- every object names its member (ObjView::dec) and the GRP = true forms of the decoder kernels read that member's
 // MlpParams from Pd.  The members' options must agree (group_check); the first member lends the group its stream and its
 // option fields, and a range fallback / screening repeat of a group call overrides them there.
 struct qsp_decoder_group {
@@ -600,50 +600,50 @@ static int jtj_waves_t32() {
     return w;
 }
 
+// The instantiations of the decoder kernels that run_once() launches, each named once: its single-decoder form, or for a decoder
+// group's batch (grp) the form that reads every work item's decoder from the group's parameter array.  mlp_attr_once() raises the
+// dynamic-LDS limit of both forms through the same helpers.
+template <bool BF3> static auto fwd_kernel(bool grp) { return grp ? k_mlp_fwd<BF3, true> : k_mlp_fwd<BF3, false>; }
+template <int NW> static auto fwd_h1_kernel(bool grp) { return grp ? k_mlp_fwd_h1<NW, true> : k_mlp_fwd_h1<NW, false>; }
+template <int NR, bool NARROW, int NW>
+static auto fwd_h2_kernel(bool grp) { return grp ? k_mlp_fwd_h2<NR, NARROW, NW, true> : k_mlp_fwd_h2<NR, NARROW, NW, false>; }
+template <bool B3> static auto jtj_kernel(bool grp) { return grp ? k_mlp_jtj<B3, true> : k_mlp_jtj<B3, false>; }
+template <int NR, int NW, bool NARROW>
+static auto jtj_h2_kernel(bool grp) { return grp ? k_mlp_jtj_h2<NR, NW, NARROW, true> : k_mlp_jtj_h2<NR, NW, NARROW, false>; }
+
 static int mlp_attr_once() {
     static bool done = false;
     if (done) return QSP_OK;
-    const int bytes = (int)sizeof(MlpSmem);
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_fwd_h2<2, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_fwd_h2<2, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj_h2<2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj_h2<1, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode_h2<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode_h2<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_fwd_h1<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_fwd_h1<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode_screen<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode_screen<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode_h2<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode_h2<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj_h2<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj_h2<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj_h2<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj_h2<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * SCAN_RAYS * SCAN_LD)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_mlp_jtj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_decode<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    // the decoder-group twins of the refinement's decoder kernels
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h2<2, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h2<2, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h1<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_fwd_h1<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpSmemH1)));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<2, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<1, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<2, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<1, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    QSP_HIP(hipFuncSetAttribute((const void*)k_grp_mlp_jtj_h2<1, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    const auto lds = [](auto kernel, size_t bytes) {
+        return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    };
+    for (const bool grp : {false, true}) {
+        QSP_HIP(lds(fwd_kernel<false>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(fwd_kernel<true>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(fwd_h1_kernel<4>(grp), sizeof(MlpSmemH1)));
+        QSP_HIP(lds(fwd_h1_kernel<8>(grp), sizeof(MlpSmemH1)));
+        QSP_HIP(lds(fwd_h2_kernel<2, false, 4>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(fwd_h2_kernel<2, true, 8>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_kernel<false>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_kernel<true>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_h2_kernel<2, 4, false>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_h2_kernel<1, 4, false>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_h2_kernel<2, 8, false>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_h2_kernel<1, 8, false>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_h2_kernel<2, 8, true>(grp), sizeof(MlpSmem)));
+        QSP_HIP(lds(jtj_h2_kernel<1, 8, true>(grp), sizeof(MlpSmem)));
+    }
+    QSP_HIP(lds(k_scan, sizeof(float) * SCAN_RAYS * SCAN_LD));
+    QSP_HIP(lds(k_decode<false>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode<true>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode<false, true>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode<true, true>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode_h2<false, false>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode_h2<true, false>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode_h2<false, true>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode_h2<true, true>, sizeof(MlpSmem)));
+    QSP_HIP(lds(k_decode_screen<4>, sizeof(MlpSmemH1)));
+    QSP_HIP(lds(k_decode_screen<8>, sizeof(MlpSmemH1)));
     done = true;
     return QSP_OK;
 }
@@ -1281,14 +1281,11 @@ constexpr float SCREEN_TRUST = 0.5f;
 
 // one pass over n_iter Gauss-Newton iterations on the decoder's current pipes; *hit = a split-fp16 kernel left fp16's range,
 // *screen_hit = the screened forward saw |s1 - s3| above half its margin on a band sample (the margin's premise is in doubt)
-// the kernel a launch of a batch uses: the decoder-group twin for a group's batch
-template <class F>
-static F pick(const qsp_refine_batch* b, F single, F group) { return b->grp ? group : single; }
-
 static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen_hit) {
     bool screened_any = false;
     hipStream_t s = b->dec->stream;
-    const MlpParams* Pm = b->grp ? b->grp->Pd : b->dec->Pd;      // (a group's: one entry per member)
+    const bool grp = b->grp != nullptr;      // a decoder group's batch: the GRP forms of the decoder kernels
+    const MlpParams* Pm = grp ? b->grp->Pd : b->dec->Pd;      // (a group's: one entry per member)
     const int nH = b->n_hyp;
     const int nw_total = b->nw_sdf + (b->cfg.pose_only ? 0 : NW_REND);
     size_t cur = 0;
@@ -1304,8 +1301,8 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
         if (b->dec->jac_bf3 != 2) cfg.tile_p = TILE_P;      // (32-point tiles exist on the split-fp16 pipe only: the f32 repeat of a
                                                             //  batch created for them runs 64-point tiles over the same slots)
         hipEvent_t a = nullptr;
-        if (cfg.pose_only && b->grp) hipLaunchKernelGGL(k_grp_c0, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->objs, Pm, b->c0_all);
-        else if (cfg.pose_only) hipLaunchKernelGGL(k_c0, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->dec->Pd, b->c0_all);
+        if (cfg.pose_only)
+            hipLaunchKernelGGL(grp ? k_c0<true> : k_c0<false>, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->objs, Pm, b->c0_all);
         if (!cfg.pose_only) {      // (k_sample also forms the bias vectors k_c0 forms in pose-only mode)
             if (b->prof) a = next_event(b, cur);
             // Two passes pay when the one-pass kernel would need more than one round of 64-point tiles over the chip; a batch that
@@ -1326,7 +1323,7 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
                                 (b->dec->depth_staging == 2 || (b->dec->depth_staging == 1 && ub_samples > 64 * (int64_t)b->n_cu * H1_ROWS));
             const PlanTail pt_fwd{staged ? nullptr : b->work_fwd, b->qctl, b->qctl + 4, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                   screen ? H1_ROWS : TILE_P, 0};
-            hipLaunchKernelGGL(pick(b, k_sample, k_grp_sample), dim3(nH), dim3(SAMPLE_THREADS), 0, s, b->st, b->objs, b->rays, cfg,
+            hipLaunchKernelGGL(grp ? k_sample<true> : k_sample<false>, dim3(nH), dim3(SAMPLE_THREADS), 0, s, b->st, b->objs, b->rays, cfg,
                                b->valid_rk, b->rk_stride, b->ray_voff, b->ray_stride, Pm, b->c0_all, pt_fwd);
             if (b->prof) spans.push_back({a, next_event(b, cur), 2});
             if (b->prof) a = next_event(b, cur);
@@ -1346,33 +1343,33 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
                         stage_list = b->stage_idx;
                     }
                     if (screen_waves() == 8)
-                        hipLaunchKernelGGL(pick(b, k_mlp_fwd_h1<8>, k_grp_mlp_fwd_h1<8>), dim3(b->n_cu), dim3(512), sizeof(MlpSmemH1), s,
+                        hipLaunchKernelGGL(fwd_h1_kernel<8>(grp), dim3(b->n_cu), dim3(512), sizeof(MlpSmemH1), s,
                                            b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                            b->band_idx, cfg.cut_off + b->dec->screen_margin, b->dec->screen_audit, stage_list);
                     else
-                        hipLaunchKernelGGL(pick(b, k_mlp_fwd_h1<4>, k_grp_mlp_fwd_h1<4>), dim3(b->n_cu), dim3(H2_THREADS),
+                        hipLaunchKernelGGL(fwd_h1_kernel<4>(grp), dim3(b->n_cu), dim3(H2_THREADS),
                                            sizeof(MlpSmemH1), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                            b->band_idx, cfg.cut_off + b->dec->screen_margin, b->dec->screen_audit, stage_list);
                     hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, 2, b->st, b->objs, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                        b->work_fwd, b->qctl, TILE_P);
-                    hipLaunchKernelGGL(pick(b, k_mlp_fwd_h2<2, false, 4>, k_grp_mlp_fwd_h2<2, false, 4>), dim3(b->n_cu), dim3(H2_THREADS),
+                    hipLaunchKernelGGL((fwd_h2_kernel<2, false, 4>(grp)), dim3(b->n_cu), dim3(H2_THREADS),
                                        sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid,
                                        b->work_fwd, b->qctl, b->c0_all, (const int32_t*)b->band_idx, (unsigned int*)(b->counters + 5));
                 }
                 screened_any = true;
             } else if (b->dec->fwd_bf3 == 2 && b->dec->P.narrow)
-                hipLaunchKernelGGL(pick(b, k_mlp_fwd_h2<2, true, 8>, k_grp_mlp_fwd_h2<2, true, 8>), dim3(b->n_cu), dim3(512),
+                hipLaunchKernelGGL((fwd_h2_kernel<2, true, 8>(grp)), dim3(b->n_cu), dim3(512),
                                    sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                    (const int32_t*)nullptr, (unsigned int*)nullptr);
             else if (b->dec->fwd_bf3 == 2)
-                hipLaunchKernelGGL(pick(b, k_mlp_fwd_h2<2, false, 4>, k_grp_mlp_fwd_h2<2, false, 4>), dim3(b->n_cu), dim3(H2_THREADS),
+                hipLaunchKernelGGL((fwd_h2_kernel<2, false, 4>(grp)), dim3(b->n_cu), dim3(H2_THREADS),
                                    sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
                                    (const int32_t*)nullptr, (unsigned int*)nullptr);
             else if (b->dec->fwd_bf3)
-                hipLaunchKernelGGL(pick(b, k_mlp_fwd<true>, k_grp_mlp_fwd<true>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
+                hipLaunchKernelGGL(fwd_kernel<true>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
                                    s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
             else
-                hipLaunchKernelGGL(pick(b, k_mlp_fwd<false>, k_grp_mlp_fwd<false>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
+                hipLaunchKernelGGL(fwd_kernel<false>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
                                    s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
             if (b->prof) spans.push_back({a, next_event(b, cur), 1});
             if (b->prof) a = next_event(b, cur);
@@ -1394,25 +1391,25 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
             // (32-point tiles are the latency option -- one tile deep: there the four-wave form is the shorter chain, 180 us
             //  against 248 per tile; QSP_JTJ_WAVES_T32=8 selects the other for measurements)
             if (b->dec->P.narrow && cfg.tile_p == 32)      // narrow decoders: eight waves, so that the column blocks that exist
-                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<1, 8, true>, k_grp_mlp_jtj_h2<1, 8, true>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);   // spread over all SIMDs
+                hipLaunchKernelGGL((jtj_h2_kernel<1, 8, true>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);   // spread over all SIMDs
             else if (b->dec->P.narrow)
-                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<2, 8, true>, k_grp_mlp_jtj_h2<2, 8, true>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL((jtj_h2_kernel<2, 8, true>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
             else if (cfg.tile_p == 32 && jtj_waves_t32() == 8)
-                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<1, 8>, k_grp_mlp_jtj_h2<1, 8, false>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL((jtj_h2_kernel<1, 8, false>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
             else if (cfg.tile_p == 32)
-                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<1, 4>, k_grp_mlp_jtj_h2<1, 4, false>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL((jtj_h2_kernel<1, 4, false>(grp)), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
             else if (jtj_waves() == 8)
-                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<2, 8>, k_grp_mlp_jtj_h2<2, 8, false>), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL((jtj_h2_kernel<2, 8, false>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
             else
-                hipLaunchKernelGGL(pick(b, k_mlp_jtj_h2<2, 4>, k_grp_mlp_jtj_h2<2, 4, false>), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
+                hipLaunchKernelGGL((jtj_h2_kernel<2, 4, false>(grp)), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
         }
         else if (b->dec->jac_bf3)
-            hipLaunchKernelGGL(pick(b, k_mlp_jtj<true>, k_grp_mlp_jtj<true>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
+            hipLaunchKernelGGL(jtj_kernel<true>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
                                b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
                                b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
                                b->work_jtj, b->qctl, b->c0_all);
         else
-            hipLaunchKernelGGL(pick(b, k_mlp_jtj<false>, k_grp_mlp_jtj<false>), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
+            hipLaunchKernelGGL(jtj_kernel<false>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
                                b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
                                b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
                                b->work_jtj, b->qctl, b->c0_all);

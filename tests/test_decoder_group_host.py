@@ -1,6 +1,6 @@
 """CPU: the decoder-group API without a device -- its symbols in the header, the ctypes binding and the library, the Python
-argument checks of OptimizerGroup, and the group twins of the decoder kernels in the compiled ISA (present, inside the spill
-budget of their single-decoder twin, clean under the MFMA hazard scan)."""
+argument checks of OptimizerGroup, and the group forms (GRP = true) of the decoder kernels in the compiled ISA (present, inside
+the spill budget of their single-decoder twin, clean under the MFMA hazard scan)."""
 import os
 import re
 import subprocess
@@ -11,22 +11,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUP_SYMBOLS = ["qsp_decoder_group_create", "qsp_decoder_group_destroy", "qsp_refine_batch_create_group",
                  "qsp_reconstruct_objects_group", "qsp_estimate_pose_group", "qsp_refine_detections_group"]
 
-# group kernel -> its single-decoder twin in tests/test_isa_budget.py's BUDGET
+# group kernel (last template argument GRP = true) -> its single-decoder twin in tests/test_isa_budget.py's BUDGET
 GROUP_KERNELS = {
-    "qsp::k_grp_mlp_jtj_h2<2, 4, false>": "qsp::k_mlp_jtj_h2<2, 4, false>",
-    "qsp::k_grp_mlp_jtj_h2<1, 4, false>": "qsp::k_mlp_jtj_h2<1, 4, false>",
-    "qsp::k_grp_mlp_jtj_h2<2, 8, false>": "qsp::k_mlp_jtj_h2<2, 8, false>",
-    "qsp::k_grp_mlp_jtj_h2<1, 8, false>": "qsp::k_mlp_jtj_h2<1, 8, false>",
-    "qsp::k_grp_mlp_jtj_h2<2, 8, true>": "qsp::k_mlp_jtj_h2<2, 8, true>",
-    "qsp::k_grp_mlp_jtj_h2<1, 8, true>": "qsp::k_mlp_jtj_h2<1, 8, true>",
-    "qsp::k_grp_mlp_fwd_h2<2, false, 4>": "qsp::k_mlp_fwd_h2<2, false, 4>",
-    "qsp::k_grp_mlp_fwd_h2<2, true, 8>": "qsp::k_mlp_fwd_h2<2, true, 8>",
-    "qsp::k_grp_mlp_fwd_h1<4>": "qsp::k_mlp_fwd_h1<4>",
-    "qsp::k_grp_mlp_fwd_h1<8>": "qsp::k_mlp_fwd_h1<8>",
-    "qsp::k_grp_mlp_fwd<false>": "qsp::k_mlp_fwd<false>",
-    "qsp::k_grp_mlp_fwd<true>": "qsp::k_mlp_fwd<true>",
-    "qsp::k_grp_mlp_jtj<false>": "qsp::k_mlp_jtj<false>",
-    "qsp::k_grp_mlp_jtj<true>": "qsp::k_mlp_jtj<true>",
+    "qsp::k_mlp_jtj_h2<2, 4, false, true>": "qsp::k_mlp_jtj_h2<2, 4, false, false>",
+    "qsp::k_mlp_jtj_h2<1, 4, false, true>": "qsp::k_mlp_jtj_h2<1, 4, false, false>",
+    "qsp::k_mlp_jtj_h2<2, 8, false, true>": "qsp::k_mlp_jtj_h2<2, 8, false, false>",
+    "qsp::k_mlp_jtj_h2<1, 8, false, true>": "qsp::k_mlp_jtj_h2<1, 8, false, false>",
+    "qsp::k_mlp_jtj_h2<2, 8, true, true>": "qsp::k_mlp_jtj_h2<2, 8, true, false>",
+    "qsp::k_mlp_jtj_h2<1, 8, true, true>": "qsp::k_mlp_jtj_h2<1, 8, true, false>",
+    "qsp::k_mlp_fwd_h2<2, false, 4, true>": "qsp::k_mlp_fwd_h2<2, false, 4, false>",
+    "qsp::k_mlp_fwd_h2<2, true, 8, true>": "qsp::k_mlp_fwd_h2<2, true, 8, false>",
+    "qsp::k_mlp_fwd_h1<4, true>": "qsp::k_mlp_fwd_h1<4, false>",
+    "qsp::k_mlp_fwd_h1<8, true>": "qsp::k_mlp_fwd_h1<8, false>",
+    "qsp::k_mlp_fwd<false, true>": "qsp::k_mlp_fwd<false, false>",
+    "qsp::k_mlp_fwd<true, true>": "qsp::k_mlp_fwd<true, false>",
+    "qsp::k_mlp_jtj<false, true>": "qsp::k_mlp_jtj<false, false>",
+    "qsp::k_mlp_jtj<true, true>": "qsp::k_mlp_jtj<true, false>",
 }
 # the per-item parameter lookup is a few scalar registers more across the tile: what a group kernel may spill beyond its twin's
 # budget (spilled VGPRs, scratch bytes per lane, spilled SGPRs)
@@ -103,8 +103,8 @@ def test_group_kernels_pass_the_mfma_hazard_scan(sdf_isa):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_mfma_hazards as chk
-    txt = open(sdf_isa).read()
-    assert "k_grp_mlp_jtj" in txt and "k_grp_mlp_jtj_h2" in txt
+    from tests.test_isa_budget import kernel_metadata
+    assert not [k for k in GROUP_KERNELS if k not in kernel_metadata(sdf_isa)]
     n, bad = chk.check(sdf_isa)
     assert not bad, bad[:5]
     assert not chk.check_valu_def_before_mfma(sdf_isa)

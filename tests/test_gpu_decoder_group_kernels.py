@@ -1,4 +1,4 @@
-"""Decoder groups on every form of the group kernels (csrc/sdf_body_*.inc, QSP_GRP = 1): the narrow split-fp16 tiles, 32-point
+"""Decoder groups on every form of the group kernels (csrc/sdf_kernels.hpp, GRP = true): the narrow split-fp16 tiles, 32-point
 Jacobian tiles, both wave counts of the Jacobian and screening kernels (selected per process: QSP_JTJ_WAVES, QSP_JTJ_WAVES_T32,
 QSP_SCREEN_WAVES, so those run in a child process), and the group range fallback.  The bar is the one of
 tests/test_gpu_decoder_group.py: a mixed-class batch equals one batch per class bit for bit.  The batches are large enough
@@ -77,7 +77,7 @@ def check_mixed_equals_per_class(decs, cfg, seed=77):
 
 @pytest.mark.parametrize("tile", [64, 32])
 def test_narrow_members_mixed_batch_bit_for_bit(tile):
-    """4 x 256 / code 32 members on the narrow split-fp16 tiles: k_grp_mlp_fwd_h2<2, true, 8>, k_grp_mlp_jtj_h2<2 or 1, 8, true>"""
+    """4 x 256 / code 32 members on the narrow split-fp16 tiles: k_mlp_fwd_h2<2, true, 8, true>, k_mlp_jtj_h2<2 or 1, 8, true, true>"""
     decs = _members("decoder_4x256_c32.npz")
     try:
         for d in decs:
@@ -91,7 +91,7 @@ def test_narrow_members_mixed_batch_bit_for_bit(tile):
 
 
 def test_full_width_members_32_point_tiles_bit_for_bit():
-    """8 x 512 members at 32-point Jacobian tiles (k_grp_mlp_jtj_h2<1, 4, false>), screened forward (k_grp_mlp_fwd_h1<4>)"""
+    """8 x 512 members at 32-point Jacobian tiles (k_mlp_jtj_h2<1, 4, false, true>), screened forward (k_mlp_fwd_h1<4, true>)"""
     decs = _members("decoder_8x512.npz")
     try:
         for d in decs:
@@ -122,7 +122,7 @@ print("ok")
 
 
 def test_other_wave_counts_bit_for_bit():
-    """the wave counts the defaults do not pick: k_grp_mlp_jtj_h2<2, 4, false>, <1, 8, false>, k_grp_mlp_fwd_h1<8>"""
+    """the wave counts the defaults do not pick: k_mlp_jtj_h2<2, 4, false, true>, <1, 8, false, true>, k_mlp_fwd_h1<8, true>"""
     env = dict(os.environ, QSP_JTJ_WAVES="4", QSP_JTJ_WAVES_T32="8", QSP_SCREEN_WAVES="8")
     r = subprocess.run([sys.executable, "-c", CHILD, ROOT], env=env, timeout=600, capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

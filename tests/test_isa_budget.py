@@ -9,30 +9,47 @@ import subprocess
 
 # kernel (demangled prefix) -> (max spilled VGPRs, max scratch bytes per lane, max spilled SGPRs)
 BUDGET = {
-    "qsp::k_mlp_jtj_h2<2, 4, false>": (32, 128, 2),      # (round 4: one SGPR spilled to a VGPR lane by the packed-triangle epilogue)
-    "qsp::k_mlp_jtj_h2<1, 4, false>": (0, 0, 2),
-    "qsp::k_mlp_jtj_h2<2, 8, false>": (32, 128, 0),
-    "qsp::k_mlp_jtj_h2<1, 8, false>": (0, 0, 0),
-    "qsp::k_mlp_jtj_h2<2, 8, true>": (72, 200, 0),       # the NARROW forms: runtime slab counts and skipped slots cost the allocator
-    "qsp::k_mlp_jtj_h2<1, 8, true>": (8, 32, 0),         # some of its footing; they run a fraction of the full shape's work
-    "qsp::k_mlp_fwd_h2<2, false, 4>": (24, 96, 0),
-    "qsp::k_mlp_fwd_h2<2, true, 8>": (64, 160, 0),
-    "qsp::k_mlp_fwd_h1<4>": (0, 0, 0),
-    "qsp::k_mlp_fwd_h1<8>": (20, 80, 0),
+    "qsp::k_mlp_jtj_h2<2, 4, false, false>": (32, 128, 2),   # (round 4: one SGPR spilled to a VGPR lane by the packed-triangle epilogue)
+    "qsp::k_mlp_jtj_h2<1, 4, false, false>": (0, 0, 2),
+    "qsp::k_mlp_jtj_h2<2, 8, false, false>": (32, 128, 0),
+    "qsp::k_mlp_jtj_h2<1, 8, false, false>": (0, 0, 0),
+    "qsp::k_mlp_jtj_h2<2, 8, true, false>": (72, 200, 0),    # the NARROW forms: runtime slab counts and skipped slots cost the allocator
+    "qsp::k_mlp_jtj_h2<1, 8, true, false>": (8, 32, 0),      # some of its footing; they run a fraction of the full shape's work
+    "qsp::k_mlp_fwd_h2<2, false, 4, false>": (24, 96, 0),
+    "qsp::k_mlp_fwd_h2<2, true, 8, false>": (64, 160, 0),
+    "qsp::k_mlp_fwd_h1<4, false>": (0, 0, 0),
+    "qsp::k_mlp_fwd_h1<8, false>": (20, 80, 0),
     "qsp::k_decode_screen<4>": (0, 0, 0),
     "qsp::k_decode_screen<8>": (20, 80, 0),
     "qsp::k_decode_h2<false, false>": (24, 96, 0),
     "qsp::k_decode_h2<true, false>": (40, 160, 0),
     "qsp::k_decode_h2<false, true>": (64, 160, 0),
     "qsp::k_decode_h2<true, true>": (80, 200, 4),
-    "qsp::k_mlp_fwd<false>": (0, 0, 0),
-    "qsp::k_mlp_fwd<true>": (48, 192, 0),
-    "qsp::k_mlp_jtj<false>": (72, 232, 184),             # (round 4: the packed-triangle store of the partial sums walks ONE running
-    "qsp::k_mlp_jtj<true>": (76, 308, 172),              #  index -- sixteen independent per-lane offsets cost 25 more spilled VGPRs here)
+    "qsp::k_mlp_fwd<false, false>": (0, 0, 0),
+    "qsp::k_mlp_fwd<true, false>": (48, 192, 0),
+    "qsp::k_mlp_jtj<false, false>": (72, 232, 184),          # (round 4: the packed-triangle store of the partial sums walks ONE running
+    "qsp::k_mlp_jtj<true, false>": (76, 308, 172),           #  index -- sixteen independent per-lane offsets cost 25 more spilled VGPRs here)
     "qsp::k_decode<false, false>": (0, 0, 0),
     "qsp::k_decode<true, false>": (0, 0, 0),
     "qsp::k_decode<false, true>": (36, 136, 0),
     "qsp::k_decode<true, true>": (40, 160, 0),
+    # The decoder-group forms (last template argument GRP = true; the single-decoder forms above end in false).  The per-item
+    # parameter lookup is a few scalar registers more across the tile: an entry is at most the single-decoder form's plus
+    # (8, 32, 4), tests/test_decoder_group_host.py's SLACK, and lower wherever the kernel compiles to less.
+    "qsp::k_mlp_jtj_h2<2, 4, false, true>": (32, 128, 2),
+    "qsp::k_mlp_jtj_h2<1, 4, false, true>": (0, 0, 2),
+    "qsp::k_mlp_jtj_h2<2, 8, false, true>": (32, 128, 0),
+    "qsp::k_mlp_jtj_h2<1, 8, false, true>": (0, 0, 0),
+    "qsp::k_mlp_jtj_h2<2, 8, true, true>": (72, 200, 0),
+    "qsp::k_mlp_jtj_h2<1, 8, true, true>": (8, 32, 0),
+    "qsp::k_mlp_fwd_h2<2, false, 4, true>": (24, 96, 0),
+    "qsp::k_mlp_fwd_h2<2, true, 8, true>": (64, 160, 0),
+    "qsp::k_mlp_fwd_h1<4, true>": (0, 0, 0),
+    "qsp::k_mlp_fwd_h1<8, true>": (28, 112, 0),              # (the decoder's constants are staged per item: 8 spilled VGPRs over its twin)
+    "qsp::k_mlp_fwd<false, true>": (0, 0, 0),
+    "qsp::k_mlp_fwd<true, true>": (48, 192, 0),
+    "qsp::k_mlp_jtj<false, true>": (72, 232, 160),
+    "qsp::k_mlp_jtj<true, true>": (76, 308, 176),
 }
 
 

@@ -1,12 +1,15 @@
-"""Compare the kernels of two gfx950 assembly listings of csrc/sdf_refine.hip, kernel by kernel.
+r"""Compare the kernels of two gfx950 assembly listings of csrc/sdf_refine.hip, kernel by kernel.
 
 Make each listing with tools/check_mfma_hazards.compile_isa (the command tests/conftest.py uses), in the two trees to compare:
     python -c "import sys; sys.path.insert(0, 'tools'); import check_mfma_hazards as c; c.compile_isa('/tmp/a.s')"
-then  python tools/isa_kernel_diff.py /tmp/a.s /tmp/b.s  [-v NAME]
-Every function body is cut out by its mangled symbol (label to .Lfunc_end, its .size or the next function); assembler comments and the numbers of local basic
-block labels are dropped (they carry source positions and a function-wide counter, not code).  Prints the kernels that are
+then  python tools/isa_kernel_diff.py /tmp/a.s /tmp/b.s  [-v NAME] [--alias REGEX=REPL ...]
+Every function body is cut out by its mangled symbol (label to .Lfunc_end, its .size or the next function) and paired by its
+demangled name; assembler comments, the numbers of local labels, section directives and the function's own symbol are dropped
+(source positions, counters over the function or the file, and where the code is placed: not code).  Prints the kernels that are
 identical, differ, are missing, and are new; -v NAME shows the first lines of the difference of a kernel whose demangled name
-contains NAME.  Exit status 1 if any kernel of the first listing differs or is missing in the second."""
+contains NAME.  --alias pairs kernels under a renaming: re.sub(REGEX, REPL) on the demangled names (up to the argument list) of
+the first listing, e.g. --alias 'k_twin_(\w+)<(.*)>$=k_\1<\2, true>'.  Exit status 1 if any kernel of the first listing differs
+or is missing in the second."""
 import difflib
 import re
 import subprocess
@@ -27,33 +30,42 @@ def bodies(path):
             cur = None
             continue
         if cur:
-            s = re.sub(r";.*$", "", line).rstrip()
+            s = re.sub(r";.*$", "", line).rstrip().replace(cur, "<self>")      # (its own symbol: the kernel descriptor names it)
             s = re.sub(r"\.LBB\d+_", ".LBB_", s)
-            if s:
-                buf.append(s)
+            s = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", s)      # (long branches: a counter over the whole file)
+            if s and not re.match(r"\s*\.(text|section)\b", s):      # (where the code goes -- .text, or a template's own section --
+                buf.append(s)                                       #  is not code)
     return out
 
 
-def demangle(names):
-    r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return dict(zip(names, r))
+def named(path, alias=()):
+    """bodies() keyed by demangled name without the argument list, the aliases applied in the order given"""
+    raw, out = bodies(path), {}
+    dm = subprocess.run(["c++filt"], input="\n".join(raw), capture_output=True, text=True).stdout.split("\n")
+    for sym, name in zip(raw, dm):
+        name = name.replace("void ", "", 1).split("(")[0]
+        for pat, repl in alias:
+            name = re.sub(pat, repl, name)
+        assert name not in out, "two functions named " + name
+        out[name] = raw[sym]
+    return out
 
 
 def main():
-    a, b = bodies(sys.argv[1]), bodies(sys.argv[2])
-    dm = demangle(sorted(set(a) | set(b)))
+    alias = [sys.argv[i + 1].split("=", 1) for i, x in enumerate(sys.argv) if x == "--alias"]
+    a, b = named(sys.argv[1], alias), named(sys.argv[2])
     same = [n for n in a if n in b and a[n] == b[n]]
     diff = [n for n in a if n in b and a[n] != b[n]]
     missing = [n for n in a if n not in b]
     new = [n for n in b if n not in a]
     for tag, lst in (("DIFFERENT", diff), ("MISSING", missing), ("NEW", new)):
-        for n in sorted(lst, key=lambda x: dm[x]):
-            print("%-9s %s" % (tag, dm[n].split("(")[0]))
+        for n in sorted(lst):
+            print("%-9s %s" % (tag, n))
     print("identical %d, different %d, missing %d, new %d" % (len(same), len(diff), len(missing), len(new)))
     if "-v" in sys.argv:
         key = sys.argv[sys.argv.index("-v") + 1]
         for n in diff:
-            if key in dm[n]:
+            if key in n:
                 print("\n".join(list(difflib.unified_diff(a[n], b[n], lineterm="", n=1))[:80]))
                 break
     return 1 if diff or missing else 0
