@@ -1,7 +1,7 @@
 // Device-side mesh extraction: SDF volume on the reference's voxel grid (reconstruct/utils.py:98-117) decoded with the MLP
 // tile kernel, then marching cubes on the GPU (replaces skimage.measure.marching_cubes_lewiner called from
 // reconstruct/utils.py:120-141; MeshExtractor.extract_mesh_from_code, reconstruct/optimizer.py:284-304).
-// Included at the end of sdf_refine.hip (same translation unit: it launches k_decode and reads qsp_decoder).
+// Included at the end of sdf_refine.hip (same translation unit: it decodes with launch_decode and reads qsp_decoder).
 //
 // Marching cubes: method 0 (default, round 4) is Lewiner's, exactly as scikit-image's marching_cubes_lewiner runs it -- mesh_lewiner.hpp,
 // pinned by scikit-image's own output.  Method 1 is the triangulation rounds 2-3 shipped when the dependency had not been found in the
@@ -410,19 +410,7 @@ static int mesh_decode(qsp_mesh_extractor* m, const float* code, bool* hit) {
     memcpy(code64, code, sizeof(float) * m->dec->code_len);
     QSP_HIP(hipMemcpyAsync(m->code, code64, CODE_LEN * sizeof(float), hipMemcpyHostToDevice, s));
     QSP_HIP(hipStreamSynchronize(s));                  // (code64 lives on this stack frame)
-    const int64_t tiles = (m->n + TILE_P - 1) / TILE_P;
-    const int grid = (int)std::min<int64_t>(tiles, 4096);
-    if (m->dec->fwd_bf3 == 2)
-        if (m->dec->P.narrow) hipLaunchKernelGGL((k_decode_h2<false, true>), dim3(grid), dim3(H2_THREADS), sizeof(MlpSmem), s, m->code, m->xyz, m->n,
-                                                 m->dec->Pd, m->sdf, (float*)nullptr);
-        else hipLaunchKernelGGL((k_decode_h2<false, false>), dim3(grid), dim3(H2_THREADS), sizeof(MlpSmem), s, m->code, m->xyz, m->n, m->dec->Pd,
-                                m->sdf, (float*)nullptr);
-    else if (m->dec->fwd_bf3)
-        hipLaunchKernelGGL((k_decode<false, true>), dim3(grid), dim3(MLP_THREADS), sizeof(MlpSmem), s, m->code, m->xyz, m->n,
-                           m->dec->Pd, m->sdf, (float*)nullptr);
-    else
-        hipLaunchKernelGGL(k_decode<false>, dim3(grid), dim3(MLP_THREADS), sizeof(MlpSmem), s, m->code, m->xyz, m->n, m->dec->Pd,
-                           m->sdf, (float*)nullptr);
+    launch_decode(m->dec, m->code, m->xyz, m->n, m->sdf, nullptr);
     QSP_HIP(hipGetLastError());
     QSP_HIP(hipStreamSynchronize(s));
     *hit = range_hit(m->dec);

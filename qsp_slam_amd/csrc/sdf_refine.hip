@@ -572,78 +572,101 @@ static bool range_should_fall_back(qsp_decoder* d) { return d->range_fallback &&
 static int check_range(qsp_decoder* d) { return range_hit(d) ? range_error() : QSP_OK; }
 
 // Waves per workgroup of the split-fp16 Jacobian kernel: 4 (one 512-register wave per SIMD) or 8 (two 256-register waves per
-// SIMD).  QSP_JTJ_WAVES overrides the default for same-box A/B measurements (tools/ab_bench.sh).
-static int jtj_waves() {
-    static int w = 0;
-    if (!w) {
-        const char* e = getenv("QSP_JTJ_WAVES");
-        w = (e && atoi(e) == 8) ? 8 : ((e && atoi(e) == 4) ? 4 : QSP_JTJ_WAVES_DEFAULT);
-    }
-    return w;
+// SIMD).  QSP_JTJ_WAVES overrides the default for same-box A/B measurements (tools/ab_bench.sh); likewise QSP_SCREEN_WAVES for the
+// screening pass and QSP_JTJ_WAVES_T32 for the Jacobian kernel on 32-point tiles.  Each is read once per process.
+static int env_waves(const char* name, int dflt) {
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : 0;
+    return (v == 4 || v == 8) ? v : dflt;
+}
+static int jtj_waves() { static const int w = env_waves("QSP_JTJ_WAVES", QSP_JTJ_WAVES_DEFAULT); return w; }
+static int screen_waves() { static const int w = env_waves("QSP_SCREEN_WAVES", QSP_SCREEN_WAVES_DEFAULT); return w; }
+static int jtj_waves_t32() { static const int w = env_waves("QSP_JTJ_WAVES_T32", 4); return w; }
+
+// A launch form: one instantiation of a decoder kernel together with the block size and the dynamic-LDS bytes it must be
+// launched with.  The three are written down once, in the family helpers below -- the block size from the template arguments
+// that fix it, the LDS bytes from the type the kernel body casts its dynamic LDS to -- and travel together from there:
+// launch() is the only place that starts a decoder kernel, mlp_attr_once() the only one that raises an LDS limit.
+template <class... A> struct Form { void (*fn)(A...); int threads; int lds; };
+template <class Smem, class... A> static Form<A...> form(void (*fn)(A...), int threads) { return {fn, threads, (int)sizeof(Smem)}; }
+template <class... A, class... B> static void launch(const Form<A...>& f, int grid, hipStream_t s, const B&... args) {
+    hipLaunchKernelGGL(f.fn, dim3(grid), dim3(f.threads), f.lds, s, static_cast<A>(args)...);
 }
 
-// ... and of the screening pass (QSP_SCREEN_WAVES; same values either way)
-static int screen_waves() {
-    static int w = 0;
-    if (!w) {
-        const char* e = getenv("QSP_SCREEN_WAVES");
-        w = (e && atoi(e) == 8) ? 8 : ((e && atoi(e) == 4) ? 4 : QSP_SCREEN_WAVES_DEFAULT);
-    }
-    return w;
+// The instantiations that exist, each named once per family: its single-decoder form, or for a decoder group's batch (grp) the
+// form that reads every work item's decoder from the group's parameter array.
+template <bool BF3> static auto fwd_kernel(bool grp) { return form<MlpSmem>(grp ? k_mlp_fwd<BF3, true> : k_mlp_fwd<BF3, false>, MLP_THREADS); }
+template <int NW> static auto fwd_h1_kernel(bool grp) { return form<MlpSmemH1>(grp ? k_mlp_fwd_h1<NW, true> : k_mlp_fwd_h1<NW, false>, 64 * NW); }
+template <int NR, bool NARROW, int NW> static auto fwd_h2_kernel(bool grp) {
+    return form<MlpSmem>(grp ? k_mlp_fwd_h2<NR, NARROW, NW, true> : k_mlp_fwd_h2<NR, NARROW, NW, false>, 64 * NW);
 }
-static int jtj_waves_t32() {
-    static int w = 0;
-    if (!w) {
-        const char* e = getenv("QSP_JTJ_WAVES_T32");
-        w = (e && atoi(e) == 8) ? 8 : 4;
-    }
-    return w;
+template <bool B3> static auto jtj_kernel(bool grp) { return form<MlpSmem>(grp ? k_mlp_jtj<B3, true> : k_mlp_jtj<B3, false>, MLP_THREADS); }
+template <int NR, int NW, bool NARROW> static auto jtj_h2_kernel(bool grp) {
+    return form<MlpSmem>(grp ? k_mlp_jtj_h2<NR, NW, NARROW, true> : k_mlp_jtj_h2<NR, NW, NARROW, false>, 64 * NW);
 }
+template <bool GRAD, bool BF3> static auto decode_kernel() { return form<MlpSmem>(k_decode<GRAD, BF3>, MLP_THREADS); }
+template <bool GRAD, bool NARROW> static auto decode_h2_kernel() { return form<MlpSmem>(k_decode_h2<GRAD, NARROW>, H2_THREADS); }
+template <int NW> static auto decode_screen_kernel() { return form<MlpSmemH1>(k_decode_screen<NW>, 64 * NW); }
+static auto scan_kernel() { return form<float[SCAN_RAYS * SCAN_LD]>(k_scan, SCAN_RAYS); }
 
-// The instantiations of the decoder kernels that run_once() launches, each named once: its single-decoder form, or for a decoder
-// group's batch (grp) the form that reads every work item's decoder from the group's parameter array.  mlp_attr_once() raises the
-// dynamic-LDS limit of both forms through the same helpers.
-template <bool BF3> static auto fwd_kernel(bool grp) { return grp ? k_mlp_fwd<BF3, true> : k_mlp_fwd<BF3, false>; }
-template <int NW> static auto fwd_h1_kernel(bool grp) { return grp ? k_mlp_fwd_h1<NW, true> : k_mlp_fwd_h1<NW, false>; }
-template <int NR, bool NARROW, int NW>
-static auto fwd_h2_kernel(bool grp) { return grp ? k_mlp_fwd_h2<NR, NARROW, NW, true> : k_mlp_fwd_h2<NR, NARROW, NW, false>; }
-template <bool B3> static auto jtj_kernel(bool grp) { return grp ? k_mlp_jtj<B3, true> : k_mlp_jtj<B3, false>; }
-template <int NR, int NW, bool NARROW>
-static auto jtj_h2_kernel(bool grp) { return grp ? k_mlp_jtj_h2<NR, NW, NARROW, true> : k_mlp_jtj_h2<NR, NW, NARROW, false>; }
+// The selectors: which form a pass takes, from the decoder's settings.  A selector returns one family's Form type, so the
+// passes that span two families (exact-f32 / split-bf16 against split-fp16: different argument lists) have one per family and
+// the caller asks `precision == 2` first.  mlp_attr_once() walks each selector's whole domain.
+//
+// one-pass forward
+static auto fwd_form(int bf3, bool grp) { return bf3 ? fwd_kernel<true>(grp) : fwd_kernel<false>(grp); }
+// split-fp16 forward: the one-pass kernel, and (narrow = false) the band pass of the screening pair
+static auto fwd_h2_form(bool narrow, bool grp) { return narrow ? fwd_h2_kernel<2, true, 8>(grp) : fwd_h2_kernel<2, false, 4>(grp); }
+// the one-product pass of the screening pair; waves = screen_waves()
+static auto screen_form(int waves, bool grp) { return waves == 8 ? fwd_h1_kernel<8>(grp) : fwd_h1_kernel<4>(grp); }
+static auto jtj_form(int bf3, bool grp) { return bf3 ? jtj_kernel<true>(grp) : jtj_kernel<false>(grp); }
+// split-fp16 Jacobian: eight waves of 256 registers (two per SIMD) or four of 512 (one per SIMD): same arithmetic, same bits;
+// waves = jtj_waves(), waves_t32 = jtj_waves_t32()
+// (32-point tiles are the latency option -- one tile deep: there the four-wave form is the shorter chain, 180 us against 248 per
+//  tile; QSP_JTJ_WAVES_T32=8 selects the other for measurements)
+static auto jtj_h2_form(bool narrow, int tile_p, int waves, int waves_t32, bool grp) {
+    if (narrow && tile_p == 32) return jtj_h2_kernel<1, 8, true>(grp);      // narrow decoders: eight waves, so that the column
+    if (narrow) return jtj_h2_kernel<2, 8, true>(grp);                      // blocks that exist spread over all SIMDs
+    if (tile_p == 32 && waves_t32 == 8) return jtj_h2_kernel<1, 8, false>(grp);
+    if (tile_p == 32) return jtj_h2_kernel<1, 4, false>(grp);
+    if (waves == 8) return jtj_h2_kernel<2, 8, false>(grp);
+    return jtj_h2_kernel<2, 4, false>(grp);
+}
+// qsp_decode_sdf / qsp_sdf_value_grad / the mesh extractor's volume; bf3 = the precision of the pass (Jacobian with grad, else forward)
+static auto decode_form(bool grad, int bf3, bool narrow) {
+    if (bf3 == 2 && narrow) return grad ? decode_h2_kernel<true, true>() : decode_h2_kernel<false, true>();
+    if (bf3 == 2) return grad ? decode_h2_kernel<true, false>() : decode_h2_kernel<false, false>();
+    if (bf3) return grad ? decode_kernel<true, true>() : decode_kernel<false, true>();
+    return grad ? decode_kernel<true, false>() : decode_kernel<false, false>();
+}
+static auto decode_screen_form(int waves) { return waves == 8 ? decode_screen_kernel<8>() : decode_screen_kernel<4>(); }
 
+// Raises the dynamic-LDS limit of every form a selector can return (once per process): a form that can be launched cannot be
+// missing here.
 static int mlp_attr_once() {
     static bool done = false;
     if (done) return QSP_OK;
-    const auto lds = [](auto kernel, size_t bytes) {
-        return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    const auto raise = [](const auto& f) {
+        return hipFuncSetAttribute((const void*)f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, f.lds);
     };
     for (const bool grp : {false, true}) {
-        QSP_HIP(lds(fwd_kernel<false>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(fwd_kernel<true>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(fwd_h1_kernel<4>(grp), sizeof(MlpSmemH1)));
-        QSP_HIP(lds(fwd_h1_kernel<8>(grp), sizeof(MlpSmemH1)));
-        QSP_HIP(lds(fwd_h2_kernel<2, false, 4>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(fwd_h2_kernel<2, true, 8>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_kernel<false>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_kernel<true>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_h2_kernel<2, 4, false>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_h2_kernel<1, 4, false>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_h2_kernel<2, 8, false>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_h2_kernel<1, 8, false>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_h2_kernel<2, 8, true>(grp), sizeof(MlpSmem)));
-        QSP_HIP(lds(jtj_h2_kernel<1, 8, true>(grp), sizeof(MlpSmem)));
+        for (const int bf3 : {0, 1}) {
+            QSP_HIP(raise(fwd_form(bf3, grp)));
+            QSP_HIP(raise(jtj_form(bf3, grp)));
+        }
+        for (const int waves : {4, 8}) QSP_HIP(raise(screen_form(waves, grp)));
+        for (const bool narrow : {false, true}) {
+            QSP_HIP(raise(fwd_h2_form(narrow, grp)));
+            for (const int tile_p : {32, 64})
+                for (const int waves : {4, 8})
+                    for (const int waves_t32 : {4, 8}) QSP_HIP(raise(jtj_h2_form(narrow, tile_p, waves, waves_t32, grp)));
+        }
     }
-    QSP_HIP(lds(k_scan, sizeof(float) * SCAN_RAYS * SCAN_LD));
-    QSP_HIP(lds(k_decode<false>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode<true>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode<false, true>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode<true, true>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode_h2<false, false>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode_h2<true, false>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode_h2<false, true>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode_h2<true, true>, sizeof(MlpSmem)));
-    QSP_HIP(lds(k_decode_screen<4>, sizeof(MlpSmemH1)));
-    QSP_HIP(lds(k_decode_screen<8>, sizeof(MlpSmemH1)));
+    QSP_HIP(raise(scan_kernel()));
+    for (const bool grad : {false, true})
+        for (const int bf3 : {0, 1, 2})
+            for (const bool narrow : {false, true}) QSP_HIP(raise(decode_form(grad, bf3, narrow)));
+    for (const int waves : {4, 8}) QSP_HIP(raise(decode_screen_form(waves)));
     done = true;
     return QSP_OK;
 }
@@ -759,37 +782,38 @@ extern "C" void qsp_decoder_destroy(qsp_decoder* d) {
     delete d;
 }
 
+// A device allocation owned by a scope: freed when the scope is left, on every path.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }
+    operator T*() const { return p; }
+};
+
+// the decode kernel of the decoder's current settings over n points (device pointers; grad may be null), on the decoder's stream
+static void launch_decode(qsp_decoder* d, const float* code, const float* xyz, int64_t n, float* y, float* grad) {
+    const int64_t tiles = (n + TILE_P - 1) / TILE_P;
+    const int grid = (int)std::min<int64_t>(tiles, 4096);
+    launch(decode_form(grad != nullptr, grad ? d->jac_bf3 : d->fwd_bf3, d->P.narrow), grid, d->stream, code, xyz, n, d->Pd, y, grad);
+}
+
 static int decode_once(qsp_decoder* d, const float* code, const float* xyz, int64_t n, float* y, float* grad, bool* hit) {
     QSP_HIP(hipSetDevice(d->device));
-    float *dc = nullptr, *dx = nullptr, *dy = nullptr, *dg = nullptr;
-    QSP_HIP(hipMalloc((void**)&dc, CODE_LEN * sizeof(float)));
-    QSP_HIP(hipMalloc((void**)&dx, n * 3 * sizeof(float)));
-    QSP_HIP(hipMalloc((void**)&dy, n * sizeof(float)));
-    if (grad) QSP_HIP(hipMalloc((void**)&dg, n * NIN * sizeof(float)));
+    DevBuf<float> dc, dx, dy, dg;
+    QSP_HIP(dc.alloc(CODE_LEN));
+    QSP_HIP(dx.alloc(n * 3));
+    QSP_HIP(dy.alloc(n));
+    if (grad) QSP_HIP(dg.alloc(n * NIN));
     float code64[CODE_LEN] = {};                       // the caller's code has d->code_len entries
     memcpy(code64, code, sizeof(float) * d->code_len);
     QSP_HIP(hipMemcpyAsync(dc, code64, CODE_LEN * sizeof(float), hipMemcpyHostToDevice, d->stream));
     QSP_HIP(hipMemcpyAsync(dx, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    const int64_t tiles = (n + TILE_P - 1) / TILE_P;
-    const int grid = (int)std::min<int64_t>(tiles, 4096);
-    if (grad && d->jac_bf3 == 2)
-        if (d->P.narrow) hipLaunchKernelGGL((k_decode_h2<true, true>), dim3(grid), dim3(H2_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy, dg);
-        else hipLaunchKernelGGL((k_decode_h2<true, false>), dim3(grid), dim3(H2_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy, dg);
-    else if (grad && d->jac_bf3)
-        hipLaunchKernelGGL((k_decode<true, true>), dim3(grid), dim3(MLP_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy, dg);
-    else if (grad)
-        hipLaunchKernelGGL(k_decode<true>, dim3(grid), dim3(MLP_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy, dg);
-    else if (d->fwd_bf3 == 2)
-        if (d->P.narrow) hipLaunchKernelGGL((k_decode_h2<false, true>), dim3(grid), dim3(H2_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy,
-                                            (float*)nullptr);
-        else hipLaunchKernelGGL((k_decode_h2<false, false>), dim3(grid), dim3(H2_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy,
-                                (float*)nullptr);
-    else if (d->fwd_bf3)
-        hipLaunchKernelGGL((k_decode<false, true>), dim3(grid), dim3(MLP_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy,
-                           (float*)nullptr);
-    else
-        hipLaunchKernelGGL(k_decode<false>, dim3(grid), dim3(MLP_THREADS), sizeof(MlpSmem), d->stream, dc, dx, n, d->Pd, dy,
-                           (float*)nullptr);
+    launch_decode(d, dc, dx, n, dy, dg);
     QSP_HIP(hipGetLastError());
     QSP_HIP(hipMemcpyAsync(y, dy, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
     std::vector<float> g67;
@@ -803,10 +827,6 @@ static int decode_once(qsp_decoder* d, const float* code, const float* xyz, int6
     }
     QSP_HIP(hipStreamSynchronize(d->stream));
     if (range_hit(d)) {
-        (void)hipFree(dc);
-        (void)hipFree(dx);
-        (void)hipFree(dy);
-        if (dg) (void)hipFree(dg);
         *hit = true;
         return QSP_OK;
     }
@@ -817,10 +837,6 @@ static int decode_once(qsp_decoder* d, const float* code, const float* xyz, int6
             memcpy(grad + i * (L + 3) + L, g67.data() + i * NIN + CODE_LEN, sizeof(float) * 3);
         }
     }
-    (void)hipFree(dc);
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    if (dg) (void)hipFree(dg);
     return QSP_OK;
 }
 
@@ -851,28 +867,19 @@ extern "C" int qsp_decode_sdf_screen(qsp_decoder* d, const float* code, const fl
     if (n == 0) return QSP_OK;
     if (!d->fp16_ok) return qsp_fail(QSP_ERR_UNSUPPORTED, "split fp16: a weight of this decoder is outside fp16's range");
     QSP_HIP(hipSetDevice(d->device));
-    float *dc = nullptr, *dx = nullptr, *dy = nullptr;
-    QSP_HIP(hipMalloc((void**)&dc, CODE_LEN * sizeof(float)));
-    QSP_HIP(hipMalloc((void**)&dx, n * 3 * sizeof(float)));
-    QSP_HIP(hipMalloc((void**)&dy, n * sizeof(float)));
+    DevBuf<float> dc, dx, dy;
+    QSP_HIP(dc.alloc(CODE_LEN));
+    QSP_HIP(dx.alloc(n * 3));
+    QSP_HIP(dy.alloc(n));
     float code64[CODE_LEN] = {};
     memcpy(code64, code, sizeof(float) * d->code_len);
-    hipError_t e = hipMemcpyAsync(dc, code64, CODE_LEN * sizeof(float), hipMemcpyHostToDevice, d->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dx, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, d->stream);
-    if (e == hipSuccess) {
-        const int grid = (int)std::min<int64_t>((n + H1_ROWS - 1) / H1_ROWS, 4096);
-        if (screen_waves() == 8)
-            hipLaunchKernelGGL(k_decode_screen<8>, dim3(grid), dim3(512), sizeof(MlpSmemH1), d->stream, dc, dx, n, d->Pd, dy);
-        else
-            hipLaunchKernelGGL(k_decode_screen<4>, dim3(grid), dim3(H2_THREADS), sizeof(MlpSmemH1), d->stream, dc, dx, n, d->Pd, dy);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(s1_out, dy, n * sizeof(float), hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    (void)hipFree(dc);
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    if (e != hipSuccess) return qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
+    QSP_HIP(hipMemcpyAsync(dc, code64, CODE_LEN * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    QSP_HIP(hipMemcpyAsync(dx, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    const int grid = (int)std::min<int64_t>((n + H1_ROWS - 1) / H1_ROWS, 4096);
+    launch(decode_screen_form(screen_waves()), grid, d->stream, dc, dx, n, d->Pd, dy);
+    QSP_HIP(hipGetLastError());
+    QSP_HIP(hipMemcpyAsync(s1_out, dy, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    QSP_HIP(hipStreamSynchronize(d->stream));
     return check_range(d);
 }
 
@@ -1279,40 +1286,52 @@ static hipEvent_t next_event(qsp_refine_batch* b, size_t& cursor) {
 // the screened forward is trusted while the largest |s1 - s3| it sees on a band sample stays below this share of the margin
 constexpr float SCREEN_TRUST = 0.5f;
 
+// The profiling marks of run_once(): every pass of an iteration sits between one begin() and one end(kind), which record events
+// on the decoder's stream while profiling is on and do nothing otherwise.  kind: 0 = Jacobian pass, 1 = forward pass, 2 = other.
+struct PassMarks {
+    struct Span { hipEvent_t a, b; int kind; };
+    qsp_refine_batch* b;
+    size_t cur = 0;
+    hipEvent_t a = nullptr;
+    std::vector<Span> spans;
+    hipEvent_t mark() { return b->prof ? next_event(b, cur) : nullptr; }
+    void begin() { a = mark(); }
+    void end(int kind) {
+        if (b->prof) spans.push_back({a, next_event(b, cur), kind});
+    }
+};
+
 // one pass over n_iter Gauss-Newton iterations on the decoder's current pipes; *hit = a split-fp16 kernel left fp16's range,
 // *screen_hit = the screened forward saw |s1 - s3| above half its margin on a band sample (the margin's premise is in doubt)
 static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen_hit) {
     bool screened_any = false;
-    hipStream_t s = b->dec->stream;
+    const qsp_decoder* d = b->dec;
+    hipStream_t s = d->stream;
     const bool grp = b->grp != nullptr;      // a decoder group's batch: the GRP forms of the decoder kernels
-    const MlpParams* Pm = grp ? b->grp->Pd : b->dec->Pd;      // (a group's: one entry per member)
+    const MlpParams* Pm = grp ? b->grp->Pd : d->Pd;      // (a group's: one entry per member)
     const int nH = b->n_hyp;
     const int nw_total = b->nw_sdf + (b->cfg.pose_only ? 0 : NW_REND);
-    size_t cur = 0;
-    struct Span { hipEvent_t a, b; int kind; };
-    std::vector<Span> spans;
-    hipEvent_t e_begin = nullptr, e_end = nullptr;
+    PassMarks pm{b};
     // (the work counters, and with them the queue words: the done counters of the plan tails may be left over from a run cut short)
     QSP_HIP(hipMemsetAsync(b->counters, 0, sizeof(unsigned long long) * 8 + sizeof(int) * 8, s));
-    if (b->prof) e_begin = next_event(b, cur);
+    const hipEvent_t e_begin = pm.mark();
     for (int it = 0; it < n_iter; ++it) {
         RefineCfg cfg = b->cfg;
         cfg.iter = it;
-        if (b->dec->jac_bf3 != 2) cfg.tile_p = TILE_P;      // (32-point tiles exist on the split-fp16 pipe only: the f32 repeat of a
-                                                            //  batch created for them runs 64-point tiles over the same slots)
-        hipEvent_t a = nullptr;
+        if (d->jac_bf3 != 2) cfg.tile_p = TILE_P;      // (32-point tiles exist on the split-fp16 pipe only: the f32 repeat of a
+                                                       //  batch created for them runs 64-point tiles over the same slots)
         if (cfg.pose_only)
             hipLaunchKernelGGL(grp ? k_c0<true> : k_c0<false>, dim3(nH), dim3(MLP_THREADS), 0, s, b->st, b->objs, Pm, b->c0_all);
         if (!cfg.pose_only) {      // (k_sample also forms the bias vectors k_c0 forms in pose-only mode)
-            if (b->prof) a = next_event(b, cur);
+            pm.begin();
             // Two passes pay when the one-pass kernel would need more than one round of 64-point tiles over the chip; a batch that
             // fits one round (a single object per call) is faster in one pass: one tile deep either way, without the second
             // launch.  Both give the same bits, so the choice is free.  (~half of the ray samples are inside the unit ball.)
             int64_t ub_samples = 0;
             for (int h = 0; h < nH; ++h) ub_samples += (int64_t)b->objs_h[b->hyp_obj[h]].n_rays * cfg.n_depth;
-            const int64_t min_samples = b->dec->screen_min_samples >= 0 ? b->dec->screen_min_samples : 2 * (int64_t)b->n_cu * TILE_P;
+            const int64_t min_samples = d->screen_min_samples >= 0 ? d->screen_min_samples : 2 * (int64_t)b->n_cu * TILE_P;
             // (a narrow decoder's one-pass forward on the NARROW tile is cheaper than the full-width screening pass: not screened)
-            const bool screen = b->dec->fwd_bf3 == 2 && b->dec->screen_margin > 0.f && ub_samples > min_samples && !b->dec->P.narrow;
+            const bool screen = d->fwd_bf3 == 2 && d->screen_margin > 0.f && ub_samples > min_samples && !d->P.narrow;
             // the forward kernel's item list is built in k_sample's tail (plan_tail; the forward pass keeps 64-point tiles: tens of
             // thousands of ray samples fill the chip either way) -- or, when the screened pass runs in depth stages, in the tail of
             // each stage's k_stage_list
@@ -1320,13 +1339,18 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
             //  pass is tens of tile rounds over the chip -- C4 and C5; measured break-even around C2, 0.7 M samples: 18.1 against
             //  19.1 ms per step; four yaw flips of one object: 3.8 against 4.8 ms per call)
             const bool staged = screen && cfg.n_depth >= 4 &&
-                                (b->dec->depth_staging == 2 || (b->dec->depth_staging == 1 && ub_samples > 64 * (int64_t)b->n_cu * H1_ROWS));
+                                (d->depth_staging == 2 || (d->depth_staging == 1 && ub_samples > 64 * (int64_t)b->n_cu * H1_ROWS));
             const PlanTail pt_fwd{staged ? nullptr : b->work_fwd, b->qctl, b->qctl + 4, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                   screen ? H1_ROWS : TILE_P, 0};
             hipLaunchKernelGGL(grp ? k_sample<true> : k_sample<false>, dim3(nH), dim3(SAMPLE_THREADS), 0, s, b->st, b->objs, b->rays, cfg,
                                b->valid_rk, b->rk_stride, b->ray_voff, b->ray_stride, Pm, b->c0_all, pt_fwd);
-            if (b->prof) spans.push_back({a, next_event(b, cur), 2});
-            if (b->prof) a = next_event(b, cur);
+            pm.end(2);
+            pm.begin();
+            // every forward kernel takes this argument list; `more` = what its family takes behind it
+            const auto forward = [&](const auto& f, const auto&... more) {
+                launch(f, b->n_cu, s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl,
+                       b->c0_all, more...);
+            };
             if (screen) {
                 // two passes (QSP_DEC_OPT_RENDER_SCREENING): every sample on the one-product tile, then the band around the
                 // surface on the split-fp16 tile; the queue's control words and item list are reused behind the first pass.
@@ -1342,87 +1366,47 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
                                            sg == 0 ? k_mid : cfg.n_depth, pt_st);
                         stage_list = b->stage_idx;
                     }
-                    if (screen_waves() == 8)
-                        hipLaunchKernelGGL(fwd_h1_kernel<8>(grp), dim3(b->n_cu), dim3(512), sizeof(MlpSmemH1), s,
-                                           b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
-                                           b->band_idx, cfg.cut_off + b->dec->screen_margin, b->dec->screen_audit, stage_list);
-                    else
-                        hipLaunchKernelGGL(fwd_h1_kernel<4>(grp), dim3(b->n_cu), dim3(H2_THREADS),
-                                           sizeof(MlpSmemH1), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
-                                           b->band_idx, cfg.cut_off + b->dec->screen_margin, b->dec->screen_audit, stage_list);
+                    forward(screen_form(screen_waves(), grp), b->band_idx, cfg.cut_off + d->screen_margin, d->screen_audit, stage_list);
                     hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, 2, b->st, b->objs, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                        b->work_fwd, b->qctl, TILE_P);
-                    hipLaunchKernelGGL((fwd_h2_kernel<2, false, 4>(grp)), dim3(b->n_cu), dim3(H2_THREADS),
-                                       sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid,
-                                       b->work_fwd, b->qctl, b->c0_all, (const int32_t*)b->band_idx, (unsigned int*)(b->counters + 5));
+                    forward(fwd_h2_form(false, grp), b->band_idx, (unsigned int*)(b->counters + 5));
                 }
                 screened_any = true;
-            } else if (b->dec->fwd_bf3 == 2 && b->dec->P.narrow)
-                hipLaunchKernelGGL((fwd_h2_kernel<2, true, 8>(grp)), dim3(b->n_cu), dim3(512),
-                                   sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
-                                   (const int32_t*)nullptr, (unsigned int*)nullptr);
-            else if (b->dec->fwd_bf3 == 2)
-                hipLaunchKernelGGL((fwd_h2_kernel<2, false, 4>(grp)), dim3(b->n_cu), dim3(H2_THREADS),
-                                   sizeof(MlpSmem), s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all,
-                                   (const int32_t*)nullptr, (unsigned int*)nullptr);
-            else if (b->dec->fwd_bf3)
-                hipLaunchKernelGGL(fwd_kernel<true>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
-                                   s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
+            } else if (d->fwd_bf3 == 2)
+                forward(fwd_h2_form(d->P.narrow, grp), nullptr, nullptr);      // (no band list, no screening statistics)
             else
-                hipLaunchKernelGGL(fwd_kernel<false>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem),
-                                   s, b->st, b->objs, b->rays, cfg, Pm, b->valid_rk, b->rk_stride, b->sdf_valid, b->work_fwd, b->qctl, b->c0_all);
-            if (b->prof) spans.push_back({a, next_event(b, cur), 1});
-            if (b->prof) a = next_event(b, cur);
+                forward(fwd_form(d->fwd_bf3, grp));
+            pm.end(1);
+            pm.begin();
             // (the Jacobian kernel's item list is built in k_scan's tail)
             const PlanTail pt_jtj{b->work_jtj, b->qctl, b->qctl + 5, nH, b->nw_sdf, nw_total - b->nw_sdf, cfg.tile_p, 1};
-            hipLaunchKernelGGL(k_scan, dim3(nH), dim3(SCAN_RAYS), sizeof(float) * SCAN_RAYS * SCAN_LD, s, b->st, b->objs, b->depth, cfg, b->valid_rk, b->rk_stride,
-                               b->ray_voff, b->ray_stride, b->sdf_valid, b->rend_rk, b->rend_deds, b->rend_res, pt_jtj);
-            if (b->prof) spans.push_back({a, next_event(b, cur), 2});
+            launch(scan_kernel(), nH, s, b->st, b->objs, b->depth, cfg, b->valid_rk, b->rk_stride, b->ray_voff, b->ray_stride, b->sdf_valid,
+                   b->rend_rk, b->rend_deds, b->rend_res, pt_jtj);
+            pm.end(2);
         }
-        if (b->prof) a = next_event(b, cur);
+        pm.begin();
         if (cfg.pose_only)      // (no render pass in front of it: the plan is a launch of its own)
             hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, 1, b->st, b->objs, nH, b->nw_sdf, nw_total - b->nw_sdf,
                                b->work_jtj, b->qctl, cfg.tile_p);
-        if (b->dec->jac_bf3 == 2) {
-            const JtjArgs ja{b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, nw_total, b->rend_rk, b->rend_deds, b->rend_res,
-                             b->rk_stride, b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, b->work_jtj,
-                             b->qctl, b->c0_all};
-            // eight waves of 256 registers (two per SIMD) or four of 512 (one per SIMD): same arithmetic, same bits; jtj_waves()
-            // (32-point tiles are the latency option -- one tile deep: there the four-wave form is the shorter chain, 180 us
-            //  against 248 per tile; QSP_JTJ_WAVES_T32=8 selects the other for measurements)
-            if (b->dec->P.narrow && cfg.tile_p == 32)      // narrow decoders: eight waves, so that the column blocks that exist
-                hipLaunchKernelGGL((jtj_h2_kernel<1, 8, true>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);   // spread over all SIMDs
-            else if (b->dec->P.narrow)
-                hipLaunchKernelGGL((jtj_h2_kernel<2, 8, true>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
-            else if (cfg.tile_p == 32 && jtj_waves_t32() == 8)
-                hipLaunchKernelGGL((jtj_h2_kernel<1, 8, false>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
-            else if (cfg.tile_p == 32)
-                hipLaunchKernelGGL((jtj_h2_kernel<1, 4, false>(grp)), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
-            else if (jtj_waves() == 8)
-                hipLaunchKernelGGL((jtj_h2_kernel<2, 8, false>(grp)), dim3(b->n_cu), dim3(512), sizeof(MlpSmem), s, ja);
-            else
-                hipLaunchKernelGGL((jtj_h2_kernel<2, 4, false>(grp)), dim3(b->n_cu), dim3(H2_THREADS), sizeof(MlpSmem), s, ja);
-        }
-        else if (b->dec->jac_bf3)
-            hipLaunchKernelGGL(jtj_kernel<true>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
-                               b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
-                               b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
-                               b->work_jtj, b->qctl, b->c0_all);
+        if (d->jac_bf3 == 2)
+            launch(jtj_h2_form(d->P.narrow, cfg.tile_p, jtj_waves(), jtj_waves_t32(), grp), b->n_cu, s,
+                   JtjArgs{b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, nw_total, b->rend_rk, b->rend_deds, b->rend_res,
+                           b->rk_stride, b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, b->work_jtj,
+                           b->qctl, b->c0_all});
         else
-            hipLaunchKernelGGL(jtj_kernel<false>(grp), dim3(b->n_cu), dim3(MLP_THREADS), sizeof(MlpSmem), s,
-                               b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds, b->rend_res, b->rk_stride,
-                               b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
-                               b->work_jtj, b->qctl, b->c0_all);
-        if (b->prof) spans.push_back({a, next_event(b, cur), 0});
-        if (b->prof) a = next_event(b, cur);
+            launch(jtj_form(d->jac_bf3, grp), b->n_cu, s, b->st, b->objs, b->pts, b->rays, cfg, Pm, b->nw_sdf, b->rend_rk, b->rend_deds,
+                   b->rend_res, b->rk_stride, b->pt_active, b->act_stride, b->res_buf, b->rows, b->rows_stride, b->partials, nw_total,
+                   b->work_jtj, b->qctl, b->c0_all);
+        pm.end(0);
+        pm.begin();
         hipLaunchKernelGGL(k_solve, dim3(nH), dim3(SOLVE_THREADS), 0, s, b->st, b->objs, cfg, b->partials, b->nw_sdf, nw_total,
                            b->pt_active, b->act_stride, b->trH, b->trb, b->trdx, b->counters, b->trrot);
-        if (b->prof) spans.push_back({a, next_event(b, cur), 2});
+        pm.end(2);
         if (cfg.pose_only && it == 4)   // optimizer.py:80-82
             hipLaunchKernelGGL(k_inlier_filter, dim3((b->max_pts + 255) / 256, nH), dim3(256), 0, s, b->st, b->objs,
                                b->res_buf, b->act_stride, b->pt_active);
     }
-    if (b->prof) e_end = next_event(b, cur);
+    const hipEvent_t e_end = pm.mark();
     QSP_HIP(hipGetLastError());
     QSP_HIP(hipStreamSynchronize(s));
     if (range_hit(b->dec)) {
@@ -1449,7 +1433,7 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
         p.screen_max_diff = dmax;
         p.pts_audit = screened_any ? b->last_audited : 0;
         (void)hipEventElapsedTime(&p.ms_total, e_begin, e_end);
-        for (const Span& sp : spans) {
+        for (const PassMarks::Span& sp : pm.spans) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, sp.a, sp.b);
             if (sp.kind == 0) { p.ms_mlp_jtj += ms; p.n_launch_jtj++; }
@@ -1481,14 +1465,11 @@ extern "C" int qsp_refine_batch_run(qsp_refine_batch* b, int32_t n_iter) {
         const int rc_up = batch_upload(b);
         if (rc_up) return rc_up;
     }
+    // The state this run starts from (n_hyp x 432 bytes), in case it has to be repeated: on the f32 pipe after a value left fp16's
+    // range, or in one pass after the self-check of the screened forward (a split-fp16 feature) failed.
     const bool may_fall_back = range_should_fall_back(d);
-    if (may_fall_back) {      // the state this run starts from, in case it has to be repeated on the f32 pipe (n_hyp x 432 bytes)
-        QSP_HIP(hipMemcpyAsync(b->st_snap, b->st, sizeof(HypState) * b->n_hyp, hipMemcpyDeviceToDevice, d->stream));
-        if (b->pt_active) QSP_HIP(hipMemcpyAsync(b->act_snap, b->pt_active, (size_t)b->n_hyp * b->act_stride, hipMemcpyDeviceToDevice, d->stream));
-    }
-    // (the screened forward is a split-fp16 feature; its self-check needs the same snapshot)
     const bool may_screen = d->fwd_bf3 == 2 && d->screen_margin > 0.f;
-    if (may_screen && !may_fall_back) {
+    if (may_fall_back || may_screen) {
         QSP_HIP(hipMemcpyAsync(b->st_snap, b->st, sizeof(HypState) * b->n_hyp, hipMemcpyDeviceToDevice, d->stream));
         if (b->pt_active) QSP_HIP(hipMemcpyAsync(b->act_snap, b->pt_active, (size_t)b->n_hyp * b->act_stride, hipMemcpyDeviceToDevice, d->stream));
     }

@@ -1,7 +1,9 @@
 """The split-fp16 Jacobian kernel exists with four waves of 512 registers per workgroup and with eight of 256 (csrc/sdf_mlp.hpp:
 mlp_tile_h2<.., NW>), and so does the screening pass of the render forward (mlp_tile_h1<.., NW>): the same arithmetic in the same
 order, so the two must give the same bits.  Each variant is selected per process (QSP_JTJ_WAVES, QSP_JTJ_WAVES_T32,
-QSP_SCREEN_WAVES), so the comparison runs the same seeded batch in two child processes."""
+QSP_SCREEN_WAVES), so the comparison runs the same seeded batch in two child processes.  QSP_SCREEN_WAVES also selects the form of
+the screening tile's decode on explicit points (k_decode_screen<4 | 8>), which no batch reaches: it is compared the same way, on 65
+points and on 129 (its tile is 128 rows: one full tile and one with a single live row)."""
 import os
 import subprocess
 import sys
@@ -39,6 +41,10 @@ for tile in (64, 32):
     for k, v in dict(H=tr["H"], b=tr["b"], K=tr["K"], T=T, code=code, loss=loss, good=good).items():
         out["t%d_%s" % (tile, k)] = np.asarray(v)
     b.close()
+rng = np.random.default_rng(65)
+code, x = (0.1 * rng.standard_normal(64)).astype(np.float32), rng.uniform(-0.9, 0.9, (129, 3)).astype(np.float32)
+for n in (65, 129):
+    out["screen_decode_%d" % n] = dec.decode_sdf_screen(code, x[:n])
 np.savez(sys.argv[2], **out)
 '''
 
@@ -53,4 +59,4 @@ def test_four_and_eight_wave_kernels_give_the_same_bits(tmp_path):
     assert sorted(res["4"].files) == sorted(res["8"].files)
     for k in res["4"].files:
         assert np.array_equal(res["4"][k], res["8"][k], equal_nan=True), k
-    assert res["4"]["t64_good"].all()
+    assert res["4"]["t64_good"].all() and np.isfinite(res["4"]["screen_decode_129"]).all()
