@@ -11,6 +11,8 @@ those committed outputs (tests/golden/sdf_*.npz).  The reference has no tests or
 Every function cites the reference lines it follows (paths relative to the reference root).
 """
 import ast
+import contextlib
+
 import numpy as np
 
 F32 = np.float32
@@ -358,6 +360,27 @@ def gn_iteration(dec, cfg, T_oc, z, pts, rays, depth_obs, n_fg):
                 res_render=rt["res"], Jp_render=rt["J_pose"], Jc_render=rt["J_code"], n_valid=rt["n_valid"],
                 K=int(rt["res"].shape[0]), H=H, b=b, dx=dx, loss=loss, loss_sdf=float(loss_s),
                 loss_render=float(loss_r), T_oc_new=T_new, code_new=z_new, J_rot=J_rot, res_rot=res_rot)
+
+
+@contextlib.contextmanager
+def working_precision(dtype):
+    """Every function of this file reads the module global F32 when it is called: inside this block they compute in `dtype`."""
+    global F32
+    old = F32
+    F32 = dtype
+    try:
+        yield
+    finally:
+        F32 = old
+
+
+def gn_iteration_f64(dec, cfg, T_oc, z, pts, rays, depth_obs, n_fg):
+    """gn_iteration evaluated in float64 on the same (float32-valued) weights and inputs: the yardstick of the decoder-family GPU
+    tests.  T_oc may be given in float64 (the exact inverse of a float32 t_cam_obj)."""
+    with working_precision(np.float64):
+        d64 = DecoderWeights(dec.layers, dec.latent_in, dec.code_len, getattr(dec, "use_tanh", False))
+        return gn_iteration(d64, cfg, np.asarray(T_oc, np.float64), np.asarray(z, np.float64), np.asarray(pts, np.float64),
+                            np.asarray(rays, np.float64), np.asarray(depth_obs, np.float64), n_fg)
 
 
 def reconstruct_object(dec, cfg, t_cam_obj, pts, rays, depth, code=None, trace=None):

@@ -98,7 +98,9 @@ def test_narrow_and_embedded_forms_agree_and_the_narrow_one_is_faster(small):
 
 def test_random_narrow_members_of_the_family_vs_the_oracle():
     """narrow shapes specs.json may ask for, random weights, against the numpy decoder on the split-fp16 pipe: with and without
-    a latent_in layer, unequal widths, codes of 8 / 32 / 64"""
+    a latent_in layer, unequal widths, codes of 8 / 32 / 64.  This covers the decode kernels only (qsp_decode_sdf /
+    qsp_sdf_value_grad: mlp_tile_h2<GRAD, 2, .., NR = 2, NW = 4, NARROW>); the refinement kernels' instantiations on family
+    shapes are covered by tests/test_gpu_decoder_family.py."""
     from qsp_slam_amd import DeepSdfDecoder
     rng = np.random.default_rng(15)
 

@@ -117,7 +117,9 @@ def test_unsupported_decoder_family_is_refused(golden_dir):
 @pytest.mark.gpu
 def test_decoder_family_members_match_the_oracle():
     """shapes specs.json may ask for (deep_sdf/deep_sdf_decoder.py:29-63), random weights, against the numpy decoder: no
-    latent_in at all, latent_in at the first possible layer, 8 hidden layers of unequal widths, code lengths 8 / 32 / 64"""
+    latent_in at all, latent_in at the first possible layer, 8 hidden layers of unequal widths, code lengths 8 / 32 / 64.
+    This covers the decode kernels only (qsp_decode_sdf / qsp_sdf_value_grad on the f32 pipe); the fused refinement kernels on
+    family shapes are covered by tests/test_gpu_decoder_family.py."""
     from oracle import sdf_oracle as so
     from qsp_slam_amd import DeepSdfDecoder
     rng = np.random.default_rng(5)
