@@ -9,6 +9,7 @@ import pytest
 
 from oracle import ba_oracle as bo
 from qsp_slam_amd import synth
+from tests.margins import within
 
 pytestmark = pytest.mark.gpu
 
@@ -44,12 +45,53 @@ def compare(r, g):
 
 
 @pytest.mark.parametrize("seed,n,stereo_frac,outl", [(1, 400, 0.3, 0.1), (2, 1500, 0.0, 0.2), (3, 257, 1.0, 0.05),
-                                                     (4, 9, 0.5, 0.0), (5, 40, 0.5, 0.5), (6, 3000, 0.4, 0.1)])
+                                                     (4, 9, 0.5, 0.0), (5, 40, 0.5, 0.5), (6, 3000, 0.4, 0.1),
+                                                     # the counts at which k_pose_opt's control flow changes: the first that runs
+                                                     # (1 stereo + 2 mono), the first that runs all four rounds (`n < 10` breaks
+                                                     # after one; 1 gross outlier), both sides of the 256-thread stride, capacity
+                                                     (15, 3, 0.5, 0.0), (19, 10, 0.5, 0.1), (12, 255, 0.4, 0.1),
+                                                     (13, 256, 0.6, 0.1), (14, 4096, 0.3, 0.1)])
 def test_pose_optimisation_matches_oracle(po, seed, n, stereo_frac, outl):
     pp = synth.make_pose_problem(seed, n=n, stereo_frac=stereo_frac, outlier_frac=outl)
     r = bo.pose_optimization(pp["K"], pp["pose"], pp["X"], pp["obs"], pp["info"], pp["stereo"])
     g = po.optimize(pp["K"], pp["pose"], pp["X"], pp["obs"], pp["info"], pp["stereo"])
+    assert 0 < pp["stereo"].sum() < n or stereo_frac in (0.0, 1.0)
+    assert [int(k) > 0 for k in r["iters"]] == ([True] * 4 if n >= 10 else [True, False, False, False])
     compare(r, g)
+    record("n%04d" % n, r, g)
+
+
+def record(tag, r, g):
+    """the errors `compare` bounds (pose 1e-9, chi2 per iteration 1e-9 relative), measured, for the margins file"""
+    assert within("pose/%s/pose" % tag, np.abs(g["pose"] - r["pose"]).max(), 1e-9)
+    for rnd in range(4):
+        k = min(int(r["iters"][rnd]), int(g["iters"][rnd]))
+        if k:
+            c = r["trace"][rnd, :k, 0]                                    # (np.allclose: |a - b| <= 1e-8 + 1e-9 |b|)
+            assert within("pose/%s/chi2" % tag, (np.abs(g["trace"][rnd, :k, 0] - c) / (np.abs(c) + 10.0)).max(), 1e-9)
+
+
+def test_small_problem_after_a_full_one_on_the_same_handle(po):
+    """`outlier`, `level`, `chi2` and the trace are per-handle device buffers: the 9-correspondence problem (one round) run directly
+    after a 4096-correspondence one (capacity, four rounds, an outlier among its first 9) equals a fresh handle's result bit for bit -- every
+    output the call defines: pose, flags, inlier count, iteration counts and the trace rows of the iterations run -- and the oracle"""
+    from qsp_slam_amd.ba import PoseOptimizer
+    big = synth.make_pose_problem(40, n=4096, stereo_frac=0.3, outlier_frac=0.1)      # (its correspondence 6 ends an outlier)
+    pp = synth.make_pose_problem(4, n=9, stereo_frac=0.5, outlier_frac=0.0)
+    args = [pp[k] for k in ("K", "pose", "X", "obs", "info", "stereo")]
+    gb = po.optimize(*[big[k] for k in ("K", "pose", "X", "obs", "info", "stereo")])
+    assert gb["outlier"][:9].any() and (gb["iters"] > 0).all()          # the state left behind differs from a fresh handle's
+    g = po.optimize(*args)
+    fresh = PoseOptimizer(max_points=4096)
+    try:
+        f = fresh.optimize(*args)
+    finally:
+        fresh.close()
+    assert np.array_equal(g["pose"], f["pose"]) and np.array_equal(g["outlier"], f["outlier"]) and g["n_inliers"] == f["n_inliers"]
+    assert np.array_equal(g["iters"], f["iters"]) and list(g["iters"][1:]) == [0, 0, 0]
+    k = int(g["iters"][0])
+    assert np.array_equal(g["trace"][0, :k], f["trace"][0, :k])
+    compare(bo.pose_optimization(*args), g)
 
 
 def test_fewer_than_three_correspondences(po):

@@ -114,3 +114,47 @@ def test_prior_edge_pulls_the_axes_towards_the_prior_ratio():
     held = EO.prior_fit(init, planes_n[:1], planes[:2], EO.pri_of(gt[7:]) * 1.5, weight=10.0)
     target = EO.pri_of(gt[7:]) * 1.5
     assert np.abs(EO.pri_of(held["ell"][7:]) - target).max() < 0.2 * np.abs(EO.pri_of(free["ell"][7:]) - target).max()
+
+
+def test_huber_kernel_in_closed_form_on_both_sides_of_delta():
+    """RobustKernelHuber (robust_kernel_impl.cpp:78-91) on the SQUARED error: rho = e2 and weight 1 up to delta^2, then
+    rho = 2 delta sqrt(e2) - delta^2 and weight delta / sqrt(e2); value and weight are continuous at e2 = delta^2"""
+    for e2 in (0.0, 0.25, 1.0):
+        assert EO._huber(e2) == (e2, 1.0)
+    for e2, rho, w in ((4.0, 3.0, 0.5), (9.0, 5.0, 1.0 / 3.0), (2.25, 2.0, 1.0 / 1.5)):
+        r0, r1 = EO._huber(e2)
+        assert abs(r0 - rho) < 1e-15 and abs(r1 - w) < 1e-15
+    r0, r1 = EO._huber(16.0, delta=2.0)                                   # |e| = 4 = 2 delta: 2 * 2 * 4 - 4, 2 / 4
+    assert abs(r0 - 12.0) < 1e-15 and abs(r1 - 0.5) < 1e-15
+    assert EO._huber(4.0, delta=2.0) == (4.0, 1.0)
+    for eps in (1e-6, 1e-9, 1e-12):                                       # continuity, and the slope d rho / d e2 = weight
+        lo, hi = EO._huber(1.0 - eps), EO._huber(1.0 + eps)
+        assert abs(hi[0] - lo[0]) < 2.5 * eps and abs(hi[1] - lo[1]) < eps
+    h = 1e-6
+    for e2 in (0.5, 1.7, 6.0):
+        assert abs((EO._huber(e2 + h)[0] - EO._huber(e2 - h)[0]) / (2 * h) - EO._huber(e2)[1]) < 1e-8
+
+
+def test_prior_fit_with_a_gross_outlier_lands_nearer_the_ground_truth_than_without_the_kernel(monkeypatch):
+    """exact planes but ONE plain plane moved by 2 m: its omega e^2 stays above delta, Huber weighs it down (the fit is robust),
+    the identity kernel lets it drag the ellipsoid away"""
+    rng = np.random.default_rng(13)
+    gt, init, planes_n, planes = _prior_scene(rng)
+    planes = planes.copy()
+    planes[4, 3] -= 2.0
+    above = []
+    real = EO._huber
+
+    def counting(e2, delta=1.0):
+        above.append(e2 > delta * delta)
+        return real(e2, delta)
+    monkeypatch.setattr(EO, "_huber", counting)
+    robust = EO.prior_fit(init, planes_n, planes, EO.pri_of(gt[7:]), weight=1.0)
+    assert 0.05 < np.mean(above) < 0.2                                    # one of 13 robust edges, through the whole fit
+    monkeypatch.setattr(EO, "_huber", lambda e2, delta=1.0: (e2, 1.0))
+    plain = EO.prior_fit(init, planes_n, planes, EO.pri_of(gt[7:]), weight=1.0)
+    err_r = np.abs(robust["ell"][[0, 1, 2, 7, 8, 9]] - gt[[0, 1, 2, 7, 8, 9]]).max()
+    err_p = np.abs(plain["ell"][[0, 1, 2, 7, 8, 9]] - gt[[0, 1, 2, 7, 8, 9]]).max()
+    print("centre / half-axes error: Huber %.3f, identity %.3f" % (err_r, err_p))
+    assert err_r < err_p                                                  # (measured 0.240 against 0.359)
+    assert np.all(np.diff(robust["trace"][:, 0]) <= 1e-15)
