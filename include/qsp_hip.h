@@ -62,7 +62,7 @@ typedef struct qsp_decoder qsp_decoder;
 /* Threads.  A decoder owns one HIP stream, one resident refinement batch and a few fields that a call rewrites for its own duration
  * (the f32 override of a range fallback, the screening margin of a self-check repeat).  Every entry point that launches on a
  * decoder -- qsp_decode_sdf*, qsp_sdf_value_grad, qsp_refine_batch_set_state / _run / _get, qsp_reconstruct_objects,
- * qsp_estimate_pose, qsp_refine_detections, qsp_mesh_extract / _from_volume, qsp_decoder_set_option -- takes the decoder's lock:
+ * qsp_estimate_pose, qsp_refine_detections, qsp_mesh_extract / _from_volume and their batch forms, qsp_decoder_set_option -- takes the decoder's lock:
  * host threads may share a decoder and get correct results, one call at a time.  Threads that should overlap on the GPU use a
  * decoder each.  A call on a decoder GROUP (qsp_decoder_group_create below) -- the *_group entry points and the batch calls on a
  * group's batch -- takes the lock of every member, always in the same order (by address), so it cannot deadlock against
@@ -272,7 +272,28 @@ int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_se3, const 
  *   vertices: qsp_mesh_fetch gives (V,3) float32 = float32(index coordinate) * float32(2/(dim-1)) - 1; qsp_mesh_fetch_f64 gives
  *   the reference's own float64 values, float32(index coordinate) * (2.0/(dim-1)) + (-1.0), bit for bit.
  *   qsp_mesh_extractor_set_method(m, 1) selects the triangulation of rounds 2-3 instead (face-consistent segments from a
- *   generated 256-case table, vertices ordered by owning grid point then axis: the same vertex set, other diagonals). */
+ *   generated 256-case table, vertices ordered by owning grid point then axis: the same vertex set, other diagonals).
+ *
+ * Batches: the reference extracts a mesh after every successful refinement (src/LocalMapping_util.cc:832); after a batched
+ * refinement that is many codes at once.  qsp_mesh_extract_batch / qsp_mesh_from_volumes take n codes / volumes and give n
+ * meshes, each the mesh the single call gives (decoded volume bit for bit on every precision -- one exception below --; vertex numbers from 0 and
+ * face indices local to each mesh; scikit-image's values and order), with one launch per stage and one synchronisation for all
+ * of them instead of per mesh.  Method 0 only: with method 1 selected both return QSP_ERR_UNSUPPORTED.  n == 0 is QSP_OK and
+ * touches nothing (a batch result that is resident stays); null pointers and n < 0 are QSP_ERR_INVALID.  An item whose volume
+ * has no surface has counts 0 and does not fail the call.  A split-fp16 decode that leaves fp16's range is repeated on the f32
+ * pipe and counted (per pass, see below), or fails with QSP_ERR_UNSUPPORTED when QSP_DEC_OPT_RANGE_FALLBACK is 0, as
+ * qsp_mesh_extract does.  The one case in which an item is NOT the single call's mesh follows from that: the range flag is
+ * one per decoder, so when some items of a split-fp16 pass leave the range ALL volumes of that pass are decoded on the f32
+ * pipe, also those whose single call would have stayed on the split-fp16 pipe (f32 bits instead of split-fp16 bits: inside the
+ * decoder tolerance, not bit-identical).  Both calls take the decoder's lock.
+ *   Passes: a batch is processed in passes of at most 64 volumes (the default; qsp_mesh_extractor_set_batch_limit sets
+ *   1 .. 64).  A pass needs 20 bytes of scratch per grid point (rounded up to 2048 points per volume) and volume: 42 MB for 64
+ *   volumes of 32^3, 336 MB at 64^3, 2.7 GB at 128^3 -- lower the limit where that is too much.  The n decoded volumes (4 bytes
+ *   per point) and the meshes stay on the device until the next batch call; all buffers grow to the high-water mark and are
+ *   freed with the extractor.  No result depends on the limit.
+ *   State: the batch has buffers of its own.  qsp_mesh_fetch / qsp_mesh_fetch_f64 give the mesh of the last qsp_mesh_extract /
+ *   qsp_mesh_from_volume, qsp_mesh_fetch_batch the result of the last successful batch call, in whatever order single and batch
+ *   calls were mixed; a batch call that fails leaves no batch result. */
 typedef struct qsp_mesh_extractor qsp_mesh_extractor;
 int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, const float* voxel_points, qsp_mesh_extractor** out);
 void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m);
@@ -286,6 +307,16 @@ int qsp_mesh_fetch(qsp_mesh_extractor* m, float* verts, int32_t* faces, float* s
 int qsp_mesh_fetch_f64(qsp_mesh_extractor* m, double* verts);
 /* 0 (default): Lewiner's marching cubes, what the reference calls; 1: the face-consistent table of rounds 2-3 */
 int qsp_mesh_extractor_set_method(qsp_mesh_extractor* m, int32_t method);
+/* B codes (n x code_len floats) -> B meshes; counts per item; results stay on the device */
+int qsp_mesh_extract_batch(qsp_mesh_extractor* m, int32_t n, const float* codes, int64_t* n_verts, int64_t* n_faces);
+/* marching cubes alone on n caller-supplied (dim,dim,dim) volumes */
+int qsp_mesh_from_volumes(qsp_mesh_extractor* m, int32_t n, const float* sdf_volumes, int64_t* n_verts, int64_t* n_faces);
+/* last batch result, concatenated in item order; any pointer may be NULL.  verts: float32 as qsp_mesh_fetch gives them;
+ * verts_f64: the reference's float64 values as qsp_mesh_fetch_f64 gives them; faces: indices local to each item's mesh;
+ * sdf_volumes: (n, dim^3) */
+int qsp_mesh_fetch_batch(qsp_mesh_extractor* m, float* verts, double* verts_f64, int32_t* faces, float* sdf_volumes);
+/* volumes per pass of the batch calls: 1 .. 64 (default 64) */
+int qsp_mesh_extractor_set_batch_limit(qsp_mesh_extractor* m, int32_t max_volumes_per_pass);
 /* method 1's generated case table: ntri[256], tri[256][24] cube-edge ids (edge = 4*axis + u + 2v), -1 padded */
 int qsp_mc_tables(int8_t* ntri, int8_t* tri);
 

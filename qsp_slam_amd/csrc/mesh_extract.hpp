@@ -15,6 +15,21 @@
 //     no diagonal inside a cube face (such a fan exists for every loop of every case).
 // Where Lewiner differs from method 1: the diagonals inside a cell's polygons, interior ambiguity tests and the extra centre vertex
 // of a few of the 33 cases, face order, vertex order.  Both share the scan kernels and the buffers of this file.
+//
+// Batches (qsp_mesh_extract_batch / qsp_mesh_from_volumes / qsp_mesh_fetch_batch; method 0 only): B codes or volumes -> B meshes
+// with the launches and the synchronisations of ONE single call per pass instead of per mesh.  A pass is at most `limit`
+// volumes (QSP_MESH_BATCH_LIMIT_DEFAULT = 64; qsp_mesh_extractor_set_batch_limit lowers it) and runs
+//   k_grid_decode* (one launch, every code of the pass; sdf_kernels.hpp) -> k_lew_count_batch -> k_mc_scan_blocks over all volumes'
+//   scan blocks -> k_mc_scan_top_batch (one workgroup per volume) -> k_mc_scan_top over the volumes' totals -> [the host reads the
+//   pass's totals: the one synchronisation that sizes the outputs] -> k_lew_verts_batch -> k_lew_faces_batch,
+// plain launches in stream order.  Every volume of a pass owns n_pad = whole scan blocks of the count array, so the scan restarts
+// with each volume and a mesh is numbered from 0 exactly as mesh_march numbers it; where its vertices and faces go in the batch's
+// concatenated arrays is the device-side scan of the totals plus what the passes before produced.  Scratch per pass: 20 bytes per
+// padded grid point and volume (64-bit counts, three int32 maps) -- 42 MB for 64 volumes of 32^3, 336 MB at 64^3, 2.7 GB at 128^3
+// --; the B decoded volumes themselves (4 bytes per point) are part of the result and stay until the next batch.  All of it grows to
+// the high-water mark and is freed with the extractor.  A result does not depend on the pass size.
+// The batch has buffers of its own: qsp_mesh_fetch / _fetch_f64 always give the last SINGLE call's mesh, qsp_mesh_fetch_batch the
+// last batch call's, whatever was called in between.
 #pragma once
 
 namespace qsp {
@@ -204,7 +219,7 @@ __global__ __launch_bounds__(256) void k_mc_scan_blocks(unsigned long long* __re
 }
 
 // exclusive scan of the block totals (<= 1024) by one workgroup; total[0] = grand total
-__global__ __launch_bounds__(1024) void k_mc_scan_top(unsigned long long* __restrict__ bsum, int nb, unsigned long long* __restrict__ total) {
+__device__ inline void scan_top(unsigned long long* __restrict__ bsum, int nb, unsigned long long* __restrict__ total) {
     __shared__ unsigned long long wsum[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const unsigned long long v = t < nb ? bsum[t] : 0;
@@ -220,6 +235,16 @@ __global__ __launch_bounds__(1024) void k_mc_scan_top(unsigned long long* __rest
     for (int w = 0; w < wave; ++w) off += wsum[w];
     if (t < nb) bsum[t] = off;
     if (t == 1023) total[0] = off + v;
+}
+__global__ __launch_bounds__(1024) void k_mc_scan_top(unsigned long long* __restrict__ bsum, int nb, unsigned long long* __restrict__ total) {
+    scan_top(bsum, nb, total);
+}
+// a batch pass: volume blockIdx.x's nb block totals, scanned from 0; its totals to vtot (for the host) and voff (scanned next)
+__global__ __launch_bounds__(1024) void k_mc_scan_top_batch(unsigned long long* __restrict__ bsum, int nb, unsigned long long* __restrict__ vtot,
+                                                            unsigned long long* __restrict__ voff) {
+    const int v = blockIdx.x;
+    scan_top(bsum + (size_t)v * nb, nb, vtot + v);
+    if (threadIdx.x == 1023) voff[v] = vtot[v];      // (the thread that wrote it)
 }
 
 __device__ inline unsigned vertex_id(const uint8_t* flags, const unsigned long long* cnt, const unsigned long long* bsum, int64_t q, int a) {
@@ -282,6 +307,8 @@ __global__ __launch_bounds__(256) void k_mc_emit(const float* __restrict__ sdf, 
 
 #include "mesh_lewiner.hpp"
 
+constexpr int QSP_MESH_BATCH_LIMIT_DEFAULT = 64;      // volumes per pass of a batch call
+
 struct qsp_mesh_extractor {
     qsp_decoder* dec = nullptr;
     int marched_method = 0; // of the mesh that is resident
@@ -300,12 +327,27 @@ struct qsp_mesh_extractor {
     int64_t n_verts = 0, n_faces = 0, cap_verts = 0, cap_faces = 0;
     bool have_volume = false;
     int device = 0;         // of the decoder, cached: destroy must not touch a decoder that may already be gone
+    // the batch (see the head of this file): nothing below is touched by the single calls, nothing above by the batch calls
+    struct Batch {
+        int limit = QSP_MESH_BATCH_LIMIT_DEFAULT;
+        float *codes = nullptr, *sdf = nullptr;                     // (B, CODE_LEN), (B, n): the whole batch
+        unsigned long long *cnt = nullptr, *bsum = nullptr, *vtot = nullptr, *voff = nullptr;      // a pass: (V, n_pad), (V, nb), (V), (V + 1: the grand total last)
+        int32_t* vmap = nullptr;                                    // a pass: (V, 3, n)
+        float *verts = nullptr, *vidx = nullptr;                    // the batch's meshes, concatenated in item order
+        int32_t* faces = nullptr;
+        int64_t cap_codes = 0, cap_sdf = 0, cap_cnt = 0, cap_bsum = 0, cap_vtot = 0, cap_voff = 0, cap_vmap = 0, cap_verts = 0, cap_vidx = 0,
+                cap_faces = 0;                                     // elements each buffer holds
+        std::vector<int64_t> n_verts, n_faces;                      // per item
+        int64_t tot_verts = 0, tot_faces = 0;
+        bool have = false;
+    } b;
 };
 
 extern "C" void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    void* ptrs[] = {m->xyz, m->sdf, m->code, m->verts, m->faces, m->flags, m->cnt, m->bsum, m->total, m->tables, m->vidx, m->vmap};
+    void* ptrs[] = {m->xyz, m->sdf, m->code, m->verts, m->faces, m->flags, m->cnt, m->bsum, m->total, m->tables, m->vidx, m->vmap,
+                    m->b.codes, m->b.sdf, m->b.cnt, m->b.bsum, m->b.vtot, m->b.voff, m->b.vmap, m->b.verts, m->b.vidx, m->b.faces};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete m;
@@ -476,6 +518,180 @@ extern "C" int qsp_mesh_fetch_f64(qsp_mesh_extractor* m, double* verts) {
     QSP_HIP(hipStreamSynchronize(m->dec->stream));
     const double spacing = 2.0 / (double)(m->dim - 1);
     for (size_t i = 0; i < tmp.size(); ++i) verts[i] = lewiner ? (double)tmp[i] * spacing + (-1.0) : (double)tmp[i];
+    return QSP_OK;
+}
+
+// ---- batches ---------------------------------------------------------------------------------------------------------------
+// device buffer of at least `need` elements; its first `keep` elements survive when it has to move
+template <class T> static int batch_reserve(T** p, int64_t* cap, int64_t need, int64_t keep, hipStream_t s) {
+    if (need <= *cap) return QSP_OK;
+    const int64_t ncap = need + need / 4 + 1024;
+    T* q = nullptr;
+    QSP_HIP(hipMalloc((void**)&q, sizeof(T) * ncap));
+    if (keep && *p) {
+        hipError_t e = hipMemcpyAsync(q, *p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
+        }
+    } else if (*p) {
+        QSP_HIP(hipStreamSynchronize(s));      // (nothing queued may still use the buffer that goes)
+    }
+    if (*p) (void)hipFree(*p);
+    *p = q;
+    *cap = ncap;
+    return QSP_OK;
+}
+
+// buffers for a batch of n_items volumes in passes of at most n_pass
+static int batch_scratch(qsp_mesh_extractor* m, int64_t n_items, int64_t n_pass) {
+    auto& b = m->b;
+    hipStream_t s = m->dec->stream;
+    int rc = batch_reserve(&b.codes, &b.cap_codes, n_items * qsp::CODE_LEN, 0, s);
+    if (!rc) rc = batch_reserve(&b.sdf, &b.cap_sdf, n_items * m->n, 0, s);
+    if (!rc) rc = batch_reserve(&b.cnt, &b.cap_cnt, n_pass * m->n_pad, 0, s);
+    if (!rc) rc = batch_reserve(&b.bsum, &b.cap_bsum, n_pass * m->nb, 0, s);
+    if (!rc) rc = batch_reserve(&b.vtot, &b.cap_vtot, n_pass, 0, s);
+    if (!rc) rc = batch_reserve(&b.voff, &b.cap_voff, n_pass + 1, 0, s);
+    if (!rc) rc = batch_reserve(&b.vmap, &b.cap_vmap, n_pass * 3 * m->n, 0, s);
+    return rc;
+}
+
+// marching cubes on items [i0, i0 + V) of the batch, whose volumes are in b.sdf; with `decode`, the grid decode of their codes
+// first, in the same stream order.  One synchronisation: the read of the pass's totals (and of the fp16 range flag with them).
+static int batch_pass(qsp_mesh_extractor* m, int64_t i0, int V, bool decode, bool* hit) {
+    using namespace qsp;
+    auto& b = m->b;
+    hipStream_t s = m->dec->stream;
+    float* sdf = b.sdf + i0 * m->n;
+    const lew::BatchPass bp = {m->dim, m->nb, mc::SCAN_BLOCK, m->n, m->n_pad, m->voxel_size};
+    if (decode) launch_grid_decode(m->dec, b.codes + i0 * CODE_LEN, m->xyz, m->n, V, sdf);
+    hipLaunchKernelGGL(lew::k_lew_count_batch, dim3((int)(m->n_pad / 256), V), dim3(256), 0, s, sdf, bp, b.cnt);
+    hipLaunchKernelGGL(mc::k_mc_scan_blocks, dim3(m->nb * V), dim3(256), 0, s, b.cnt, b.bsum);
+    hipLaunchKernelGGL(mc::k_mc_scan_top_batch, dim3(V), dim3(1024), 0, s, b.bsum, m->nb, b.vtot, b.voff);
+    hipLaunchKernelGGL(mc::k_mc_scan_top, dim3(1), dim3(1024), 0, s, b.voff, V, b.voff + V);
+    QSP_HIP(hipGetLastError());
+    std::vector<unsigned long long> tot(V);
+    QSP_HIP(hipMemcpyAsync(tot.data(), b.vtot, sizeof(unsigned long long) * V, hipMemcpyDeviceToHost, s));
+    QSP_HIP(hipStreamSynchronize(s));
+    *hit = decode && range_hit(m->dec);
+    if (*hit) return QSP_OK;        // (the caller decodes the pass again on the f32 pipe, or fails)
+    int64_t nv = 0, nf = 0;
+    for (int v = 0; v < V; ++v) {
+        b.n_verts[i0 + v] = (int64_t)(tot[v] & 0xffffffffull);
+        b.n_faces[i0 + v] = (int64_t)(tot[v] >> 32);
+        nv += b.n_verts[i0 + v];
+        nf += b.n_faces[i0 + v];
+    }
+    if (nv) {       // (a pass without any surface launches nothing more)
+        int rc = batch_reserve(&b.verts, &b.cap_verts, 3 * (b.tot_verts + nv), 3 * b.tot_verts, s);
+        if (!rc) rc = batch_reserve(&b.vidx, &b.cap_vidx, 3 * (b.tot_verts + nv), 3 * b.tot_verts, s);
+        if (!rc) rc = batch_reserve(&b.faces, &b.cap_faces, 3 * (b.tot_faces + nf), 3 * b.tot_faces, s);
+        if (rc) return rc;
+        const dim3 g((int)((m->n + 255) / 256), V);
+        hipLaunchKernelGGL(lew::k_lew_verts_batch, g, dim3(256), 0, s, sdf, bp, b.cnt, b.bsum, b.voff, b.tot_verts, b.vidx, b.verts, b.vmap);
+        hipLaunchKernelGGL(lew::k_lew_faces_batch, g, dim3(256), 0, s, sdf, bp, b.cnt, b.bsum, b.voff, b.tot_faces, b.vmap, b.faces);
+        QSP_HIP(hipGetLastError());
+    }
+    b.tot_verts += nv;
+    b.tot_faces += nf;
+    return QSP_OK;
+}
+
+// the passes of a batch whose codes (decode) or volumes are already on their way to the device
+static int batch_run(qsp_mesh_extractor* m, int32_t n, bool decode, int64_t* n_verts, int64_t* n_faces) {
+    using namespace qsp;
+    auto& b = m->b;
+    b.n_verts.assign(n, 0);
+    b.n_faces.assign(n, 0);
+    b.tot_verts = b.tot_faces = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += b.limit) {
+        const int V = (int)std::min<int64_t>(b.limit, n - i0);
+        bool hit = false;
+        int rc = batch_pass(m, i0, V, decode, &hit);
+        if (rc) return rc;
+        if (hit) {      // as qsp_mesh_extract: this pass again on the f32 pipe, counted once -- or the call fails
+            if (!range_should_fall_back(m->dec)) return range_error();
+            F32Override f32(m->dec);
+            m->dec->n_range_fallbacks++;
+            rc = batch_pass(m, i0, V, decode, &hit);
+            if (rc) return rc;
+        }
+    }
+    QSP_HIP(hipStreamSynchronize(m->dec->stream));
+    b.have = true;
+    for (int32_t i = 0; i < n; ++i) {
+        n_verts[i] = b.n_verts[i];
+        n_faces[i] = b.n_faces[i];
+    }
+    return QSP_OK;
+}
+
+// argument checks of both batch entry points, then the buffers; a batch that fails leaves no batch result behind
+static int batch_begin(qsp_mesh_extractor* m, int32_t n, const void* in, const int64_t* n_verts, const int64_t* n_faces, const char* who) {
+    const std::string w(who);
+    if (!m || !in || !n_verts || !n_faces) return qsp_fail(QSP_ERR_INVALID, (w + ": null argument").c_str());
+    if (n < 0) return qsp_fail(QSP_ERR_INVALID, (w + ": negative number of items").c_str());
+    if (m->method != 0)
+        return qsp_fail(QSP_ERR_UNSUPPORTED, (w + ": batches run Lewiner's marching cubes (method 0) only; method 1, the "
+                                                  "face-consistent table, is extracted one mesh per call").c_str());
+    if (n == 0) return QSP_OK;
+    QSP_HIP(hipSetDevice(m->dec->device));
+    m->b.have = false;
+    return batch_scratch(m, n, std::min<int64_t>(n, m->b.limit));
+}
+
+extern "C" int qsp_mesh_extract_batch(qsp_mesh_extractor* m, int32_t n, const float* codes, int64_t* n_verts, int64_t* n_faces) {
+    using namespace qsp;
+    std::unique_lock<std::recursive_mutex> lk_d;
+    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    const int rc = batch_begin(m, n, codes, n_verts, n_faces, "qsp_mesh_extract_batch");
+    if (rc || n == 0) return rc;
+    const int L = m->dec->code_len;
+    std::vector<float> c64((size_t)n * CODE_LEN, 0.f);           // `codes` holds the decoder's code_len entries per item
+    for (int32_t i = 0; i < n; ++i) memcpy(&c64[(size_t)i * CODE_LEN], codes + (size_t)i * L, sizeof(float) * L);
+    QSP_HIP(hipMemcpyAsync(m->b.codes, c64.data(), sizeof(float) * c64.size(), hipMemcpyHostToDevice, m->dec->stream));
+    QSP_HIP(hipStreamSynchronize(m->dec->stream));               // (c64 lives on this frame)
+    return batch_run(m, n, true, n_verts, n_faces);
+}
+
+extern "C" int qsp_mesh_from_volumes(qsp_mesh_extractor* m, int32_t n, const float* sdf_volumes, int64_t* n_verts, int64_t* n_faces) {
+    std::unique_lock<std::recursive_mutex> lk_d;
+    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    const int rc = batch_begin(m, n, sdf_volumes, n_verts, n_faces, "qsp_mesh_from_volumes");
+    if (rc || n == 0) return rc;
+    QSP_HIP(hipMemcpyAsync(m->b.sdf, sdf_volumes, sizeof(float) * n * m->n, hipMemcpyHostToDevice, m->dec->stream));
+    return batch_run(m, n, false, n_verts, n_faces);
+}
+
+extern "C" int qsp_mesh_fetch_batch(qsp_mesh_extractor* m, float* verts, double* verts_f64, int32_t* faces, float* sdf_volumes) {
+    if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_batch: null extractor");
+    std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
+    const auto& b = m->b;
+    if (!b.have) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_batch: no batch extracted yet");
+    QSP_HIP(hipSetDevice(m->dec->device));
+    hipStream_t s = m->dec->stream;
+    std::vector<float> tmp;
+    if (verts && b.tot_verts) QSP_HIP(hipMemcpyAsync(verts, b.verts, sizeof(float) * 3 * b.tot_verts, hipMemcpyDeviceToHost, s));
+    if (verts_f64 && b.tot_verts) {
+        tmp.resize((size_t)3 * b.tot_verts);
+        QSP_HIP(hipMemcpyAsync(tmp.data(), b.vidx, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost, s));
+    }
+    if (faces && b.tot_faces) QSP_HIP(hipMemcpyAsync(faces, b.faces, sizeof(int32_t) * 3 * b.tot_faces, hipMemcpyDeviceToHost, s));
+    if (sdf_volumes) QSP_HIP(hipMemcpyAsync(sdf_volumes, b.sdf, sizeof(float) * b.n_verts.size() * m->n, hipMemcpyDeviceToHost, s));
+    QSP_HIP(hipStreamSynchronize(s));
+    const double spacing = 2.0 / (double)(m->dim - 1);           // (the values of qsp_mesh_fetch_f64)
+    for (size_t i = 0; i < tmp.size(); ++i) verts_f64[i] = (double)tmp[i] * spacing + (-1.0);
+    return QSP_OK;
+}
+
+extern "C" int qsp_mesh_extractor_set_batch_limit(qsp_mesh_extractor* m, int32_t max_volumes_per_pass) {
+    if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extractor_set_batch_limit: null extractor");
+    if (max_volumes_per_pass < 1 || max_volumes_per_pass > QSP_MESH_BATCH_LIMIT_DEFAULT)
+        return qsp_fail(QSP_ERR_INVALID, "mesh batch limit: 1 .. 64 (QSP_MESH_BATCH_LIMIT_DEFAULT) volumes per pass");
+    std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
+    m->b.limit = max_volumes_per_pass;
     return QSP_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -144,6 +145,42 @@ struct MeshExtractor {
         kw["faces"] = faces;
         return cls(**kw);
     }
+    // the batch form (qsp_mesh_extract_batch): codes (B, >= code_len) -> a list of the objects above, None where a code's volume
+    // has no surface (the Python twin's extract_meshes_from_codes; the single call raises there)
+    py::list extract_meshes_from_codes(farr codes) {
+        if (codes.ndim() != 2) throw std::invalid_argument("codes: a (B, code_len) array");
+        const int64_t n = codes.shape(0), have = codes.shape(1);
+        const int64_t width = decoder.attr("code_len").cast<int>();       // the row length the library reads
+        const int64_t take = std::min<int64_t>(std::min<int64_t>(code_len, have), width);
+        std::vector<float> rows((size_t)std::max<int64_t>(n, 1) * width, 0.f);
+        for (int64_t i = 0; i < n; ++i) memcpy(&rows[(size_t)i * width], codes.data(i, 0), sizeof(float) * take);
+        std::vector<int64_t> nv((size_t)n + 1, 0), nf((size_t)n + 1, 0);
+        check(qsp_mesh_extract_batch(m, (int32_t)n, rows.data(), nv.data(), nf.data()));
+        py::list out;
+        if (n == 0) return out;
+        int64_t tv = 0, tf = 0;
+        for (int64_t i = 0; i < n; ++i) { tv += nv[i]; tf += nf[i]; }
+        std::vector<double> verts((size_t)3 * tv);
+        std::vector<int32_t> faces((size_t)3 * tf);
+        check(qsp_mesh_fetch_batch(m, nullptr, verts.data(), faces.data(), nullptr));
+        py::object cls = py::module_::import("qsp_slam_amd.reconstruct.utils").attr("ForceKeyErrorDict");
+        int64_t v0 = 0, f0 = 0;
+        for (int64_t i = 0; i < n; v0 += nv[i], f0 += nf[i], ++i) {
+            if (nv[i] == 0) {
+                out.append(py::none());
+                continue;
+            }
+            py::array_t<double> v({(py::ssize_t)nv[i], (py::ssize_t)3});
+            py::array_t<int32_t> f({(py::ssize_t)nf[i], (py::ssize_t)3});
+            memcpy(v.mutable_data(), &verts[(size_t)3 * v0], sizeof(double) * 3 * nv[i]);
+            if (nf[i]) memcpy(f.mutable_data(), &faces[(size_t)3 * f0], sizeof(int32_t) * 3 * nf[i]);
+            py::dict kw;
+            kw["vertices"] = v;
+            kw["faces"] = f;
+            out.append(cls(**kw));
+        }
+        return out;
+    }
 };
 
 PYBIND11_MODULE(reconstruct_hip, mod) {
@@ -159,5 +196,6 @@ PYBIND11_MODULE(reconstruct_hip, mod) {
              py::arg("code"));
     py::class_<MeshExtractor>(mod, "MeshExtractor")
         .def(py::init<py::object, int, int>(), py::arg("decoder"), py::arg("code_len") = 64, py::arg("voxels_dim") = 64)
-        .def("extract_mesh_from_code", &MeshExtractor::extract_mesh_from_code, py::arg("code"));
+        .def("extract_mesh_from_code", &MeshExtractor::extract_mesh_from_code, py::arg("code"))
+        .def("extract_meshes_from_codes", &MeshExtractor::extract_meshes_from_codes, py::arg("codes"));
 }

@@ -1718,6 +1718,104 @@ __global__ __launch_bounds__(H2_THREADS) void k_decode_h2(const float* __restric
     if (!(amax <= H2_MAX)) *P->range_flag = 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// grid decode: the n points of ONE grid under n_vol codes -> n_vol volumes in one launch (the mesh extractor's batch;
+// codes (n_vol, CODE_LEN), y_out (n_vol, n)).  Tiles are cut per volume exactly as k_decode / k_decode_h2 cut them (tile t of a
+// volume = its points [t TILE_P, (t + 1) TILE_P), the last one ragged), so no tile holds points of two volumes, and a tile is
+// the same arithmetic on the same inputs whichever workgroup runs it: a volume has the bits of a k_decode launch with its code.
+// A workgroup takes `chunk` consecutive tiles of the (volume, tile) sequence and folds the code into c0 / c4 again (mlp_prepare)
+// whenever the next tile belongs to another volume -- consecutive, so that happens once per volume it touches and not per tile.
+// ---------------------------------------------------------------------------------------------------------------
+template <bool BF3>
+__global__ __launch_bounds__(MLP_THREADS, 2) void k_grid_decode(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n,
+                                                                int n_vol, int chunk, const MlpParams* __restrict__ P,
+                                                                float* __restrict__ y_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
+    const int tpv = (int)((n + TILE_P - 1) / TILE_P);          // (n_vol tpv < 2^31: a pass is at most 64 volumes of 128^3)
+    const int g0 = blockIdx.x * chunk, run = min(chunk, tpv * n_vol - g0);
+    int vol = g0 / tpv, t = g0 - vol * tpv;
+    for (int i = 0; i < run; ++i) {
+        if (i == 0 || t == 0) {             // the run's first tile, or the first tile of the next volume
+            __syncthreads();                // (the tile before is through with c0 / c4)
+            if (threadIdx.x < CODE_LEN) s.code[threadIdx.x] = codes[vol * CODE_LEN + threadIdx.x];
+            mlp_prepare(s, P);
+            y_out += i == 0 ? vol * n : n;
+        }
+        __syncthreads();
+        if (threadIdx.x < TILE_P) {
+            const int64_t v = t * TILE_P + threadIdx.x;
+            float x = 0, y = 0, z = 0;
+            if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
+            s.xin[4 * threadIdx.x + 0] = x;
+            s.xin[4 * threadIdx.x + 1] = y;
+            s.xin[4 * threadIdx.x + 2] = z;
+            s.xin[4 * threadIdx.x + 3] = 0.f;
+        }
+        __syncthreads();
+        if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, P);
+        else mlp_tile<false, 4, false, false>(s, P);
+        if (threadIdx.x < TILE_P) {
+            const int64_t v = t * TILE_P + threadIdx.x;
+            if (v < n) y_out[v] = s.y[threadIdx.x];
+        }
+        if (++t == tpv) {
+            t = 0;
+            ++vol;
+        }
+    }
+}
+
+// grid decode on the split-fp16 tile (four waves per workgroup)
+template <bool NARROW>
+__global__ __launch_bounds__(H2_THREADS) void k_grid_decode_h2(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n,
+                                                               int n_vol, int chunk, const MlpParams* __restrict__ P,
+                                                               float* __restrict__ y_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
+    const int tpv = (int)((n + TILE_P - 1) / TILE_P);
+    const int g0 = blockIdx.x * chunk, run = min(chunk, tpv * n_vol - g0);
+    int vol = g0 / tpv, t = g0 - vol * tpv;
+    bool staged = false;
+    float amax = 0.f;
+    for (int i = 0; i < run; ++i) {
+        if (i == 0 || t == 0) {             // the run's first tile, or the first tile of the next volume
+            __syncthreads();                // (the tile before is through with c0 / c4)
+            if (threadIdx.x < CODE_LEN) s.code[threadIdx.x] = codes[vol * CODE_LEN + threadIdx.x];
+            __syncthreads();
+            for (int u = threadIdx.x; u < HID; u += H2_THREADS) {      // mlp_prepare for 256 threads
+                float a, a4;
+                code_bias(P, u, s.code, a, a4);
+                s.c0[u] = a;
+                s.c4[u] = a4;
+            }
+            y_out += i == 0 ? vol * n : n;
+        }
+        __syncthreads();
+        if (threadIdx.x < TILE_P) {
+            const int64_t v = t * TILE_P + threadIdx.x;
+            float x = 0, y = 0, z = 0;
+            if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
+            s.xin[4 * threadIdx.x + 0] = x;
+            s.xin[4 * threadIdx.x + 1] = y;
+            s.xin[4 * threadIdx.x + 2] = z;
+            s.xin[4 * threadIdx.x + 3] = 0.f;
+        }
+        __syncthreads();
+        mlp_tile_h2<false, 2, !NARROW, 2, 4, NARROW>(s, P, amax, !staged);
+        staged = true;
+        if (threadIdx.x < TILE_P) {
+            const int64_t v = t * TILE_P + threadIdx.x;
+            if (v < n) y_out[v] = s.y[threadIdx.x];
+        }
+        if (++t == tpv) {
+            t = 0;
+            ++vol;
+        }
+    }
+    if (!(amax <= H2_MAX)) *P->range_flag = 1;
+}
+
 // the screening tile (mlp_tile_h1) on explicit query points: what the first pass of the screened forward computes, exposed for
 // the tests and the margin measurement (qsp_decode_sdf_screen) -- these are NOT SDF values of the decoder's precision
 template <int NW>

@@ -607,6 +607,8 @@ template <int NR, int NW, bool NARROW> static auto jtj_h2_kernel(bool grp) {
 template <bool GRAD, bool BF3> static auto decode_kernel() { return form<MlpSmem>(k_decode<GRAD, BF3>, MLP_THREADS); }
 template <bool GRAD, bool NARROW> static auto decode_h2_kernel() { return form<MlpSmem>(k_decode_h2<GRAD, NARROW>, H2_THREADS); }
 template <int NW> static auto decode_screen_kernel() { return form<MlpSmemH1>(k_decode_screen<NW>, 64 * NW); }
+template <bool BF3> static auto grid_decode_kernel() { return form<MlpSmem>(k_grid_decode<BF3>, MLP_THREADS); }
+template <bool NARROW> static auto grid_decode_h2_kernel() { return form<MlpSmem>(k_grid_decode_h2<NARROW>, H2_THREADS); }
 static auto scan_kernel() { return form<float[SCAN_RAYS * SCAN_LD]>(k_scan, SCAN_RAYS); }
 
 // The selectors: which form a pass takes, from the decoder's settings.  A selector returns one family's Form type, so the
@@ -639,6 +641,11 @@ static auto decode_form(bool grad, int bf3, bool narrow) {
     if (bf3) return grad ? decode_kernel<true, true>() : decode_kernel<false, true>();
     return grad ? decode_kernel<true, false>() : decode_kernel<false, false>();
 }
+// the mesh extractor's batch of volumes: the forward forms of decode_form, over one grid and many codes; bf3 = the forward precision
+static auto grid_decode_form(int bf3, bool narrow) {
+    if (bf3 == 2) return narrow ? grid_decode_h2_kernel<true>() : grid_decode_h2_kernel<false>();
+    return bf3 ? grid_decode_kernel<true>() : grid_decode_kernel<false>();
+}
 static auto decode_screen_form(int waves) { return waves == 8 ? decode_screen_kernel<8>() : decode_screen_kernel<4>(); }
 
 // Raises the dynamic-LDS limit of every form a selector can return (once per process): a form that can be launched cannot be
@@ -667,6 +674,8 @@ static int mlp_attr_once() {
         for (const int bf3 : {0, 1, 2})
             for (const bool narrow : {false, true}) QSP_HIP(raise(decode_form(grad, bf3, narrow)));
     for (const int waves : {4, 8}) QSP_HIP(raise(decode_screen_form(waves)));
+    for (const int bf3 : {0, 1, 2})
+        for (const bool narrow : {false, true}) QSP_HIP(raise(grid_decode_form(bf3, narrow)));
     done = true;
     return QSP_OK;
 }
@@ -800,6 +809,15 @@ static void launch_decode(qsp_decoder* d, const float* code, const float* xyz, i
     const int64_t tiles = (n + TILE_P - 1) / TILE_P;
     const int grid = (int)std::min<int64_t>(tiles, 4096);
     launch(decode_form(grad != nullptr, grad ? d->jac_bf3 : d->fwd_bf3, d->P.narrow), grid, d->stream, code, xyz, n, d->Pd, y, grad);
+}
+
+// the forward decode of n_vol codes (device, n_vol x CODE_LEN) over the same n points: y (n_vol, n).  Every workgroup gets the
+// same number of consecutive (volume, tile) pairs, see k_grid_decode.
+static void launch_grid_decode(qsp_decoder* d, const float* codes, const float* xyz, int64_t n, int n_vol, float* y) {
+    const int64_t tiles = (n + TILE_P - 1) / TILE_P * n_vol;
+    const int chunk = (int)((tiles + 4095) / 4096);
+    const int grid = (int)((tiles + chunk - 1) / chunk);
+    launch(grid_decode_form(d->fwd_bf3, d->P.narrow), grid, d->stream, codes, xyz, n, n_vol, chunk, d->Pd, y);
 }
 
 static int decode_once(qsp_decoder* d, const float* code, const float* xyz, int64_t n, float* y, float* grad, bool* hit) {

@@ -433,6 +433,28 @@ def create_voxel_grid(vol_dim=128):
     return v * size - np.float32(1)
 
 
+def split_batch_meshes(n_verts, n_faces, verts, faces, volumes=None):
+    """The per-item results of a batch call from its concatenated arrays (qsp_mesh_fetch_batch): item i owns the next n_verts[i]
+    rows of verts (sum V,3) and the next n_faces[i] rows of faces (sum F,3; indices local to the item's mesh), and volumes[i].
+    Returns a list in item order of (vertices, faces, volume or None), copies that do not keep the batch's arrays alive -- or
+    None for an item without a surface (n_verts[i] == 0)."""
+    n_verts = np.asarray(n_verts, np.int64).reshape(-1)
+    n_faces = np.asarray(n_faces, np.int64).reshape(-1)
+    if len(n_verts) != len(n_faces):
+        raise ValueError("n_verts and n_faces: one entry per item each")
+    v_end, f_end = np.cumsum(n_verts), np.cumsum(n_faces)
+    if len(n_verts) and (v_end[-1] != len(verts) or f_end[-1] != len(faces)):
+        raise ValueError("the counts do not add up to the concatenated arrays")
+    out = []
+    for i in range(len(n_verts)):
+        if n_verts[i] == 0:
+            out.append(None)
+            continue
+        out.append((verts[v_end[i] - n_verts[i]:v_end[i]].copy(), faces[f_end[i] - n_faces[i]:f_end[i]].copy(),
+                    None if volumes is None else volumes[i].copy()))
+    return out
+
+
 class MeshExtractor(object):
     """reconstruct/optimizer.py:284-304.  The SDF volume over create_voxel_grid(voxels_dim) is decoded and triangulated on
     the GPU (qsp_mesh_extract: MLP tile kernel + Lewiner's marching cubes, include/qsp_hip.h); only vertices and faces come
@@ -504,4 +526,56 @@ class MeshExtractor(object):
         out = ForceKeyErrorDict(vertices=verts, faces=faces)
         if return_volume:
             out["sdf_volume"] = vol
+        return out
+
+    # ---- batches: many meshes per call (qsp_mesh_extract_batch / qsp_mesh_from_volumes, include/qsp_hip.h) ------------------
+    def set_batch_limit(self, max_volumes_per_pass):
+        """volumes a batch call holds scratch memory for at a time (1 .. 64, the default); results do not depend on it"""
+        _lib.check(_lib.lib().qsp_mesh_extractor_set_batch_limit(self.handle, int(max_volumes_per_pass)))
+
+    def _batch(self, entry, host, n, volumes):
+        nv, nf = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        _lib.check(entry(self.handle, n, _lib.fptr(host), _lib.i64ptr(nv), _lib.i64ptr(nf)))
+        if n == 0:
+            return []
+        nv, nf = nv[:n], nf[:n]
+        verts = np.empty((int(nv.sum()), 3), np.float64)
+        faces = np.empty((int(nf.sum()), 3), np.int32)
+        vols = np.empty((n,) + (self.voxels_dim,) * 3, np.float32) if volumes else None
+        _lib.check(_lib.lib().qsp_mesh_fetch_batch(self.handle, None, verts.ctypes.data_as(C.POINTER(C.c_double)), _lib.i32ptr(faces),
+                                                   _lib.fptr(vols) if volumes else None))
+        return split_batch_meshes(nv, nf, verts, faces, vols)
+
+    def meshes_from_volumes(self, volumes):
+        """mesh_from_volume on a sequence of (dim,dim,dim) volumes in one call: a list of (vertices, faces) in input order, the
+        values mesh_from_volume gives for each -- or None for a volume without a surface, where the single call raises."""
+        vols = [np.asarray(v, np.float32).reshape(-1) for v in volumes]
+        if any(v.size != self.voxels_dim ** 3 for v in vols):
+            raise ValueError("volumes must be (%d,)*3" % self.voxels_dim)
+        host = _lib.f32c(np.stack(vols)) if vols else np.zeros(1, np.float32)
+        return [r if r is None else r[:2] for r in self._batch(_lib.lib().qsp_mesh_from_volumes, host, len(vols), False)]
+
+    def extract_meshes_from_codes(self, codes, return_volumes=False):
+        """extract_mesh_from_code for a sequence of codes in one call (one grid decode and one marching-cubes launch chain for
+        all of them, csrc/mesh_extract.hpp): a list, in input order, of the ForceKeyErrorDict(vertices (V,3) float64, faces (F,3)
+        int32[, sdf_volume]) objects the single call returns, bit for bit (unless an fp16x2 range fallback repeats a pass on the f32
+        pipe for items that alone would not have needed it).  Every code is cut to code_len and zero-padded as there.
+        One difference: a code whose volume has no surface yields None at its place in the list -- the single call raises like
+        scikit-image, which would lose the other meshes of the batch.  Lewiner's method only (method="table" is not batched)."""
+        start = time.time()
+        rows = [np.asarray(c, np.float32).reshape(-1)[: self.code_len] for c in codes]
+        width = self.decoder.code_len                     # the row length the library reads
+        host = np.zeros((max(len(rows), 1), width), np.float32)
+        for i, c in enumerate(rows):
+            host[i, :min(c.size, width)] = c[:width]
+        res = self._batch(_lib.lib().qsp_mesh_extract_batch, host, len(rows), return_volumes)
+        print("Extract %d meshes takes %f seconds" % (len(rows), time.time() - start))
+        out = []
+        for r in res:
+            if r is not None:
+                d = ForceKeyErrorDict(vertices=r[0], faces=r[1])
+                if return_volumes:
+                    d["sdf_volume"] = r[2]
+                r = d
+            out.append(r)
         return out
