@@ -291,9 +291,12 @@ int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_se3, const 
  *   volumes of 32^3, 336 MB at 64^3, 2.7 GB at 128^3 -- lower the limit where that is too much.  The n decoded volumes (4 bytes
  *   per point) and the meshes stay on the device until the next batch call; all buffers grow to the high-water mark and are
  *   freed with the extractor.  No result depends on the limit.
- *   State: the batch has buffers of its own.  qsp_mesh_fetch / qsp_mesh_fetch_f64 give the mesh of the last qsp_mesh_extract /
- *   qsp_mesh_from_volume, qsp_mesh_fetch_batch the result of the last successful batch call, in whatever order single and batch
- *   calls were mixed; a batch call that fails leaves no batch result. */
+ *   State: single and batch calls run the same launch chain on the same scratch, which holds nothing after a call returns;
+ *   the results (volumes, meshes, counts) are kept twice.  qsp_mesh_fetch / qsp_mesh_fetch_f64 give the mesh of the last
+ *   successful qsp_mesh_extract / qsp_mesh_from_volume, qsp_mesh_fetch_batch the result of the last successful batch call, in
+ *   whatever order single and batch calls were mixed.  A call that fails leaves no result of its kind: after a failed single
+ *   call qsp_mesh_fetch / _fetch_f64 return QSP_ERR_INVALID until the next successful one (as qsp_mesh_fetch_batch does after a
+ *   failed batch call) -- the volume the failed call overwrote cannot be fetched under the counts of the call before. */
 typedef struct qsp_mesh_extractor qsp_mesh_extractor;
 int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, const float* voxel_points, qsp_mesh_extractor** out);
 void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m);

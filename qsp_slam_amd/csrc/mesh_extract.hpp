@@ -1,7 +1,7 @@
 // Device-side mesh extraction: SDF volume on the reference's voxel grid (reconstruct/utils.py:98-117) decoded with the MLP
 // tile kernel, then marching cubes on the GPU (replaces skimage.measure.marching_cubes_lewiner called from
 // reconstruct/utils.py:120-141; MeshExtractor.extract_mesh_from_code, reconstruct/optimizer.py:284-304).
-// Included at the end of sdf_refine.hip (same translation unit: it decodes with launch_decode and reads qsp_decoder).
+// Included at the end of sdf_refine.hip (same translation unit: it decodes with launch_grid_decode and reads qsp_decoder).
 //
 // Marching cubes: method 0 (default, round 4) is Lewiner's, exactly as scikit-image's marching_cubes_lewiner runs it -- mesh_lewiner.hpp,
 // pinned by scikit-image's own output.  Method 1 is the triangulation rounds 2-3 shipped when the dependency had not been found in the
@@ -16,20 +16,23 @@
 // Where Lewiner differs from method 1: the diagonals inside a cell's polygons, interior ambiguity tests and the extra centre vertex
 // of a few of the 33 cases, face order, vertex order.  Both share the scan kernels and the buffers of this file.
 //
-// Batches (qsp_mesh_extract_batch / qsp_mesh_from_volumes / qsp_mesh_fetch_batch; method 0 only): B codes or volumes -> B meshes
-// with the launches and the synchronisations of ONE single call per pass instead of per mesh.  A pass is at most `limit`
-// volumes (QSP_MESH_BATCH_LIMIT_DEFAULT = 64; qsp_mesh_extractor_set_batch_limit lowers it) and runs
-//   k_grid_decode* (one launch, every code of the pass; sdf_kernels.hpp) -> k_lew_count_batch -> k_mc_scan_blocks over all volumes'
+// One launch chain runs every call.  A call is n codes or volumes -> n meshes in passes of at most `limit` volumes
+// (QSP_MESH_BATCH_LIMIT_DEFAULT = 64; qsp_mesh_extractor_set_batch_limit lowers it); the single calls (qsp_mesh_extract /
+// qsp_mesh_from_volume) are n = 1, the batch calls (qsp_mesh_extract_batch / qsp_mesh_from_volumes; method 0 only) any n, with the
+// launches and the synchronisations of one mesh per pass instead of per mesh.  A pass (mesh_pass) runs
+//   k_grid_decode* (one launch, every code of the pass; sdf_kernels.hpp) -> k_lew_count -> k_mc_scan_blocks over all volumes'
 //   scan blocks -> k_mc_scan_top_batch (one workgroup per volume) -> k_mc_scan_top over the volumes' totals -> [the host reads the
-//   pass's totals: the one synchronisation that sizes the outputs] -> k_lew_verts_batch -> k_lew_faces_batch,
-// plain launches in stream order.  Every volume of a pass owns n_pad = whole scan blocks of the count array, so the scan restarts
-// with each volume and a mesh is numbered from 0 exactly as mesh_march numbers it; where its vertices and faces go in the batch's
-// concatenated arrays is the device-side scan of the totals plus what the passes before produced.  Scratch per pass: 20 bytes per
-// padded grid point and volume (64-bit counts, three int32 maps) -- 42 MB for 64 volumes of 32^3, 336 MB at 64^3, 2.7 GB at 128^3
-// --; the B decoded volumes themselves (4 bytes per point) are part of the result and stay until the next batch.  All of it grows to
-// the high-water mark and is freed with the extractor.  A result does not depend on the pass size.
-// The batch has buffers of its own: qsp_mesh_fetch / _fetch_f64 always give the last SINGLE call's mesh, qsp_mesh_fetch_batch the
-// last batch call's, whatever was called in between.
+//   pass's totals: the one synchronisation that sizes the outputs] -> k_lew_verts -> k_lew_faces,
+// plain launches in stream order; with method 1, k_mc_flags and k_mc_emit in the places of the k_lew_* kernels.  Every volume of a
+// pass owns n_pad = whole scan blocks of the count array, so the scan restarts with each volume and a mesh is numbered from 0;
+// where its vertices and faces go in the call's concatenated arrays is the device-side scan of the totals plus what the passes
+// before produced.
+// Buffers: the scratch of a pass -- 20 bytes per padded grid point and volume (64-bit counts, three int32 maps): 42 MB for 64
+// volumes of 32^3, 336 MB at 64^3, 2.7 GB at 128^3 -- exists once and every call uses it: nothing in it is read after the call
+// returns.  What a fetch reads (the decoded or uploaded volumes, 4 bytes per point, the meshes, the counts) exists twice, `single`
+// and `batch`: qsp_mesh_fetch / _fetch_f64 always give the last SINGLE call's mesh, qsp_mesh_fetch_batch the last batch call's,
+// whatever was called in between.  All of it grows to the high-water mark (mesh_reserve) and is freed with the extractor.  A
+// result does not depend on the pass size.  A call that fails leaves no result of its kind to fetch.
 #pragma once
 
 namespace qsp {
@@ -309,45 +312,48 @@ __global__ __launch_bounds__(256) void k_mc_emit(const float* __restrict__ sdf, 
 
 constexpr int QSP_MESH_BATCH_LIMIT_DEFAULT = 64;      // volumes per pass of a batch call
 
+// a device buffer and the number of elements it holds
+template <class T> struct MeshBuf {
+    T* p = nullptr;
+    int64_t cap = 0;
+};
+
 struct qsp_mesh_extractor {
     qsp_decoder* dec = nullptr;
-    int marched_method = 0; // of the mesh that is resident
+    int device = 0;         // of the decoder, cached: destroy must not touch a decoder that may already be gone
     int method = 0;         // 0: Lewiner's marching cubes, what the reference calls (mesh_lewiner.hpp); 1: the face-consistent table of rounds 2-3
-    float* vidx = nullptr;  // Lewiner: the vertices as float32 index coordinates (the float64 mesh of the reference is these x spacing - 1)
-    int32_t* vmap = nullptr;   // Lewiner: (axis, grid point) -> vertex number
+    int limit = QSP_MESH_BATCH_LIMIT_DEFAULT;
     int dim = 0;
     int64_t n = 0, n_pad = 0;
     int nb = 0;
     float voxel_size = 0;
-    float *xyz = nullptr, *sdf = nullptr, *code = nullptr, *verts = nullptr;
-    int32_t* faces = nullptr;
-    uint8_t* flags = nullptr;
-    unsigned long long *cnt = nullptr, *bsum = nullptr, *total = nullptr;
+    float* xyz = nullptr;
     qsp::mc::Tables* tables = nullptr;
-    int64_t n_verts = 0, n_faces = 0, cap_verts = 0, cap_faces = 0;
-    bool have_volume = false;
-    int device = 0;         // of the decoder, cached: destroy must not touch a decoder that may already be gone
-    // the batch (see the head of this file): nothing below is touched by the single calls, nothing above by the batch calls
-    struct Batch {
-        int limit = QSP_MESH_BATCH_LIMIT_DEFAULT;
-        float *codes = nullptr, *sdf = nullptr;                     // (B, CODE_LEN), (B, n): the whole batch
-        unsigned long long *cnt = nullptr, *bsum = nullptr, *vtot = nullptr, *voff = nullptr;      // a pass: (V, n_pad), (V, nb), (V), (V + 1: the grand total last)
-        int32_t* vmap = nullptr;                                    // a pass: (V, 3, n)
-        float *verts = nullptr, *vidx = nullptr;                    // the batch's meshes, concatenated in item order
-        int32_t* faces = nullptr;
-        int64_t cap_codes = 0, cap_sdf = 0, cap_cnt = 0, cap_bsum = 0, cap_vtot = 0, cap_voff = 0, cap_vmap = 0, cap_verts = 0, cap_vidx = 0,
-                cap_faces = 0;                                     // elements each buffer holds
-        std::vector<int64_t> n_verts, n_faces;                      // per item
+    // scratch of a pass of V volumes, shared by all calls: nothing in it is read after the call that filled it
+    struct Scratch {
+        MeshBuf<float> codes;                           // (items, CODE_LEN): the whole call's
+        MeshBuf<unsigned long long> cnt, bsum, vtot, voff;      // (V, n_pad), (V, nb), (V), (V + 1: the grand total last)
+        MeshBuf<int32_t> vmap;                          // Lewiner: (V, 3, n), (axis, grid point) -> vertex number
+        MeshBuf<uint8_t> flags;                         // method 1: (n_pad)
+    } s;
+    // what a fetch reads: one for the single calls, one for the batch calls
+    struct Result {
+        MeshBuf<float> sdf;                             // (items, n): decoded or uploaded
+        MeshBuf<float> verts, vidx;                     // the meshes, concatenated in item order; vidx (Lewiner): float32 index
+        MeshBuf<int32_t> faces;                         // coordinates (the float64 mesh of the reference is these x spacing - 1)
+        std::vector<int64_t> n_verts, n_faces;          // per item
         int64_t tot_verts = 0, tot_faces = 0;
+        int method = 0;                                 // that marched it
         bool have = false;
-    } b;
+    } single, batch;
 };
 
 extern "C" void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    void* ptrs[] = {m->xyz, m->sdf, m->code, m->verts, m->faces, m->flags, m->cnt, m->bsum, m->total, m->tables, m->vidx, m->vmap,
-                    m->b.codes, m->b.sdf, m->b.cnt, m->b.bsum, m->b.vtot, m->b.voff, m->b.vmap, m->b.verts, m->b.vidx, m->b.faces};
+    void* ptrs[] = {m->xyz, m->tables, m->s.codes.p, m->s.cnt.p, m->s.bsum.p, m->s.vtot.p, m->s.voff.p, m->s.vmap.p, m->s.flags.p,
+                    m->single.sdf.p, m->single.verts.p, m->single.vidx.p, m->single.faces.p,
+                    m->batch.sdf.p, m->batch.verts.p, m->batch.vidx.p, m->batch.faces.p};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete m;
@@ -371,91 +377,147 @@ extern "C" int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, c
     m->nb = (int)((m->n + mc::SCAN_BLOCK - 1) / mc::SCAN_BLOCK);
     m->n_pad = (int64_t)m->nb * mc::SCAN_BLOCK;
     m->voxel_size = (float)(2.0 / (voxels_dim - 1));
-    int rc = QSP_OK;
-#define MAL(field, bytes)                                                                     \
-    if (!rc) {                                                                                \
-        hipError_t e_ = hipMalloc((void**)&m->field, (bytes));                                \
-        if (e_ != hipSuccess) rc = qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e_));           \
-    }
-    MAL(xyz, sizeof(float) * 3 * m->n);
-    MAL(sdf, sizeof(float) * m->n);
-    MAL(code, sizeof(float) * CODE_LEN);
-    MAL(flags, m->n_pad);
-    MAL(cnt, sizeof(unsigned long long) * m->n_pad);
-    MAL(bsum, sizeof(unsigned long long) * 1024);
-    MAL(total, sizeof(unsigned long long));
-    MAL(tables, sizeof(mc::Tables));
-    MAL(vmap, sizeof(int32_t) * 3 * m->n);
-#undef MAL
-    if (!rc) {
-        hipError_t e = hipMemcpy(m->xyz, voxel_points, sizeof(float) * 3 * m->n, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(m->tables, &host_tables, sizeof(mc::Tables), hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
-    }
-    if (rc) {
+    // the two buffers that are filled here; every other one grows with the calls (mesh_call)
+    hipError_t e = hipMalloc((void**)&m->xyz, sizeof(float) * 3 * m->n);
+    if (e == hipSuccess) e = hipMalloc((void**)&m->tables, sizeof(mc::Tables));
+    if (e == hipSuccess) e = hipMemcpy(m->xyz, voxel_points, sizeof(float) * 3 * m->n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->tables, &host_tables, sizeof(mc::Tables), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
         qsp_mesh_extractor_destroy(m);
-        return rc;
+        return qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
     }
     *out = m;
     return QSP_OK;
 }
 
-static int mesh_march(qsp_mesh_extractor* m, int64_t* n_verts, int64_t* n_faces) {
-    using namespace qsp;
-    hipStream_t s = m->dec->stream;
-    const int g = (int)(m->n_pad / 256);
-    const bool lewiner = m->method == 0;
-    if (lewiner) hipLaunchKernelGGL(lew::k_lew_count, dim3(g), dim3(256), 0, s, m->sdf, m->dim, m->cnt, m->n_pad);
-    else hipLaunchKernelGGL(mc::k_mc_flags, dim3(g), dim3(256), 0, s, m->sdf, m->dim, m->tables, m->flags, m->cnt, m->n_pad);
-    hipLaunchKernelGGL(mc::k_mc_scan_blocks, dim3(m->nb), dim3(256), 0, s, m->cnt, m->bsum);
-    hipLaunchKernelGGL(mc::k_mc_scan_top, dim3(1), dim3(1024), 0, s, m->bsum, m->nb, m->total);
-    unsigned long long tot = 0;
-    QSP_HIP(hipMemcpyAsync(&tot, m->total, sizeof(tot), hipMemcpyDeviceToHost, s));
-    QSP_HIP(hipStreamSynchronize(s));
-    m->n_verts = (int64_t)(tot & 0xffffffffull);
-    m->n_faces = (int64_t)(tot >> 32);
-    if (m->n_verts > m->cap_verts) {
-        if (m->verts) (void)hipFree(m->verts);
-        if (m->vidx) (void)hipFree(m->vidx);
-        m->verts = m->vidx = nullptr;
-        m->cap_verts = m->n_verts + m->n_verts / 4 + 1024;
-        QSP_HIP(hipMalloc((void**)&m->verts, sizeof(float) * 3 * m->cap_verts));
-        QSP_HIP(hipMalloc((void**)&m->vidx, sizeof(float) * 3 * m->cap_verts));
+// device buffer of at least `need` elements; its first `keep` elements survive when it has to move
+template <class T> static int mesh_reserve(MeshBuf<T>& b, int64_t need, int64_t keep, hipStream_t s) {
+    if (need <= b.cap) return QSP_OK;
+    const int64_t ncap = need + need / 4 + 1024;
+    T* q = nullptr;
+    QSP_HIP(hipMalloc((void**)&q, sizeof(T) * ncap));
+    if (keep && b.p) {
+        hipError_t e = hipMemcpyAsync(q, b.p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
+        }
+    } else if (b.p) {
+        QSP_HIP(hipStreamSynchronize(s));      // (nothing queued may still use the buffer that goes)
     }
-    if (m->n_faces > m->cap_faces) {
-        if (m->faces) (void)hipFree(m->faces);
-        m->faces = nullptr;
-        m->cap_faces = m->n_faces + m->n_faces / 4 + 1024;
-        QSP_HIP(hipMalloc((void**)&m->faces, sizeof(int32_t) * 3 * m->cap_faces));
-    }
-    if (m->n_verts && lewiner) {
-        const int gp = (int)((m->n + 255) / 256);
-        hipLaunchKernelGGL(lew::k_lew_verts, dim3(gp), dim3(256), 0, s, m->sdf, m->dim, m->voxel_size, m->cnt, m->bsum, mc::SCAN_BLOCK,
-                           m->vidx, m->verts, m->vmap);
-        hipLaunchKernelGGL(lew::k_lew_faces, dim3(gp), dim3(256), 0, s, m->sdf, m->dim, m->cnt, m->bsum, mc::SCAN_BLOCK, m->vmap, m->faces);
-    } else if (m->n_verts)
-        hipLaunchKernelGGL(mc::k_mc_emit, dim3((int)((m->n + 255) / 256)), dim3(256), 0, s, m->sdf, m->dim, m->voxel_size, m->tables,
-                           m->flags, m->cnt, m->bsum, m->verts, m->faces);
-    m->marched_method = m->method;
-    QSP_HIP(hipGetLastError());
-    QSP_HIP(hipStreamSynchronize(s));
-    m->have_volume = true;
-    if (n_verts) *n_verts = m->n_verts;
-    if (n_faces) *n_faces = m->n_faces;
+    if (b.p) (void)hipFree(b.p);
+    b.p = q;
+    b.cap = ncap;
     return QSP_OK;
 }
 
-static int mesh_decode(qsp_mesh_extractor* m, const float* code, bool* hit) {
+// marching cubes on items [i0, i0 + V) of a call, whose volumes are in r.sdf; with `decode`, the grid decode of their codes
+// first, in the same stream order.  One synchronisation: the read of the pass's totals (and of the fp16 range flag with them).
+// Method 1 (k_mc_flags / k_mc_emit) is a pass of V = 1 of a single call: voff[0] = 0 and nothing before it, so its kernels
+// take the pass's buffers as they are.
+static int mesh_pass(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int64_t i0, int V, bool decode, bool* hit) {
     using namespace qsp;
+    auto& sc = m->s;
     hipStream_t s = m->dec->stream;
-    float code64[CODE_LEN] = {};                       // `code` holds the decoder's code_len entries
-    memcpy(code64, code, sizeof(float) * m->dec->code_len);
-    QSP_HIP(hipMemcpyAsync(m->code, code64, CODE_LEN * sizeof(float), hipMemcpyHostToDevice, s));
-    QSP_HIP(hipStreamSynchronize(s));                  // (code64 lives on this stack frame)
-    launch_decode(m->dec, m->code, m->xyz, m->n, m->sdf, nullptr);
+    float* sdf = r.sdf.p + i0 * m->n;
+    const bool lewiner = m->method == 0;
+    const lew::BatchPass bp = {m->dim, m->nb, mc::SCAN_BLOCK, m->n, m->n_pad, m->voxel_size};
+    if (decode) launch_grid_decode(m->dec, sc.codes.p + i0 * CODE_LEN, m->xyz, m->n, V, sdf);
+    const dim3 gc((int)(m->n_pad / 256), V);
+    if (lewiner) hipLaunchKernelGGL(lew::k_lew_count, gc, dim3(256), 0, s, sdf, bp, sc.cnt.p);
+    else hipLaunchKernelGGL(mc::k_mc_flags, gc, dim3(256), 0, s, sdf, m->dim, m->tables, sc.flags.p, sc.cnt.p, m->n_pad);
+    hipLaunchKernelGGL(mc::k_mc_scan_blocks, dim3(m->nb * V), dim3(256), 0, s, sc.cnt.p, sc.bsum.p);
+    hipLaunchKernelGGL(mc::k_mc_scan_top_batch, dim3(V), dim3(1024), 0, s, sc.bsum.p, m->nb, sc.vtot.p, sc.voff.p);
+    hipLaunchKernelGGL(mc::k_mc_scan_top, dim3(1), dim3(1024), 0, s, sc.voff.p, V, sc.voff.p + V);
     QSP_HIP(hipGetLastError());
+    std::vector<unsigned long long> tot(V);
+    QSP_HIP(hipMemcpyAsync(tot.data(), sc.vtot.p, sizeof(unsigned long long) * V, hipMemcpyDeviceToHost, s));
     QSP_HIP(hipStreamSynchronize(s));
-    *hit = range_hit(m->dec);
+    *hit = decode && range_hit(m->dec);
+    if (*hit) return QSP_OK;        // (the caller decodes the pass again on the f32 pipe, or fails)
+    int64_t nv = 0, nf = 0;
+    for (int v = 0; v < V; ++v) {
+        r.n_verts[i0 + v] = (int64_t)(tot[v] & 0xffffffffull);
+        r.n_faces[i0 + v] = (int64_t)(tot[v] >> 32);
+        nv += r.n_verts[i0 + v];
+        nf += r.n_faces[i0 + v];
+    }
+    if (nv) {       // (a pass without any surface launches nothing more)
+        int rc = mesh_reserve(r.verts, 3 * (r.tot_verts + nv), 3 * r.tot_verts, s);
+        if (!rc) rc = mesh_reserve(r.vidx, 3 * (r.tot_verts + nv), 3 * r.tot_verts, s);
+        if (!rc) rc = mesh_reserve(r.faces, 3 * (r.tot_faces + nf), 3 * r.tot_faces, s);
+        if (rc) return rc;
+        const dim3 g((int)((m->n + 255) / 256), V);
+        if (lewiner) {
+            hipLaunchKernelGGL(lew::k_lew_verts, g, dim3(256), 0, s, sdf, bp, sc.cnt.p, sc.bsum.p, sc.voff.p, r.tot_verts, r.vidx.p, r.verts.p,
+                               sc.vmap.p);
+            hipLaunchKernelGGL(lew::k_lew_faces, g, dim3(256), 0, s, sdf, bp, sc.cnt.p, sc.bsum.p, sc.voff.p, r.tot_faces, sc.vmap.p, r.faces.p);
+        } else
+            hipLaunchKernelGGL(mc::k_mc_emit, g, dim3(256), 0, s, sdf, m->dim, m->voxel_size, m->tables, sc.flags.p, sc.cnt.p, sc.bsum.p,
+                               r.verts.p, r.faces.p);
+        QSP_HIP(hipGetLastError());
+    }
+    r.tot_verts += nv;
+    r.tot_faces += nf;
+    return QSP_OK;
+}
+
+// A call: n codes (decode; the decoder's code_len entries each) or n volumes from the host -> r.  r holds no result until the
+// call has succeeded.  Buffers for n volumes in passes of at most `limit`, the input's upload, then the passes.
+static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32_t n, const float* in, bool decode) {
+    using namespace qsp;
+    QSP_HIP(hipSetDevice(m->dec->device));
+    r.have = false;
+    auto& sc = m->s;
+    hipStream_t s = m->dec->stream;
+    const bool lewiner = m->method == 0;
+    const int64_t n_pass = std::min<int64_t>(n, m->limit);
+    int rc = mesh_reserve(sc.codes, (int64_t)n * CODE_LEN, 0, s);
+    if (!rc) rc = mesh_reserve(r.sdf, n * m->n, 0, s);
+    if (!rc) rc = mesh_reserve(sc.cnt, n_pass * m->n_pad, 0, s);
+    if (!rc) rc = mesh_reserve(sc.bsum, n_pass * m->nb, 0, s);
+    if (!rc) rc = mesh_reserve(sc.vtot, n_pass, 0, s);
+    if (!rc) rc = mesh_reserve(sc.voff, n_pass + 1, 0, s);
+    if (!rc) rc = mesh_reserve(sc.vmap, lewiner ? n_pass * 3 * m->n : 0, 0, s);
+    if (!rc) rc = mesh_reserve(sc.flags, lewiner ? 0 : m->n_pad, 0, s);
+    if (rc) return rc;
+    if (decode) {
+        const int L = m->dec->code_len;
+        std::vector<float> c64((size_t)n * CODE_LEN, 0.f);           // padded to CODE_LEN
+        for (int32_t i = 0; i < n; ++i) memcpy(&c64[(size_t)i * CODE_LEN], in + (size_t)i * L, sizeof(float) * L);
+        QSP_HIP(hipMemcpyAsync(sc.codes.p, c64.data(), sizeof(float) * c64.size(), hipMemcpyHostToDevice, s));
+        QSP_HIP(hipStreamSynchronize(s));                            // (c64 lives on this frame)
+    } else {
+        QSP_HIP(hipMemcpyAsync(r.sdf.p, in, sizeof(float) * n * m->n, hipMemcpyHostToDevice, s));
+    }
+    r.n_verts.assign(n, 0);
+    r.n_faces.assign(n, 0);
+    r.tot_verts = r.tot_faces = 0;
+    r.method = m->method;
+    for (int64_t i0 = 0; i0 < n; i0 += m->limit) {
+        const int V = (int)std::min<int64_t>(m->limit, n - i0);
+        bool hit = false;
+        rc = mesh_pass(m, r, i0, V, decode, &hit);
+        if (rc) return rc;
+        if (hit) {      // a value of the grid decode left fp16's range: this pass again on the f32 pipe, counted once -- or the call fails
+            if (!range_should_fall_back(m->dec)) return range_error();
+            F32Override f32(m->dec);
+            m->dec->n_range_fallbacks++;
+            rc = mesh_pass(m, r, i0, V, decode, &hit);
+            if (rc) return rc;
+        }
+    }
+    QSP_HIP(hipStreamSynchronize(s));
+    r.have = true;
+    return QSP_OK;
+}
+
+static int mesh_single(qsp_mesh_extractor* m, const float* in, bool decode, int64_t* n_verts, int64_t* n_faces) {
+    const int rc = mesh_call(m, m->single, 1, in, decode);
+    if (rc) return rc;
+    if (n_verts) *n_verts = m->single.n_verts[0];
+    if (n_faces) *n_faces = m->single.n_faces[0];
     return QSP_OK;
 }
 
@@ -463,39 +525,81 @@ extern "C" int qsp_mesh_extract(qsp_mesh_extractor* m, const float* code, int64_
     std::unique_lock<std::recursive_mutex> lk_d;
     if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
     if (!m || !code) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extract: null argument");
-    QSP_HIP(hipSetDevice(m->dec->device));
-    bool hit = false;
-    int rc = mesh_decode(m, code, &hit);
-    if (rc) return rc;
-    if (hit) {      // a value of the grid decode left fp16's range: the volume is decoded again on the f32 pipe (or the call fails)
-        if (!range_should_fall_back(m->dec)) return range_error();
-        F32Override f32(m->dec);
-        m->dec->n_range_fallbacks++;
-        rc = mesh_decode(m, code, &hit);
-        if (rc) return rc;
-    }
-    return mesh_march(m, n_verts, n_faces);
+    return mesh_single(m, code, true, n_verts, n_faces);
 }
 
 extern "C" int qsp_mesh_from_volume(qsp_mesh_extractor* m, const float* sdf_volume, int64_t* n_verts, int64_t* n_faces) {
     std::unique_lock<std::recursive_mutex> lk_d;
     if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
     if (!m || !sdf_volume) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_from_volume: null argument");
+    return mesh_single(m, sdf_volume, false, n_verts, n_faces);
+}
+
+// argument checks of both batch entry points, then the call; a batch that fails leaves no batch result behind
+static int mesh_batch(qsp_mesh_extractor* m, int32_t n, const float* in, bool decode, int64_t* n_verts, int64_t* n_faces, const char* who) {
+    const std::string w(who);
+    if (!m || !in || !n_verts || !n_faces) return qsp_fail(QSP_ERR_INVALID, (w + ": null argument").c_str());
+    if (n < 0) return qsp_fail(QSP_ERR_INVALID, (w + ": negative number of items").c_str());
+    if (m->method != 0)
+        return qsp_fail(QSP_ERR_UNSUPPORTED, (w + ": batches run Lewiner's marching cubes (method 0) only; method 1, the "
+                                                  "face-consistent table, is extracted one mesh per call").c_str());
+    if (n == 0) return QSP_OK;
+    const int rc = mesh_call(m, m->batch, n, in, decode);
+    if (rc) return rc;
+    std::copy(m->batch.n_verts.begin(), m->batch.n_verts.end(), n_verts);
+    std::copy(m->batch.n_faces.begin(), m->batch.n_faces.end(), n_faces);
+    return QSP_OK;
+}
+
+extern "C" int qsp_mesh_extract_batch(qsp_mesh_extractor* m, int32_t n, const float* codes, int64_t* n_verts, int64_t* n_faces) {
+    std::unique_lock<std::recursive_mutex> lk_d;
+    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    return mesh_batch(m, n, codes, true, n_verts, n_faces, "qsp_mesh_extract_batch");
+}
+
+extern "C" int qsp_mesh_from_volumes(qsp_mesh_extractor* m, int32_t n, const float* sdf_volumes, int64_t* n_verts, int64_t* n_faces) {
+    std::unique_lock<std::recursive_mutex> lk_d;
+    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    return mesh_batch(m, n, sdf_volumes, false, n_verts, n_faces, "qsp_mesh_from_volumes");
+}
+
+// A result to the host, concatenated in item order; any pointer may be null.  verts_f64: the vertices as the reference holds
+// them, float64 = float32 index coordinate x (2 / (n - 1)) + (-1) (skimage multiplies its float32 vertices by the float64
+// spacing, reconstruct/utils.py:131-139 adds the origin); the table method has no index coordinates: its float32 vertices, widened.
+static int mesh_fetch(qsp_mesh_extractor* m, const qsp_mesh_extractor::Result& r, float* verts, double* verts_f64, int32_t* faces,
+                      float* sdf_volumes, const char* who) {
+    if (!r.have) return qsp_fail(QSP_ERR_INVALID, (std::string(who) + ": nothing extracted yet").c_str());
     QSP_HIP(hipSetDevice(m->dec->device));
-    QSP_HIP(hipMemcpyAsync(m->sdf, sdf_volume, sizeof(float) * m->n, hipMemcpyHostToDevice, m->dec->stream));
-    return mesh_march(m, n_verts, n_faces);
+    hipStream_t s = m->dec->stream;
+    const bool lewiner = r.method == 0;
+    std::vector<float> tmp;
+    if (verts && r.tot_verts) QSP_HIP(hipMemcpyAsync(verts, r.verts.p, sizeof(float) * 3 * r.tot_verts, hipMemcpyDeviceToHost, s));
+    if (verts_f64 && r.tot_verts) {
+        tmp.resize((size_t)3 * r.tot_verts);
+        QSP_HIP(hipMemcpyAsync(tmp.data(), lewiner ? r.vidx.p : r.verts.p, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost, s));
+    }
+    if (faces && r.tot_faces) QSP_HIP(hipMemcpyAsync(faces, r.faces.p, sizeof(int32_t) * 3 * r.tot_faces, hipMemcpyDeviceToHost, s));
+    if (sdf_volumes) QSP_HIP(hipMemcpyAsync(sdf_volumes, r.sdf.p, sizeof(float) * r.n_verts.size() * m->n, hipMemcpyDeviceToHost, s));
+    QSP_HIP(hipStreamSynchronize(s));
+    const double spacing = 2.0 / (double)(m->dim - 1);
+    for (size_t i = 0; i < tmp.size(); ++i) verts_f64[i] = lewiner ? (double)tmp[i] * spacing + (-1.0) : (double)tmp[i];
+    return QSP_OK;
 }
 
 extern "C" int qsp_mesh_fetch(qsp_mesh_extractor* m, float* verts, int32_t* faces, float* sdf_volume) {
     if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch: null extractor");
-    if (!m->have_volume) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch: nothing extracted yet");
-    QSP_HIP(hipSetDevice(m->dec->device));
-    hipStream_t s = m->dec->stream;
-    if (verts && m->n_verts) QSP_HIP(hipMemcpyAsync(verts, m->verts, sizeof(float) * 3 * m->n_verts, hipMemcpyDeviceToHost, s));
-    if (faces && m->n_faces) QSP_HIP(hipMemcpyAsync(faces, m->faces, sizeof(int32_t) * 3 * m->n_faces, hipMemcpyDeviceToHost, s));
-    if (sdf_volume) QSP_HIP(hipMemcpyAsync(sdf_volume, m->sdf, sizeof(float) * m->n, hipMemcpyDeviceToHost, s));
-    QSP_HIP(hipStreamSynchronize(s));
-    return QSP_OK;
+    return mesh_fetch(m, m->single, verts, nullptr, faces, sdf_volume, "qsp_mesh_fetch");
+}
+
+extern "C" int qsp_mesh_fetch_f64(qsp_mesh_extractor* m, double* verts) {
+    if (!m || !verts) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_f64: null argument");
+    return mesh_fetch(m, m->single, nullptr, verts, nullptr, nullptr, "qsp_mesh_fetch_f64");
+}
+
+extern "C" int qsp_mesh_fetch_batch(qsp_mesh_extractor* m, float* verts, double* verts_f64, int32_t* faces, float* sdf_volumes) {
+    if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_batch: null extractor");
+    std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
+    return mesh_fetch(m, m->batch, verts, verts_f64, faces, sdf_volumes, "qsp_mesh_fetch_batch");
 }
 
 extern "C" int qsp_mesh_extractor_set_method(qsp_mesh_extractor* m, int32_t method) {
@@ -505,193 +609,12 @@ extern "C" int qsp_mesh_extractor_set_method(qsp_mesh_extractor* m, int32_t meth
     return QSP_OK;
 }
 
-// the vertices as the reference holds them: float64 = float32 index coordinate x (2 / (n - 1)) + (-1) (skimage multiplies its
-// float32 vertices by the float64 spacing, reconstruct/utils.py:131-139 adds the origin)
-extern "C" int qsp_mesh_fetch_f64(qsp_mesh_extractor* m, double* verts) {
-    if (!m || !verts) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_f64: null argument");
-    if (!m->have_volume) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_f64: nothing extracted yet");
-    if (!m->n_verts) return QSP_OK;
-    QSP_HIP(hipSetDevice(m->dec->device));
-    std::vector<float> tmp((size_t)3 * m->n_verts);
-    const bool lewiner = m->marched_method == 0;
-    QSP_HIP(hipMemcpyAsync(tmp.data(), lewiner ? m->vidx : m->verts, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost, m->dec->stream));
-    QSP_HIP(hipStreamSynchronize(m->dec->stream));
-    const double spacing = 2.0 / (double)(m->dim - 1);
-    for (size_t i = 0; i < tmp.size(); ++i) verts[i] = lewiner ? (double)tmp[i] * spacing + (-1.0) : (double)tmp[i];
-    return QSP_OK;
-}
-
-// ---- batches ---------------------------------------------------------------------------------------------------------------
-// device buffer of at least `need` elements; its first `keep` elements survive when it has to move
-template <class T> static int batch_reserve(T** p, int64_t* cap, int64_t need, int64_t keep, hipStream_t s) {
-    if (need <= *cap) return QSP_OK;
-    const int64_t ncap = need + need / 4 + 1024;
-    T* q = nullptr;
-    QSP_HIP(hipMalloc((void**)&q, sizeof(T) * ncap));
-    if (keep && *p) {
-        hipError_t e = hipMemcpyAsync(q, *p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(q);
-            return qsp_fail(QSP_ERR_DEVICE, hipGetErrorString(e));
-        }
-    } else if (*p) {
-        QSP_HIP(hipStreamSynchronize(s));      // (nothing queued may still use the buffer that goes)
-    }
-    if (*p) (void)hipFree(*p);
-    *p = q;
-    *cap = ncap;
-    return QSP_OK;
-}
-
-// buffers for a batch of n_items volumes in passes of at most n_pass
-static int batch_scratch(qsp_mesh_extractor* m, int64_t n_items, int64_t n_pass) {
-    auto& b = m->b;
-    hipStream_t s = m->dec->stream;
-    int rc = batch_reserve(&b.codes, &b.cap_codes, n_items * qsp::CODE_LEN, 0, s);
-    if (!rc) rc = batch_reserve(&b.sdf, &b.cap_sdf, n_items * m->n, 0, s);
-    if (!rc) rc = batch_reserve(&b.cnt, &b.cap_cnt, n_pass * m->n_pad, 0, s);
-    if (!rc) rc = batch_reserve(&b.bsum, &b.cap_bsum, n_pass * m->nb, 0, s);
-    if (!rc) rc = batch_reserve(&b.vtot, &b.cap_vtot, n_pass, 0, s);
-    if (!rc) rc = batch_reserve(&b.voff, &b.cap_voff, n_pass + 1, 0, s);
-    if (!rc) rc = batch_reserve(&b.vmap, &b.cap_vmap, n_pass * 3 * m->n, 0, s);
-    return rc;
-}
-
-// marching cubes on items [i0, i0 + V) of the batch, whose volumes are in b.sdf; with `decode`, the grid decode of their codes
-// first, in the same stream order.  One synchronisation: the read of the pass's totals (and of the fp16 range flag with them).
-static int batch_pass(qsp_mesh_extractor* m, int64_t i0, int V, bool decode, bool* hit) {
-    using namespace qsp;
-    auto& b = m->b;
-    hipStream_t s = m->dec->stream;
-    float* sdf = b.sdf + i0 * m->n;
-    const lew::BatchPass bp = {m->dim, m->nb, mc::SCAN_BLOCK, m->n, m->n_pad, m->voxel_size};
-    if (decode) launch_grid_decode(m->dec, b.codes + i0 * CODE_LEN, m->xyz, m->n, V, sdf);
-    hipLaunchKernelGGL(lew::k_lew_count_batch, dim3((int)(m->n_pad / 256), V), dim3(256), 0, s, sdf, bp, b.cnt);
-    hipLaunchKernelGGL(mc::k_mc_scan_blocks, dim3(m->nb * V), dim3(256), 0, s, b.cnt, b.bsum);
-    hipLaunchKernelGGL(mc::k_mc_scan_top_batch, dim3(V), dim3(1024), 0, s, b.bsum, m->nb, b.vtot, b.voff);
-    hipLaunchKernelGGL(mc::k_mc_scan_top, dim3(1), dim3(1024), 0, s, b.voff, V, b.voff + V);
-    QSP_HIP(hipGetLastError());
-    std::vector<unsigned long long> tot(V);
-    QSP_HIP(hipMemcpyAsync(tot.data(), b.vtot, sizeof(unsigned long long) * V, hipMemcpyDeviceToHost, s));
-    QSP_HIP(hipStreamSynchronize(s));
-    *hit = decode && range_hit(m->dec);
-    if (*hit) return QSP_OK;        // (the caller decodes the pass again on the f32 pipe, or fails)
-    int64_t nv = 0, nf = 0;
-    for (int v = 0; v < V; ++v) {
-        b.n_verts[i0 + v] = (int64_t)(tot[v] & 0xffffffffull);
-        b.n_faces[i0 + v] = (int64_t)(tot[v] >> 32);
-        nv += b.n_verts[i0 + v];
-        nf += b.n_faces[i0 + v];
-    }
-    if (nv) {       // (a pass without any surface launches nothing more)
-        int rc = batch_reserve(&b.verts, &b.cap_verts, 3 * (b.tot_verts + nv), 3 * b.tot_verts, s);
-        if (!rc) rc = batch_reserve(&b.vidx, &b.cap_vidx, 3 * (b.tot_verts + nv), 3 * b.tot_verts, s);
-        if (!rc) rc = batch_reserve(&b.faces, &b.cap_faces, 3 * (b.tot_faces + nf), 3 * b.tot_faces, s);
-        if (rc) return rc;
-        const dim3 g((int)((m->n + 255) / 256), V);
-        hipLaunchKernelGGL(lew::k_lew_verts_batch, g, dim3(256), 0, s, sdf, bp, b.cnt, b.bsum, b.voff, b.tot_verts, b.vidx, b.verts, b.vmap);
-        hipLaunchKernelGGL(lew::k_lew_faces_batch, g, dim3(256), 0, s, sdf, bp, b.cnt, b.bsum, b.voff, b.tot_faces, b.vmap, b.faces);
-        QSP_HIP(hipGetLastError());
-    }
-    b.tot_verts += nv;
-    b.tot_faces += nf;
-    return QSP_OK;
-}
-
-// the passes of a batch whose codes (decode) or volumes are already on their way to the device
-static int batch_run(qsp_mesh_extractor* m, int32_t n, bool decode, int64_t* n_verts, int64_t* n_faces) {
-    using namespace qsp;
-    auto& b = m->b;
-    b.n_verts.assign(n, 0);
-    b.n_faces.assign(n, 0);
-    b.tot_verts = b.tot_faces = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += b.limit) {
-        const int V = (int)std::min<int64_t>(b.limit, n - i0);
-        bool hit = false;
-        int rc = batch_pass(m, i0, V, decode, &hit);
-        if (rc) return rc;
-        if (hit) {      // as qsp_mesh_extract: this pass again on the f32 pipe, counted once -- or the call fails
-            if (!range_should_fall_back(m->dec)) return range_error();
-            F32Override f32(m->dec);
-            m->dec->n_range_fallbacks++;
-            rc = batch_pass(m, i0, V, decode, &hit);
-            if (rc) return rc;
-        }
-    }
-    QSP_HIP(hipStreamSynchronize(m->dec->stream));
-    b.have = true;
-    for (int32_t i = 0; i < n; ++i) {
-        n_verts[i] = b.n_verts[i];
-        n_faces[i] = b.n_faces[i];
-    }
-    return QSP_OK;
-}
-
-// argument checks of both batch entry points, then the buffers; a batch that fails leaves no batch result behind
-static int batch_begin(qsp_mesh_extractor* m, int32_t n, const void* in, const int64_t* n_verts, const int64_t* n_faces, const char* who) {
-    const std::string w(who);
-    if (!m || !in || !n_verts || !n_faces) return qsp_fail(QSP_ERR_INVALID, (w + ": null argument").c_str());
-    if (n < 0) return qsp_fail(QSP_ERR_INVALID, (w + ": negative number of items").c_str());
-    if (m->method != 0)
-        return qsp_fail(QSP_ERR_UNSUPPORTED, (w + ": batches run Lewiner's marching cubes (method 0) only; method 1, the "
-                                                  "face-consistent table, is extracted one mesh per call").c_str());
-    if (n == 0) return QSP_OK;
-    QSP_HIP(hipSetDevice(m->dec->device));
-    m->b.have = false;
-    return batch_scratch(m, n, std::min<int64_t>(n, m->b.limit));
-}
-
-extern "C" int qsp_mesh_extract_batch(qsp_mesh_extractor* m, int32_t n, const float* codes, int64_t* n_verts, int64_t* n_faces) {
-    using namespace qsp;
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
-    const int rc = batch_begin(m, n, codes, n_verts, n_faces, "qsp_mesh_extract_batch");
-    if (rc || n == 0) return rc;
-    const int L = m->dec->code_len;
-    std::vector<float> c64((size_t)n * CODE_LEN, 0.f);           // `codes` holds the decoder's code_len entries per item
-    for (int32_t i = 0; i < n; ++i) memcpy(&c64[(size_t)i * CODE_LEN], codes + (size_t)i * L, sizeof(float) * L);
-    QSP_HIP(hipMemcpyAsync(m->b.codes, c64.data(), sizeof(float) * c64.size(), hipMemcpyHostToDevice, m->dec->stream));
-    QSP_HIP(hipStreamSynchronize(m->dec->stream));               // (c64 lives on this frame)
-    return batch_run(m, n, true, n_verts, n_faces);
-}
-
-extern "C" int qsp_mesh_from_volumes(qsp_mesh_extractor* m, int32_t n, const float* sdf_volumes, int64_t* n_verts, int64_t* n_faces) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
-    const int rc = batch_begin(m, n, sdf_volumes, n_verts, n_faces, "qsp_mesh_from_volumes");
-    if (rc || n == 0) return rc;
-    QSP_HIP(hipMemcpyAsync(m->b.sdf, sdf_volumes, sizeof(float) * n * m->n, hipMemcpyHostToDevice, m->dec->stream));
-    return batch_run(m, n, false, n_verts, n_faces);
-}
-
-extern "C" int qsp_mesh_fetch_batch(qsp_mesh_extractor* m, float* verts, double* verts_f64, int32_t* faces, float* sdf_volumes) {
-    if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_batch: null extractor");
-    std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
-    const auto& b = m->b;
-    if (!b.have) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_batch: no batch extracted yet");
-    QSP_HIP(hipSetDevice(m->dec->device));
-    hipStream_t s = m->dec->stream;
-    std::vector<float> tmp;
-    if (verts && b.tot_verts) QSP_HIP(hipMemcpyAsync(verts, b.verts, sizeof(float) * 3 * b.tot_verts, hipMemcpyDeviceToHost, s));
-    if (verts_f64 && b.tot_verts) {
-        tmp.resize((size_t)3 * b.tot_verts);
-        QSP_HIP(hipMemcpyAsync(tmp.data(), b.vidx, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost, s));
-    }
-    if (faces && b.tot_faces) QSP_HIP(hipMemcpyAsync(faces, b.faces, sizeof(int32_t) * 3 * b.tot_faces, hipMemcpyDeviceToHost, s));
-    if (sdf_volumes) QSP_HIP(hipMemcpyAsync(sdf_volumes, b.sdf, sizeof(float) * b.n_verts.size() * m->n, hipMemcpyDeviceToHost, s));
-    QSP_HIP(hipStreamSynchronize(s));
-    const double spacing = 2.0 / (double)(m->dim - 1);           // (the values of qsp_mesh_fetch_f64)
-    for (size_t i = 0; i < tmp.size(); ++i) verts_f64[i] = (double)tmp[i] * spacing + (-1.0);
-    return QSP_OK;
-}
-
 extern "C" int qsp_mesh_extractor_set_batch_limit(qsp_mesh_extractor* m, int32_t max_volumes_per_pass) {
     if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extractor_set_batch_limit: null extractor");
     if (max_volumes_per_pass < 1 || max_volumes_per_pass > QSP_MESH_BATCH_LIMIT_DEFAULT)
         return qsp_fail(QSP_ERR_INVALID, "mesh batch limit: 1 .. 64 (QSP_MESH_BATCH_LIMIT_DEFAULT) volumes per pass");
     std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
-    m->b.limit = max_volumes_per_pass;
+    m->limit = max_volumes_per_pass;
     return QSP_OK;
 }
 

@@ -198,10 +198,10 @@ __device__ inline bool owns_edge(const Cell& c, int e) {
     return ox == c.x && oy == c.y && oz == c.z;
 }
 
-// The three passes are written per grid point p of ONE volume (count_at / verts_at / faces_at); the kernels below hand them a
-// volume: the single-volume ones their arguments as they are, the batched ones (k_lew_*_batch, blockIdx.y = volume of the pass)
-// that volume's slices of the pass's buffers.  Everything a point reads or writes is addressed from those per-volume pointers, so
-// a cell on a volume's upper faces, owns_edge's clamp and the (edge -> vertex) map cannot reach a neighbouring volume.
+// The three passes are written per grid point p of ONE volume (count_at / verts_at / faces_at); the kernels at the end of this
+// file hand them volume blockIdx.y's slices of a pass's buffers.  Everything a point reads or writes is addressed from those
+// per-volume pointers, so a cell on a volume's upper faces, owns_edge's clamp and the (edge -> vertex) map cannot reach a
+// neighbouring volume.
 //
 // pass 1: per grid point, low 32 bits = vertices its cell creates, high 32 bits = its triangles
 __device__ inline void count_at(const float* __restrict__ sdf, int d, unsigned long long* __restrict__ cnt, int64_t n_pad, int64_t p) {
@@ -221,9 +221,6 @@ __device__ inline void count_at(const float* __restrict__ sdf, int d, unsigned l
         out = (unsigned long long)created | ((unsigned long long)nt << 32);
     }
     cnt[p] = out;
-}
-__global__ __launch_bounds__(256) void k_lew_count(const float* __restrict__ sdf, int d, unsigned long long* __restrict__ cnt, int64_t n_pad) {
-    count_at(sdf, d, cnt, n_pad, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // pass 2: the vertices a cell creates, numbered in the order its triangles first use them, and the edge -> vertex map
@@ -276,12 +273,6 @@ __device__ inline void verts_at(const float* __restrict__ sdf, int d, float voxe
         ++id;
     }
 }
-__global__ __launch_bounds__(256) void k_lew_verts(const float* __restrict__ sdf, int d, float voxel_size,
-                                                   const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ bsum,
-                                                   int scan_block, float* __restrict__ vidx, float* __restrict__ verts,
-                                                   int32_t* __restrict__ vmap) {
-    verts_at(sdf, d, voxel_size, cnt, bsum, scan_block, vidx, verts, vmap, (int64_t)blockIdx.x * 256 + threadIdx.x);
-}
 
 // pass 3: faces (corners reversed: gradient_direction = 'descent')
 __device__ inline void faces_at(const float* __restrict__ sdf, int d, const unsigned long long* __restrict__ cnt,
@@ -318,39 +309,34 @@ __device__ inline void faces_at(const float* __restrict__ sdf, int d, const unsi
         faces[3 * (f0 + t) + (2 - k)] = id;
     }
 }
-__global__ __launch_bounds__(256) void k_lew_faces(const float* __restrict__ sdf, int d, const unsigned long long* __restrict__ cnt,
-                                                   const unsigned long long* __restrict__ bsum, int scan_block,
-                                                   const int32_t* __restrict__ vmap, int32_t* __restrict__ faces) {
-    faces_at(sdf, d, cnt, bsum, scan_block, vmap, faces, (int64_t)blockIdx.x * 256 + threadIdx.x);
-}
 
-// ---- the same three passes over the V volumes of a batch pass: one launch each, grid (points / 256, V) ------------------------
+// ---- the three passes over the V volumes of a pass (a single call: V = 1): one launch each, grid (points / 256, V) ---------------
 // Buffers of a pass, volume v of it: sdf + v n | cnt + v n_pad (n_pad = nb scan blocks: every volume starts a scan block, so the
 // scan restarts at every volume and a volume's vertex and face numbers start at 0) | bsum + v nb | vmap + v 3n.  voff[v] = the
 // exclusive scan of the volumes' totals (vertices low, faces high 32 bits, as everywhere here): with the totals of the passes
-// before (v_base, f_base) the place of the volume's vertices and faces in the batch's concatenated arrays.
+// before (v_base, f_base) the place of the volume's vertices and faces in the call's concatenated arrays.
 struct BatchPass {
     int d, nb, scan_block;
     int64_t n, n_pad;
     float voxel_size;
 };
-__global__ __launch_bounds__(256) void k_lew_count_batch(const float* __restrict__ sdf, BatchPass b, unsigned long long* __restrict__ cnt) {
+__global__ __launch_bounds__(256) void k_lew_count(const float* __restrict__ sdf, BatchPass b, unsigned long long* __restrict__ cnt) {
     const int v = blockIdx.y;
     count_at(sdf + v * b.n, b.d, cnt + v * b.n_pad, b.n_pad, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
-__global__ __launch_bounds__(256) void k_lew_verts_batch(const float* __restrict__ sdf, BatchPass b, const unsigned long long* __restrict__ cnt,
-                                                         const unsigned long long* __restrict__ bsum,
-                                                         const unsigned long long* __restrict__ voff, int64_t v_base,
-                                                         float* __restrict__ vidx, float* __restrict__ verts, int32_t* __restrict__ vmap) {
+__global__ __launch_bounds__(256) void k_lew_verts(const float* __restrict__ sdf, BatchPass b, const unsigned long long* __restrict__ cnt,
+                                                   const unsigned long long* __restrict__ bsum,
+                                                   const unsigned long long* __restrict__ voff, int64_t v_base,
+                                                   float* __restrict__ vidx, float* __restrict__ verts, int32_t* __restrict__ vmap) {
     const int v = blockIdx.y;
     const size_t v0 = 3 * (size_t)(v_base + (int64_t)(voff[v] & 0xffffffffull));
     verts_at(sdf + v * b.n, b.d, b.voxel_size, cnt + v * b.n_pad, bsum + (size_t)v * b.nb, b.scan_block, vidx + v0, verts + v0,
              vmap + v * 3 * b.n, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
-__global__ __launch_bounds__(256) void k_lew_faces_batch(const float* __restrict__ sdf, BatchPass b, const unsigned long long* __restrict__ cnt,
-                                                         const unsigned long long* __restrict__ bsum,
-                                                         const unsigned long long* __restrict__ voff, int64_t f_base,
-                                                         const int32_t* __restrict__ vmap, int32_t* __restrict__ faces) {
+__global__ __launch_bounds__(256) void k_lew_faces(const float* __restrict__ sdf, BatchPass b, const unsigned long long* __restrict__ cnt,
+                                                   const unsigned long long* __restrict__ bsum,
+                                                   const unsigned long long* __restrict__ voff, int64_t f_base,
+                                                   const int32_t* __restrict__ vmap, int32_t* __restrict__ faces) {
     const int v = blockIdx.y;
     faces_at(sdf + v * b.n, b.d, cnt + v * b.n_pad, bsum + (size_t)v * b.nb, b.scan_block, vmap + v * 3 * b.n,
              faces + 3 * (size_t)(f_base + (int64_t)(voff[v] >> 32)), (int64_t)blockIdx.x * 256 + threadIdx.x);

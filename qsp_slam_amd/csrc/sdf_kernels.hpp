@@ -1636,6 +1636,16 @@ __global__ void k_inlier_filter(const HypState* __restrict__ st, const ObjView* 
 // ---------------------------------------------------------------------------------------------------------------
 // generic decode kernels for the API-level entry points (loss_utils.py:51-103): points already in the object frame
 // ---------------------------------------------------------------------------------------------------------------
+// what the decode kernels below share: thread threadIdx.x < TILE_P stages point v of the grid (past n: zeros) as its tile row
+__device__ inline void stage_point(MlpSmem& s, const float* __restrict__ xyz, int64_t n, int64_t v) {
+    float x = 0, y = 0, z = 0;
+    if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
+    s.xin[4 * threadIdx.x + 0] = x;
+    s.xin[4 * threadIdx.x + 1] = y;
+    s.xin[4 * threadIdx.x + 2] = z;
+    s.xin[4 * threadIdx.x + 3] = 0.f;
+}
+
 template <bool GRAD, bool BF3 = false>
 __global__ __launch_bounds__(MLP_THREADS, 2) void k_decode(const float* __restrict__ code, const float* __restrict__ xyz,
                                                            int64_t n, const MlpParams* __restrict__ P, float* __restrict__ y_out,
@@ -1646,15 +1656,7 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void k_decode(const float* __restri
     mlp_prepare(s, P);
     for (int64_t t = blockIdx.x; t * TILE_P < n; t += gridDim.x) {
         __syncthreads();
-        if (threadIdx.x < TILE_P) {
-            const int64_t v = t * TILE_P + threadIdx.x;
-            float x = 0, y = 0, z = 0;
-            if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
-            s.xin[4 * threadIdx.x + 0] = x;
-            s.xin[4 * threadIdx.x + 1] = y;
-            s.xin[4 * threadIdx.x + 2] = z;
-            s.xin[4 * threadIdx.x + 3] = 0.f;
-        }
+        if (threadIdx.x < TILE_P) stage_point(s, xyz, n, t * TILE_P + threadIdx.x);
         __syncthreads();
         if (BF3 && !GRAD) mlp_tile_bf3<QSP_BF3_PF>(s, P);
         else mlp_tile<GRAD, 4, false, BF3>(s, P);
@@ -1691,15 +1693,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_decode_h2(const float* __restric
     float amax = 0.f;
     for (int64_t t = blockIdx.x; t * TILE_P < n; t += gridDim.x) {
         __syncthreads();
-        if (threadIdx.x < TILE_P) {
-            const int64_t v = t * TILE_P + threadIdx.x;
-            float x = 0, y = 0, z = 0;
-            if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
-            s.xin[4 * threadIdx.x + 0] = x;
-            s.xin[4 * threadIdx.x + 1] = y;
-            s.xin[4 * threadIdx.x + 2] = z;
-            s.xin[4 * threadIdx.x + 3] = 0.f;
-        }
+        if (threadIdx.x < TILE_P) stage_point(s, xyz, n, t * TILE_P + threadIdx.x);
         __syncthreads();
         mlp_tile_h2<GRAD, 2, !GRAD && !NARROW, 2, 4, NARROW>(s, P, amax, !staged);
         staged = true;
@@ -1743,15 +1737,7 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void k_grid_decode(const float* __r
             y_out += i == 0 ? vol * n : n;
         }
         __syncthreads();
-        if (threadIdx.x < TILE_P) {
-            const int64_t v = t * TILE_P + threadIdx.x;
-            float x = 0, y = 0, z = 0;
-            if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
-            s.xin[4 * threadIdx.x + 0] = x;
-            s.xin[4 * threadIdx.x + 1] = y;
-            s.xin[4 * threadIdx.x + 2] = z;
-            s.xin[4 * threadIdx.x + 3] = 0.f;
-        }
+        if (threadIdx.x < TILE_P) stage_point(s, xyz, n, t * TILE_P + threadIdx.x);
         __syncthreads();
         if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, P);
         else mlp_tile<false, 4, false, false>(s, P);
@@ -1792,15 +1778,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_grid_decode_h2(const float* __re
             y_out += i == 0 ? vol * n : n;
         }
         __syncthreads();
-        if (threadIdx.x < TILE_P) {
-            const int64_t v = t * TILE_P + threadIdx.x;
-            float x = 0, y = 0, z = 0;
-            if (v < n) { x = xyz[3 * v]; y = xyz[3 * v + 1]; z = xyz[3 * v + 2]; }
-            s.xin[4 * threadIdx.x + 0] = x;
-            s.xin[4 * threadIdx.x + 1] = y;
-            s.xin[4 * threadIdx.x + 2] = z;
-            s.xin[4 * threadIdx.x + 3] = 0.f;
-        }
+        if (threadIdx.x < TILE_P) stage_point(s, xyz, n, t * TILE_P + threadIdx.x);
         __syncthreads();
         mlp_tile_h2<false, 2, !NARROW, 2, 4, NARROW>(s, P, amax, !staged);
         staged = true;

@@ -634,14 +634,14 @@ static auto jtj_h2_form(bool narrow, int tile_p, int waves, int waves_t32, bool 
     if (waves == 8) return jtj_h2_kernel<2, 8, false>(grp);
     return jtj_h2_kernel<2, 4, false>(grp);
 }
-// qsp_decode_sdf / qsp_sdf_value_grad / the mesh extractor's volume; bf3 = the precision of the pass (Jacobian with grad, else forward)
+// qsp_decode_sdf / qsp_sdf_value_grad; bf3 = the precision of the pass (Jacobian with grad, else forward)
 static auto decode_form(bool grad, int bf3, bool narrow) {
     if (bf3 == 2 && narrow) return grad ? decode_h2_kernel<true, true>() : decode_h2_kernel<false, true>();
     if (bf3 == 2) return grad ? decode_h2_kernel<true, false>() : decode_h2_kernel<false, false>();
     if (bf3) return grad ? decode_kernel<true, true>() : decode_kernel<false, true>();
     return grad ? decode_kernel<true, false>() : decode_kernel<false, false>();
 }
-// the mesh extractor's batch of volumes: the forward forms of decode_form, over one grid and many codes; bf3 = the forward precision
+// the mesh extractor's volumes, one or many: the forward forms of decode_form, over one grid and n_vol codes; bf3 = the forward precision
 static auto grid_decode_form(int bf3, bool narrow) {
     if (bf3 == 2) return narrow ? grid_decode_h2_kernel<true>() : grid_decode_h2_kernel<false>();
     return bf3 ? grid_decode_kernel<true>() : grid_decode_kernel<false>();

@@ -117,6 +117,44 @@ def test_lewiner_mesh_from_code_is_the_default(gpu_decoder, golden_dir):
     assert len(of) > 100 and mo.signed_volume(ov, of) > 0
 
 
+def _single_call_volume_and_plain_decode(dec, code_len, dim, code):
+    from qsp_slam_amd.reconstruct.optimizer import MeshExtractor
+    me = MeshExtractor(dec, code_len=code_len, voxels_dim=dim)
+    vol = me.extract_mesh_from_code(code, return_volume=True)["sdf_volume"]
+    return vol, np.ascontiguousarray(me.extract_sdf_grid(code), np.float32)
+
+
+@pytest.mark.parametrize("dim", [13, 32])
+@pytest.mark.parametrize("prec", ["f32", "fp16x2", "bf16x3"])
+def test_single_call_volume_equals_the_plain_decode(gpu_decoder, prec, dim):
+    """the volume extract_mesh_from_code decodes (the grid decode, k_grid_decode*) against decode_sdf over the same grid
+    (qsp_decode_sdf: k_decode*, a kernel the extractor does not launch), bit for bit on every pipe.  13^3 = 34 tiles of 64 points
+    + 21: a ragged last tile; 32^3: whole tiles."""
+    code = (0.05 * np.random.default_rng(5).standard_normal(64)).astype(np.float32)
+    gpu_decoder.set_precision(prec)
+    try:
+        vol, plain = _single_call_volume_and_plain_decode(gpu_decoder, 64, dim, code)
+    finally:
+        gpu_decoder.set_precision("f32")
+    assert vol.shape == plain.shape == (dim,) * 3 and vol.dtype == np.float32
+    assert np.array_equal(vol.view(np.uint32), plain.view(np.uint32)), (prec, dim)
+
+
+def test_single_call_volume_equals_the_plain_decode_narrow(golden_dir):
+    """the same on the 4 x 256 / code 32 decoder's split-fp16 pipe (the NARROW tile)"""
+    from qsp_slam_amd import DeepSdfDecoder
+    d = DeepSdfDecoder.from_npz(os.path.join(golden_dir, "decoder_4x256_c32.npz"))
+    try:
+        d.set_precision("fp16x2")
+        code = (0.05 * np.random.default_rng(5).standard_normal(32)).astype(np.float32)
+        vol, plain = _single_call_volume_and_plain_decode(d, 32, 13, code)
+        assert vol.shape == plain.shape == (13,) * 3
+        assert np.array_equal(vol.view(np.uint32), plain.view(np.uint32))
+        assert d.range_fallbacks == 0
+    finally:
+        d.close()
+
+
 @pytest.mark.parametrize("dim,kind", [(16, "sphere"), (32, "sphere"), (64, "sphere"), (12, "noise"), (33, "noise"),
                                       (20, "smooth")])
 def test_marching_cubes_bit_exact(gpu_decoder, dim, kind):

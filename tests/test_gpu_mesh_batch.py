@@ -254,6 +254,83 @@ def test_scratch_is_reused_and_grows(gpu_decoder):
             assert same_mesh(got, *want[i]), (idx, i)
 
 
+def _single_c_abi(me, call, host):
+    """a single call and its float32 fetch through the C ABI (whatever method the handle has selected)"""
+    from qsp_slam_amd import _lib
+    nv, nf = np.zeros(1, np.int64), np.zeros(1, np.int64)
+    _lib.check(call(me.handle, _lib.fptr(host), _lib.i64ptr(nv), _lib.i64ptr(nf)))
+    return _fetch_single_f32(me, int(nv[0]), int(nf[0]))
+
+
+def _fetch_single_f32(me, nv, nf):
+    from qsp_slam_amd import _lib
+    v, f = np.empty((nv, 3), np.float32), np.empty((nf, 3), np.int32)
+    _lib.check(_lib.lib().qsp_mesh_fetch(me.handle, _lib.fptr(v), _lib.i32ptr(f), None))
+    return v, f
+
+
+def test_table_single_call_between_a_batch_and_its_fetch(gpu_decoder):
+    """the scratch is shared, the results are not: a table-method single call (flags, counts and block sums in the scratch the
+    Lewiner batch just used) gives the oracle's mesh, and the batch's meshes are still there afterwards"""
+    from qsp_slam_amd import _lib
+    L = _lib.lib()
+    dim = 13
+    me = extractor(gpu_decoder, dim)
+    out = me.extract_meshes_from_codes(batch_codes()[:3])
+    assert all(o is not None and len(o.faces) > 0 for o in out)
+    vol = noise_volume(dim, dim)
+    ov, of = mo.marching_cubes(vol)
+    _lib.check(L.qsp_mesh_extractor_set_method(me.handle, 1))
+    try:
+        v, f = _single_c_abi(me, L.qsp_mesh_from_volume, _lib.f32c(vol.reshape(-1)))
+    finally:
+        _lib.check(L.qsp_mesh_extractor_set_method(me.handle, 0))
+    assert len(of) > 0 and v.shape == ov.shape and np.array_equal(f, of) and np.array_equal(v.view(np.uint32), ov.view(np.uint32))
+    bv = np.empty((sum(len(o.vertices) for o in out), 3), np.float64)
+    bf = np.empty((sum(len(o.faces) for o in out), 3), np.int32)
+    _lib.check(L.qsp_mesh_fetch_batch(me.handle, None, _lib.dptr(bv), _lib.i32ptr(bf), None))
+    assert same_mesh((bv, bf), np.concatenate([o.vertices for o in out]), np.concatenate([o.faces for o in out]))
+    v2, f2 = _fetch_single_f32(me, len(ov), len(of))
+    assert np.array_equal(f2, of) and np.array_equal(v2.view(np.uint32), ov.view(np.uint32))
+
+
+def test_scratch_grows_between_two_single_calls(gpu_decoder):
+    """single call, a batch of 7 volumes (the scratch grows from one volume to seven), the same single call again"""
+    dim = 13
+    vols = [sphere_volume(dim), noise_volume(dim, 3), smooth_volume(dim), noise_volume(dim, 4), sphere_volume(dim, r=0.7),
+            noise_volume(dim, 5), smooth_volume(dim) + np.float32(0.05)]
+    code = batch_codes()[0]
+    me = extractor(gpu_decoder, dim)
+    a = single(me, code)
+    out = me.meshes_from_volumes(vols)
+    b = single(me, code)
+    assert a is not None and len(a.faces) > 0 and same_as_single(a, b)
+    for i, vol in enumerate(vols):
+        assert same_mesh(out[i], *ml.convert_sdf_voxels_to_mesh(vol)), i
+
+
+def test_a_failed_single_call_leaves_nothing_to_fetch(golden_dir, monkeypatch):
+    from qsp_slam_amd import _lib
+    from tests.test_gpu_split_precision import _scaled_decoder
+    L = _lib.lib()
+    monkeypatch.delenv("QSP_PRECISION", raising=False)
+    d = _scaled_decoder(golden_dir, 1, 6e5, rows=list(range(64)))    # activations of layer 1 beyond fp16's range
+    try:
+        me = extractor(d, 13)
+        d.set_precision("fp16x2")
+        code = _lib.f32c(np.zeros(64, np.float32))
+        nv, nf = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        assert L.qsp_mesh_extract(me.handle, _lib.fptr(code), _lib.i64ptr(nv), _lib.i64ptr(nf)) == _lib.QSP_OK      # (falls back)
+        assert L.qsp_mesh_fetch(me.handle, None, None, None) == _lib.QSP_OK
+        d.set_range_fallback(False)
+        assert L.qsp_mesh_extract(me.handle, _lib.fptr(code), _lib.i64ptr(nv), _lib.i64ptr(nf)) == _lib.QSP_ERR_UNSUPPORTED
+        assert L.qsp_mesh_fetch(me.handle, None, None, None) == _lib.QSP_ERR_INVALID
+        d.set_range_fallback(True)
+        del me
+    finally:
+        d.close()
+
+
 def test_table_method_is_not_batched(gpu_decoder):
     from qsp_slam_amd import _lib
     me = extractor(gpu_decoder, 9, method="table")

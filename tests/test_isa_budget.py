@@ -33,6 +33,11 @@ BUDGET = {
     "qsp::k_decode<true, false>": (0, 0, 0),
     "qsp::k_decode<false, true>": (36, 136, 0),
     "qsp::k_decode<true, true>": (40, 160, 0),
+    # the grid decode (the mesh extractor's volumes): the forward tile of k_decode / k_decode_h2, each entry its forward form's
+    "qsp::k_grid_decode<false>": (0, 0, 0),
+    "qsp::k_grid_decode<true>": (36, 136, 0),
+    "qsp::k_grid_decode_h2<false>": (24, 96, 0),
+    "qsp::k_grid_decode_h2<true>": (64, 160, 0),
     # The decoder-group forms (last template argument GRP = true; the single-decoder forms above end in false).  The per-item
     # parameter lookup is a few scalar registers more across the tile: an entry is at most the single-decoder form's plus
     # (8, 32, 4), tests/test_decoder_group_host.py's SLACK, and lower wherever the kernel compiles to less.
@@ -75,6 +80,6 @@ def test_decoder_kernels_stay_inside_their_spill_budget(sdf_isa):
     over = {k: (meta[k]["vspill"], meta[k]["scratch"], meta[k]["sspill"]) for k, b in BUDGET.items()
             if meta[k]["vspill"] > b[0] or meta[k]["scratch"] > b[1] or meta[k]["sspill"] > b[2]}
     assert not over, "over budget (spilled VGPRs, scratch bytes per lane, spilled SGPRs): %r" % over
-    # every k_mlp_* / k_decode* kernel of the file has a budget: a new tile kernel must be entered here
-    unbudgeted = [k for k in meta if re.match(r"qsp::k_(mlp|decode)", k) and k not in BUDGET]
+    # every k_mlp_* / k_decode* / k_grid_decode* kernel of the file has a budget: a new tile kernel must be entered here
+    unbudgeted = [k for k in meta if re.match(r"qsp::k_(mlp|decode|grid_decode)", k) and k not in BUDGET]
     assert not unbudgeted, unbudgeted

@@ -1,6 +1,6 @@
 """Mesh extraction alone (MeshExtractor.extract_mesh_from_code on the fitted decoder): ms per call at 32^3 / 64^3 / 128^3 for
 Lewiner's marching cubes (the default) and the table method of rounds 2-3.  Under rocprofv3 --kernel-trace --stats the kernel
-table shows k_decode*, k_lew_count / k_lew_verts / k_lew_faces and the two scan kernels.   python tools/mesh_only.py [precision]"""
+table shows k_grid_decode*, k_lew_count / k_lew_verts / k_lew_faces (table method: k_mc_flags / k_mc_emit) and the three scan kernels.   python tools/mesh_only.py [precision]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
