@@ -296,7 +296,21 @@ int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_se3, const 
  *   successful qsp_mesh_extract / qsp_mesh_from_volume, qsp_mesh_fetch_batch the result of the last successful batch call, in
  *   whatever order single and batch calls were mixed.  A call that fails leaves no result of its kind: after a failed single
  *   call qsp_mesh_fetch / _fetch_f64 return QSP_ERR_INVALID until the next successful one (as qsp_mesh_fetch_batch does after a
- *   failed batch call) -- the volume the failed call overwrote cannot be fetched under the counts of the call before. */
+ *   failed batch call) -- the volume the failed call overwrote cannot be fetched under the counts of the call before.
+ *   Over a decoder group: after a refinement over a decoder group (below) the codes of one key frame belong to several classes,
+ *   and the reference meshes each with the extractor of its class (src/LocalMapping_util.cc:818-835).  An extractor created
+ *   with qsp_mesh_extractor_create_group (declared with the decoder groups) shares one grid between the members;
+ *   qsp_mesh_extract_batch_group takes n codes and n class indices (position in the group) and gives n meshes from the same
+ *   passes: one grid-decode launch in which every volume is decoded with the parameters of its class, then the stages above.
+ *   Each item is bit for bit the mesh and the volume qsp_mesh_extract gives for that code on an extractor of that class's
+ *   decoder, on every precision.  The exception above widens with the group: a pass is repeated whole on the f32 pipe when the
+ *   range flag of ANY member is up after it (every member's tiles raise that member's flag), so items of every class in that
+ *   pass carry f32 bits.  The repeat is counted the way a group refinement call counts its own: once per repeated pass, in
+ *   QSP_DEC_CNT_RANGE_FALLBACKS of member 0, whichever member left the range; with QSP_DEC_OPT_RANGE_FALLBACK = 0 the call fails
+ *   with QSP_ERR_UNSUPPORTED and leaves no batch result.  qsp_mesh_fetch_batch, qsp_mesh_from_volume(s), qsp_mesh_fetch(_f64),
+ *   set_batch_limit, set_method and destroy work on such an extractor as on any other; the calls that take codes without classes
+ *   (qsp_mesh_extract, qsp_mesh_extract_batch) return QSP_ERR_INVALID on it, as qsp_mesh_extract_batch_group does on an
+ *   extractor over one decoder. */
 typedef struct qsp_mesh_extractor qsp_mesh_extractor;
 int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, const float* voxel_points, qsp_mesh_extractor** out);
 void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m);
@@ -613,6 +627,16 @@ int qsp_estimate_pose_group(qsp_decoder_group* g, int32_t n, const float* t_co_s
 /* qsp_refine_detections over a group: det_class[d] = member of detection d */
 int qsp_refine_detections_group(qsp_decoder_group* g, const qsp_joint_cfg* cfg, const qsp_detections* det,
                                 const int32_t* det_class, qsp_detection_results* out);
+/* Mesh extraction over a group (see "Mesh extraction", Batches): the meshes of the codes of all classes in one call.
+ *   The group's options are checked (and its parameter copy refreshed) at every qsp_mesh_extract_batch_group, which holds the
+ *   locks of all members; a class index outside [0, members) is QSP_ERR_INVALID, null pointers and n < 0 too; n == 0 is QSP_OK
+ *   and touches nothing; method 1 is QSP_ERR_UNSUPPORTED as for qsp_mesh_extract_batch.
+ *   Lifetime: destroy the extractor before the group, and the group before its decoders. */
+/* an extractor over a decoder group: the grid is shared, every code names its class (position in the group) */
+int qsp_mesh_extractor_create_group(qsp_decoder_group* g, int32_t voxels_dim, const float* voxel_points, qsp_mesh_extractor** out);
+/* n codes (n x code_len) + n class indices -> n meshes; everything else as qsp_mesh_extract_batch */
+int qsp_mesh_extract_batch_group(qsp_mesh_extractor* m, int32_t n, const float* codes, const int32_t* cls,
+                                 int64_t* n_verts, int64_t* n_faces);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Single-ellipsoid fits, batched: EllipsoidExtractor::OptimizeEllipsoidUsingPlanes,

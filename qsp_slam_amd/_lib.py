@@ -103,6 +103,7 @@ SYMBOLS = [
     "qsp_estimate_pose_group", "qsp_refine_detections_group",
     "qsp_mesh_extractor_create", "qsp_mesh_extractor_destroy", "qsp_mesh_extract", "qsp_mesh_from_volume", "qsp_mesh_fetch", "qsp_mesh_fetch_f64", "qsp_mesh_extractor_set_method",
     "qsp_mesh_extract_batch", "qsp_mesh_from_volumes", "qsp_mesh_fetch_batch", "qsp_mesh_extractor_set_batch_limit",
+    "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
@@ -175,6 +176,8 @@ def lib():
     L.qsp_mesh_from_volumes.argtypes = [vp, C.c_int32, c_float_p, c_int64_p, c_int64_p]
     L.qsp_mesh_fetch_batch.argtypes = [vp, c_float_p, C.POINTER(C.c_double), c_int32_p, c_float_p]
     L.qsp_mesh_extractor_set_batch_limit.argtypes = [vp, C.c_int32]
+    L.qsp_mesh_extractor_create_group.argtypes = [vp, C.c_int32, c_float_p, C.POINTER(vp)]
+    L.qsp_mesh_extract_batch_group.argtypes = [vp, C.c_int32, c_float_p, c_int32_p, c_int64_p, c_int64_p]
     L.qsp_mc_tables.argtypes = [C.POINTER(C.c_int8), C.POINTER(C.c_int8)]
     L.qsp_pose_optimizer_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
     L.qsp_pose_optimizer_destroy.argtypes = [vp]

@@ -33,6 +33,13 @@
 // and `batch`: qsp_mesh_fetch / _fetch_f64 always give the last SINGLE call's mesh, qsp_mesh_fetch_batch the last batch call's,
 // whatever was called in between.  All of it grows to the high-water mark (mesh_reserve) and is freed with the extractor.  A
 // result does not depend on the pass size.  A call that fails leaves no result of its kind to fetch.
+//
+// An extractor over a decoder GROUP (qsp_mesh_extractor_create_group) is the same extractor with one different launch: its codes
+// come with a class index each (qsp_mesh_extract_batch_group) and the pass decodes them with k_group_grid_decode*, volume v on
+// the parameters of member cls[v]; passes, scratch, results and the marching-cubes stages are those above.  The group's first
+// member lends stream and settings (the members agree on them: group_check), the call holds every member's lock.  A pass is
+// repeated on the f32 pipe when the range flag of ANY member is up after it, and counted as a group refinement call counts its
+// own repeat: once per repeated pass, on the group's first member.
 #pragma once
 
 namespace qsp {
@@ -319,7 +326,8 @@ template <class T> struct MeshBuf {
 };
 
 struct qsp_mesh_extractor {
-    qsp_decoder* dec = nullptr;
+    qsp_decoder* dec = nullptr;     // over a group: its first member (stream, device, settings -- the same for every member)
+    qsp_decoder_group* grp = nullptr;   // set: codes come with a class index each and are decoded by their member of grp->Pd
     int device = 0;         // of the decoder, cached: destroy must not touch a decoder that may already be gone
     int method = 0;         // 0: Lewiner's marching cubes, what the reference calls (mesh_lewiner.hpp); 1: the face-consistent table of rounds 2-3
     int limit = QSP_MESH_BATCH_LIMIT_DEFAULT;
@@ -332,6 +340,7 @@ struct qsp_mesh_extractor {
     // scratch of a pass of V volumes, shared by all calls: nothing in it is read after the call that filled it
     struct Scratch {
         MeshBuf<float> codes;                           // (items, CODE_LEN): the whole call's
+        MeshBuf<int32_t> cls;                           // (items): their class indices (an extractor over a decoder group)
         MeshBuf<unsigned long long> cnt, bsum, vtot, voff;      // (V, n_pad), (V, nb), (V), (V + 1: the grand total last)
         MeshBuf<int32_t> vmap;                          // Lewiner: (V, 3, n), (axis, grid point) -> vertex number
         MeshBuf<uint8_t> flags;                         // method 1: (n_pad)
@@ -351,7 +360,7 @@ struct qsp_mesh_extractor {
 extern "C" void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    void* ptrs[] = {m->xyz, m->tables, m->s.codes.p, m->s.cnt.p, m->s.bsum.p, m->s.vtot.p, m->s.voff.p, m->s.vmap.p, m->s.flags.p,
+    void* ptrs[] = {m->xyz, m->tables, m->s.codes.p, m->s.cls.p, m->s.cnt.p, m->s.bsum.p, m->s.vtot.p, m->s.voff.p, m->s.vmap.p, m->s.flags.p,
                     m->single.sdf.p, m->single.verts.p, m->single.vidx.p, m->single.faces.p,
                     m->batch.sdf.p, m->batch.verts.p, m->batch.vidx.p, m->batch.faces.p};
     for (void* p : ptrs)
@@ -360,17 +369,18 @@ extern "C" void qsp_mesh_extractor_destroy(qsp_mesh_extractor* m) {
     (void)hipGetLastError();   // errors are ignored here; do not leave one behind for the next call's launch check
 }
 
-extern "C" int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, const float* voxel_points,
-                                         qsp_mesh_extractor** out) {
+// an extractor over `dec`, or over the group `grp` whose first member `dec` is
+static int mesh_extractor_new(qsp_decoder* dec, qsp_decoder_group* grp, int32_t voxels_dim, const float* voxel_points,
+                              qsp_mesh_extractor** out) {
     using namespace qsp;
-    if (!dec || !out || !voxel_points) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extractor_create: null argument");
-    if (voxels_dim < 2 || voxels_dim > 128) return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_mesh_extractor_create: 2 <= voxels_dim <= 128");
+    if (voxels_dim < 2 || voxels_dim > 128) return qsp_fail(QSP_ERR_UNSUPPORTED, "mesh extractor: 2 <= voxels_dim <= 128");
     static mc::Tables host_tables;
     static const bool tables_ok = mc::build_tables(host_tables);
     if (!tables_ok) return qsp_fail(QSP_ERR_DEVICE, "marching-cubes table generation failed");
     QSP_HIP(hipSetDevice(dec->device));
     qsp_mesh_extractor* m = new qsp_mesh_extractor();
     m->dec = dec;
+    m->grp = grp;
     m->device = dec->device;
     m->dim = voxels_dim;
     m->n = (int64_t)voxels_dim * voxels_dim * voxels_dim;
@@ -388,6 +398,36 @@ extern "C" int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, c
     }
     *out = m;
     return QSP_OK;
+}
+
+extern "C" int qsp_mesh_extractor_create(qsp_decoder* dec, int32_t voxels_dim, const float* voxel_points,
+                                         qsp_mesh_extractor** out) {
+    if (!dec || !out || !voxel_points) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extractor_create: null argument");
+    return mesh_extractor_new(dec, nullptr, voxels_dim, voxel_points, out);
+}
+
+extern "C" int qsp_mesh_extractor_create_group(qsp_decoder_group* g, int32_t voxels_dim, const float* voxel_points,
+                                               qsp_mesh_extractor** out) {
+    if (!g || !out || !voxel_points) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extractor_create_group: null argument");
+    const CallLock lk(g);
+    const int rc = group_check(g);
+    if (rc) return rc;
+    return mesh_extractor_new(g->m[0], g, voxels_dim, voxel_points, out);
+}
+
+// The locks of a call on an extractor: its decoder's, or over a group every member's in the group's order (a null extractor: none).
+static CallLock mesh_lock(qsp_mesh_extractor* m) {
+    if (m && m->grp) return CallLock(m->grp);
+    return CallLock(m ? m->dec : (qsp_decoder*)nullptr);
+}
+
+// after a synchronisation of the extractor's stream: did the grid decode leave fp16's range?  Over a group every member's flag
+// is read (and cleared): each is raised by the tiles that ran on that member.
+static bool mesh_range_hit(qsp_mesh_extractor* m) {
+    if (!m->grp) return range_hit(m->dec);
+    bool hit = false;
+    for (qsp_decoder* d : m->grp->lock_order) hit = range_hit(d) || hit;
+    return hit;
 }
 
 // device buffer of at least `need` elements; its first `keep` elements survive when it has to move
@@ -423,7 +463,8 @@ static int mesh_pass(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int64
     float* sdf = r.sdf.p + i0 * m->n;
     const bool lewiner = m->method == 0;
     const lew::BatchPass bp = {m->dim, m->nb, mc::SCAN_BLOCK, m->n, m->n_pad, m->voxel_size};
-    if (decode) launch_grid_decode(m->dec, sc.codes.p + i0 * CODE_LEN, m->xyz, m->n, V, sdf);
+    if (decode && m->grp) launch_grid_decode_group(m->grp, sc.codes.p + i0 * CODE_LEN, sc.cls.p + i0, m->xyz, m->n, V, sdf);
+    else if (decode) launch_grid_decode(m->dec, sc.codes.p + i0 * CODE_LEN, m->xyz, m->n, V, sdf);
     const dim3 gc((int)(m->n_pad / 256), V);
     if (lewiner) hipLaunchKernelGGL(lew::k_lew_count, gc, dim3(256), 0, s, sdf, bp, sc.cnt.p);
     else hipLaunchKernelGGL(mc::k_mc_flags, gc, dim3(256), 0, s, sdf, m->dim, m->tables, sc.flags.p, sc.cnt.p, m->n_pad);
@@ -434,7 +475,7 @@ static int mesh_pass(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int64
     std::vector<unsigned long long> tot(V);
     QSP_HIP(hipMemcpyAsync(tot.data(), sc.vtot.p, sizeof(unsigned long long) * V, hipMemcpyDeviceToHost, s));
     QSP_HIP(hipStreamSynchronize(s));
-    *hit = decode && range_hit(m->dec);
+    *hit = decode && mesh_range_hit(m);
     if (*hit) return QSP_OK;        // (the caller decodes the pass again on the f32 pipe, or fails)
     int64_t nv = 0, nf = 0;
     for (int v = 0; v < V; ++v) {
@@ -463,9 +504,11 @@ static int mesh_pass(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int64
     return QSP_OK;
 }
 
-// A call: n codes (decode; the decoder's code_len entries each) or n volumes from the host -> r.  r holds no result until the
-// call has succeeded.  Buffers for n volumes in passes of at most `limit`, the input's upload, then the passes.
-static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32_t n, const float* in, bool decode) {
+// A call: n codes (decode; the decoder's code_len entries each; over a group with their n class indices cls, checked by the
+// caller) or n volumes from the host -> r.  r holds no result until the call has succeeded.  Buffers for n volumes in passes of
+// at most `limit`, the input's upload, then the passes.
+static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32_t n, const float* in, bool decode,
+                     const int32_t* cls = nullptr) {
     using namespace qsp;
     QSP_HIP(hipSetDevice(m->dec->device));
     r.have = false;
@@ -474,6 +517,7 @@ static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32
     const bool lewiner = m->method == 0;
     const int64_t n_pass = std::min<int64_t>(n, m->limit);
     int rc = mesh_reserve(sc.codes, (int64_t)n * CODE_LEN, 0, s);
+    if (!rc && cls) rc = mesh_reserve(sc.cls, n, 0, s);
     if (!rc) rc = mesh_reserve(r.sdf, n * m->n, 0, s);
     if (!rc) rc = mesh_reserve(sc.cnt, n_pass * m->n_pad, 0, s);
     if (!rc) rc = mesh_reserve(sc.bsum, n_pass * m->nb, 0, s);
@@ -487,6 +531,7 @@ static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32
         std::vector<float> c64((size_t)n * CODE_LEN, 0.f);           // padded to CODE_LEN
         for (int32_t i = 0; i < n; ++i) memcpy(&c64[(size_t)i * CODE_LEN], in + (size_t)i * L, sizeof(float) * L);
         QSP_HIP(hipMemcpyAsync(sc.codes.p, c64.data(), sizeof(float) * c64.size(), hipMemcpyHostToDevice, s));
+        if (cls) QSP_HIP(hipMemcpyAsync(sc.cls.p, cls, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
         QSP_HIP(hipStreamSynchronize(s));                            // (c64 lives on this frame)
     } else {
         QSP_HIP(hipMemcpyAsync(r.sdf.p, in, sizeof(float) * n * m->n, hipMemcpyHostToDevice, s));
@@ -500,7 +545,8 @@ static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32
         bool hit = false;
         rc = mesh_pass(m, r, i0, V, decode, &hit);
         if (rc) return rc;
-        if (hit) {      // a value of the grid decode left fp16's range: this pass again on the f32 pipe, counted once -- or the call fails
+        if (hit) {      // a value of the grid decode left fp16's range: this pass again on the f32 pipe, counted once (over a group: on
+                        // its first member, m->dec, whichever member's flag was up) -- or the call fails
             if (!range_should_fall_back(m->dec)) return range_error();
             F32Override f32(m->dec);
             m->dec->n_range_fallbacks++;
@@ -513,6 +559,12 @@ static int mesh_call(qsp_mesh_extractor* m, qsp_mesh_extractor::Result& r, int32
     return QSP_OK;
 }
 
+// the code-taking single-decoder calls on an extractor over a group: a code there needs its class
+static int group_extractor_refusal(const char* who) {
+    return qsp_fail(QSP_ERR_INVALID, (std::string(who) + ": this extractor is over a decoder group, where every code names its class: "
+                                                         "call qsp_mesh_extract_batch_group").c_str());
+}
+
 static int mesh_single(qsp_mesh_extractor* m, const float* in, bool decode, int64_t* n_verts, int64_t* n_faces) {
     const int rc = mesh_call(m, m->single, 1, in, decode);
     if (rc) return rc;
@@ -522,29 +574,40 @@ static int mesh_single(qsp_mesh_extractor* m, const float* in, bool decode, int6
 }
 
 extern "C" int qsp_mesh_extract(qsp_mesh_extractor* m, const float* code, int64_t* n_verts, int64_t* n_faces) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    const CallLock lk = mesh_lock(m);
     if (!m || !code) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extract: null argument");
+    if (m->grp) return group_extractor_refusal("qsp_mesh_extract");
     return mesh_single(m, code, true, n_verts, n_faces);
 }
 
 extern "C" int qsp_mesh_from_volume(qsp_mesh_extractor* m, const float* sdf_volume, int64_t* n_verts, int64_t* n_faces) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    const CallLock lk = mesh_lock(m);
     if (!m || !sdf_volume) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_from_volume: null argument");
     return mesh_single(m, sdf_volume, false, n_verts, n_faces);
 }
 
 // argument checks of both batch entry points, then the call; a batch that fails leaves no batch result behind
-static int mesh_batch(qsp_mesh_extractor* m, int32_t n, const float* in, bool decode, int64_t* n_verts, int64_t* n_faces, const char* who) {
+// (group: the call is qsp_mesh_extract_batch_group, cls its class indices)
+static int mesh_batch(qsp_mesh_extractor* m, int32_t n, const float* in, bool decode, int64_t* n_verts, int64_t* n_faces, const char* who,
+                      bool group = false, const int32_t* cls = nullptr) {
     const std::string w(who);
-    if (!m || !in || !n_verts || !n_faces) return qsp_fail(QSP_ERR_INVALID, (w + ": null argument").c_str());
+    if (!m || !in || !n_verts || !n_faces || (group && !cls)) return qsp_fail(QSP_ERR_INVALID, (w + ": null argument").c_str());
     if (n < 0) return qsp_fail(QSP_ERR_INVALID, (w + ": negative number of items").c_str());
+    if (group && !m->grp)
+        return qsp_fail(QSP_ERR_INVALID, (w + ": this extractor is over one decoder (qsp_mesh_extractor_create): call "
+                                              "qsp_mesh_extract_batch, or create it with qsp_mesh_extractor_create_group").c_str());
+    if (decode && !group && m->grp) return group_extractor_refusal(who);
     if (m->method != 0)
         return qsp_fail(QSP_ERR_UNSUPPORTED, (w + ": batches run Lewiner's marching cubes (method 0) only; method 1, the "
                                                   "face-consistent table, is extracted one mesh per call").c_str());
     if (n == 0) return QSP_OK;
-    const int rc = mesh_call(m, m->batch, n, in, decode);
+    int rc = QSP_OK;
+    if (group) {      // (a member's options may have changed since the extractor was created)
+        rc = group_check(m->grp);
+        if (!rc) rc = group_classes(m->grp, n, cls);
+        if (rc) return rc;
+    }
+    rc = mesh_call(m, m->batch, n, in, decode, group ? cls : nullptr);
     if (rc) return rc;
     std::copy(m->batch.n_verts.begin(), m->batch.n_verts.end(), n_verts);
     std::copy(m->batch.n_faces.begin(), m->batch.n_faces.end(), n_faces);
@@ -552,14 +615,18 @@ static int mesh_batch(qsp_mesh_extractor* m, int32_t n, const float* in, bool de
 }
 
 extern "C" int qsp_mesh_extract_batch(qsp_mesh_extractor* m, int32_t n, const float* codes, int64_t* n_verts, int64_t* n_faces) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    const CallLock lk = mesh_lock(m);
     return mesh_batch(m, n, codes, true, n_verts, n_faces, "qsp_mesh_extract_batch");
 }
 
+extern "C" int qsp_mesh_extract_batch_group(qsp_mesh_extractor* m, int32_t n, const float* codes, const int32_t* cls, int64_t* n_verts,
+                                            int64_t* n_faces) {
+    const CallLock lk = mesh_lock(m);
+    return mesh_batch(m, n, codes, true, n_verts, n_faces, "qsp_mesh_extract_batch_group", true, cls);
+}
+
 extern "C" int qsp_mesh_from_volumes(qsp_mesh_extractor* m, int32_t n, const float* sdf_volumes, int64_t* n_verts, int64_t* n_faces) {
-    std::unique_lock<std::recursive_mutex> lk_d;
-    if (m && m->dec) lk_d = std::unique_lock<std::recursive_mutex>(m->dec->mu);
+    const CallLock lk = mesh_lock(m);
     return mesh_batch(m, n, sdf_volumes, false, n_verts, n_faces, "qsp_mesh_from_volumes");
 }
 
@@ -598,7 +665,7 @@ extern "C" int qsp_mesh_fetch_f64(qsp_mesh_extractor* m, double* verts) {
 
 extern "C" int qsp_mesh_fetch_batch(qsp_mesh_extractor* m, float* verts, double* verts_f64, int32_t* faces, float* sdf_volumes) {
     if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_fetch_batch: null extractor");
-    std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
+    const CallLock lk = mesh_lock(m);
     return mesh_fetch(m, m->batch, verts, verts_f64, faces, sdf_volumes, "qsp_mesh_fetch_batch");
 }
 
@@ -613,7 +680,7 @@ extern "C" int qsp_mesh_extractor_set_batch_limit(qsp_mesh_extractor* m, int32_t
     if (!m) return qsp_fail(QSP_ERR_INVALID, "qsp_mesh_extractor_set_batch_limit: null extractor");
     if (max_volumes_per_pass < 1 || max_volumes_per_pass > QSP_MESH_BATCH_LIMIT_DEFAULT)
         return qsp_fail(QSP_ERR_INVALID, "mesh batch limit: 1 .. 64 (QSP_MESH_BATCH_LIMIT_DEFAULT) volumes per pass");
-    std::unique_lock<std::recursive_mutex> lk_d(m->dec->mu);
+    const CallLock lk = mesh_lock(m);
     m->limit = max_volumes_per_pass;
     return QSP_OK;
 }

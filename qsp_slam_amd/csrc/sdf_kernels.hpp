@@ -1719,28 +1719,45 @@ __global__ __launch_bounds__(H2_THREADS) void k_decode_h2(const float* __restric
 // the same arithmetic on the same inputs whichever workgroup runs it: a volume has the bits of a k_decode launch with its code.
 // A workgroup takes `chunk` consecutive tiles of the (volume, tile) sequence and folds the code into c0 / c4 again (mlp_prepare)
 // whenever the next tile belongs to another volume -- consecutive, so that happens once per volume it touches and not per tile.
+// GRP (the k_group_grid_decode* entry points, a mesh extractor over a decoder group): P is the group's parameter array and volume
+// v is decoded with P + cls[v], so the volume boundary inside a run may be a decoder boundary too: the next code is folded with
+// the NEXT decoder's weights, and every tile runs on its volume's parameters -- volume v has the bits of a k_decode launch of
+// decoder cls[v] with its code.  The single-decoder entry points (GRP = false) never read cls and compile to the code they had
+// before there were group forms; both are thin __global__ shells around one body, like the GRP flag of the refinement kernels
+// (the flag cannot sit on these kernels themselves: their names are looked up by the ISA budget).
 // ---------------------------------------------------------------------------------------------------------------
-template <bool BF3>
-__global__ __launch_bounds__(MLP_THREADS, 2) void k_grid_decode(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n,
-                                                                int n_vol, int chunk, const MlpParams* __restrict__ P,
-                                                                float* __restrict__ y_out) {
+template <bool BF3, bool GRP>
+__device__ __forceinline__ void grid_decode_body(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n, int n_vol,
+                                                 int chunk, const MlpParams* __restrict__ P, const int32_t* __restrict__ cls,
+                                                 float* __restrict__ y_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
     const int tpv = (int)((n + TILE_P - 1) / TILE_P);          // (n_vol tpv < 2^31: a pass is at most 64 volumes of 128^3)
     const int g0 = blockIdx.x * chunk, run = min(chunk, tpv * n_vol - g0);
     int vol = g0 / tpv, t = g0 - vol * tpv;
+    [[maybe_unused]] const MlpParams* Pv = P;      // (GRP) the parameters of the volume in hand
     for (int i = 0; i < run; ++i) {
         if (i == 0 || t == 0) {             // the run's first tile, or the first tile of the next volume
             __syncthreads();                // (the tile before is through with c0 / c4)
             if (threadIdx.x < CODE_LEN) s.code[threadIdx.x] = codes[vol * CODE_LEN + threadIdx.x];
-            mlp_prepare(s, P);
+            if constexpr (GRP) {
+                Pv = P + __builtin_amdgcn_readfirstlane(cls[vol]);      // (wave-uniform: vol is)
+                mlp_prepare(s, Pv);
+            } else {
+                mlp_prepare(s, P);
+            }
             y_out += i == 0 ? vol * n : n;
         }
         __syncthreads();
         if (threadIdx.x < TILE_P) stage_point(s, xyz, n, t * TILE_P + threadIdx.x);
         __syncthreads();
-        if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, P);
-        else mlp_tile<false, 4, false, false>(s, P);
+        if constexpr (GRP) {
+            if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, Pv);      // (neither tile keeps a decoder's constants from one call to the next)
+            else mlp_tile<false, 4, false, false>(s, Pv);
+        } else {
+            if (BF3) mlp_tile_bf3<QSP_BF3_PF>(s, P);
+            else mlp_tile<false, 4, false, false>(s, P);
+        }
         if (threadIdx.x < TILE_P) {
             const int64_t v = t * TILE_P + threadIdx.x;
             if (v < n) y_out[v] = s.y[threadIdx.x];
@@ -1752,26 +1769,51 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void k_grid_decode(const float* __r
     }
 }
 
-// grid decode on the split-fp16 tile (four waves per workgroup)
-template <bool NARROW>
-__global__ __launch_bounds__(H2_THREADS) void k_grid_decode_h2(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n,
-                                                               int n_vol, int chunk, const MlpParams* __restrict__ P,
-                                                               float* __restrict__ y_out) {
+template <bool BF3>
+__global__ __launch_bounds__(MLP_THREADS, 2) void k_grid_decode(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n,
+                                                                int n_vol, int chunk, const MlpParams* __restrict__ P,
+                                                                float* __restrict__ y_out) {
+    grid_decode_body<BF3, false>(codes, xyz, n, n_vol, chunk, P, nullptr, y_out);
+}
+template <bool BF3>
+__global__ __launch_bounds__(MLP_THREADS, 2) void k_group_grid_decode(const float* __restrict__ codes, const float* __restrict__ xyz,
+                                                                      int64_t n, int n_vol, int chunk, const MlpParams* __restrict__ P,
+                                                                      const int32_t* __restrict__ cls, float* __restrict__ y_out) {
+    grid_decode_body<BF3, true>(codes, xyz, n, n_vol, chunk, P, cls, y_out);
+}
+
+// grid decode on the split-fp16 tile (four waves per workgroup).  GRP: the tile keeps a decoder's constants (w8, the biases of
+// layers 1..7) in LDS from one call to the next, so they are staged again when -- and only when -- the next volume's decoder is
+// another one than the one staged (dec_staged, as in k_mlp_fwd_h2), not per volume.  amax is handed in at every decoder change:
+// a decoder's range flag is raised by the tiles that ran on that decoder, so each member of the group reports for itself.
+template <bool NARROW, bool GRP>
+__device__ __forceinline__ void grid_decode_h2_body(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n, int n_vol,
+                                                    int chunk, const MlpParams* __restrict__ P, const int32_t* __restrict__ cls,
+                                                    float* __restrict__ y_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     MlpSmem& s = *reinterpret_cast<MlpSmem*>(smem_raw);
     const int tpv = (int)((n + TILE_P - 1) / TILE_P);
     const int g0 = blockIdx.x * chunk, run = min(chunk, tpv * n_vol - g0);
     int vol = g0 / tpv, t = g0 - vol * tpv;
-    bool staged = false;
+    [[maybe_unused]] bool staged = false;
+    [[maybe_unused]] int dec = 0, dec_staged = -1;      // (GRP) the decoder of the volume in hand, the one whose constants are in LDS
     float amax = 0.f;
     for (int i = 0; i < run; ++i) {
         if (i == 0 || t == 0) {             // the run's first tile, or the first tile of the next volume
             __syncthreads();                // (the tile before is through with c0 / c4)
             if (threadIdx.x < CODE_LEN) s.code[threadIdx.x] = codes[vol * CODE_LEN + threadIdx.x];
+            if constexpr (GRP) {
+                dec = __builtin_amdgcn_readfirstlane(cls[vol]);      // (wave-uniform: vol is)
+                if (dec != dec_staged && dec_staged >= 0) {          // the tiles so far ran on dec_staged: its flag, then a fresh maximum
+                    if (!(amax <= H2_MAX)) *P[dec_staged].range_flag = 1;
+                    amax = 0.f;
+                }
+            }
             __syncthreads();
             for (int u = threadIdx.x; u < HID; u += H2_THREADS) {      // mlp_prepare for 256 threads
                 float a, a4;
-                code_bias(P, u, s.code, a, a4);
+                if constexpr (GRP) code_bias(P + dec, u, s.code, a, a4);
+                else code_bias(P, u, s.code, a, a4);
                 s.c0[u] = a;
                 s.c4[u] = a4;
             }
@@ -1780,8 +1822,13 @@ __global__ __launch_bounds__(H2_THREADS) void k_grid_decode_h2(const float* __re
         __syncthreads();
         if (threadIdx.x < TILE_P) stage_point(s, xyz, n, t * TILE_P + threadIdx.x);
         __syncthreads();
-        mlp_tile_h2<false, 2, !NARROW, 2, 4, NARROW>(s, P, amax, !staged);
-        staged = true;
+        if constexpr (GRP) {
+            mlp_tile_h2<false, 2, !NARROW, 2, 4, NARROW>(s, P + dec, amax, dec != dec_staged);   // (constants: again when the decoder changes)
+            dec_staged = dec;
+        } else {
+            mlp_tile_h2<false, 2, !NARROW, 2, 4, NARROW>(s, P, amax, !staged);
+            staged = true;
+        }
         if (threadIdx.x < TILE_P) {
             const int64_t v = t * TILE_P + threadIdx.x;
             if (v < n) y_out[v] = s.y[threadIdx.x];
@@ -1791,7 +1838,24 @@ __global__ __launch_bounds__(H2_THREADS) void k_grid_decode_h2(const float* __re
             ++vol;
         }
     }
-    if (!(amax <= H2_MAX)) *P->range_flag = 1;
+    if constexpr (GRP) {
+        if (dec_staged >= 0 && !(amax <= H2_MAX)) *P[dec_staged].range_flag = 1;
+    } else {
+        if (!(amax <= H2_MAX)) *P->range_flag = 1;
+    }
+}
+
+template <bool NARROW>
+__global__ __launch_bounds__(H2_THREADS) void k_grid_decode_h2(const float* __restrict__ codes, const float* __restrict__ xyz, int64_t n,
+                                                               int n_vol, int chunk, const MlpParams* __restrict__ P,
+                                                               float* __restrict__ y_out) {
+    grid_decode_h2_body<NARROW, false>(codes, xyz, n, n_vol, chunk, P, nullptr, y_out);
+}
+template <bool NARROW>
+__global__ __launch_bounds__(H2_THREADS) void k_group_grid_decode_h2(const float* __restrict__ codes, const float* __restrict__ xyz,
+                                                                     int64_t n, int n_vol, int chunk, const MlpParams* __restrict__ P,
+                                                                     const int32_t* __restrict__ cls, float* __restrict__ y_out) {
+    grid_decode_h2_body<NARROW, true>(codes, xyz, n, n_vol, chunk, P, cls, y_out);
 }
 
 // the screening tile (mlp_tile_h1) on explicit query points: what the first pass of the screened forward computes, exposed for

@@ -609,6 +609,8 @@ template <bool GRAD, bool NARROW> static auto decode_h2_kernel() { return form<M
 template <int NW> static auto decode_screen_kernel() { return form<MlpSmemH1>(k_decode_screen<NW>, 64 * NW); }
 template <bool BF3> static auto grid_decode_kernel() { return form<MlpSmem>(k_grid_decode<BF3>, MLP_THREADS); }
 template <bool NARROW> static auto grid_decode_h2_kernel() { return form<MlpSmem>(k_grid_decode_h2<NARROW>, H2_THREADS); }
+template <bool BF3> static auto group_grid_decode_kernel() { return form<MlpSmem>(k_group_grid_decode<BF3>, MLP_THREADS); }
+template <bool NARROW> static auto group_grid_decode_h2_kernel() { return form<MlpSmem>(k_group_grid_decode_h2<NARROW>, H2_THREADS); }
 static auto scan_kernel() { return form<float[SCAN_RAYS * SCAN_LD]>(k_scan, SCAN_RAYS); }
 
 // The selectors: which form a pass takes, from the decoder's settings.  A selector returns one family's Form type, so the
@@ -646,6 +648,11 @@ static auto grid_decode_form(int bf3, bool narrow) {
     if (bf3 == 2) return narrow ? grid_decode_h2_kernel<true>() : grid_decode_h2_kernel<false>();
     return bf3 ? grid_decode_kernel<true>() : grid_decode_kernel<false>();
 }
+// the same over a decoder group: one class index per volume more in the argument list, so a selector of its own
+static auto group_grid_decode_form(int bf3, bool narrow) {
+    if (bf3 == 2) return narrow ? group_grid_decode_h2_kernel<true>() : group_grid_decode_h2_kernel<false>();
+    return bf3 ? group_grid_decode_kernel<true>() : group_grid_decode_kernel<false>();
+}
 static auto decode_screen_form(int waves) { return waves == 8 ? decode_screen_kernel<8>() : decode_screen_kernel<4>(); }
 
 // Raises the dynamic-LDS limit of every form a selector can return (once per process): a form that can be launched cannot be
@@ -675,7 +682,10 @@ static int mlp_attr_once() {
             for (const bool narrow : {false, true}) QSP_HIP(raise(decode_form(grad, bf3, narrow)));
     for (const int waves : {4, 8}) QSP_HIP(raise(decode_screen_form(waves)));
     for (const int bf3 : {0, 1, 2})
-        for (const bool narrow : {false, true}) QSP_HIP(raise(grid_decode_form(bf3, narrow)));
+        for (const bool narrow : {false, true}) {
+            QSP_HIP(raise(grid_decode_form(bf3, narrow)));
+            QSP_HIP(raise(group_grid_decode_form(bf3, narrow)));
+        }
     done = true;
     return QSP_OK;
 }
@@ -818,6 +828,17 @@ static void launch_grid_decode(qsp_decoder* d, const float* codes, const float* 
     const int chunk = (int)((tiles + 4095) / 4096);
     const int grid = (int)((tiles + chunk - 1) / chunk);
     launch(grid_decode_form(d->fwd_bf3, d->P.narrow), grid, d->stream, codes, xyz, n, n_vol, chunk, d->Pd, y);
+}
+
+// the same over a decoder group (callers hold its locks, group_check has passed): volume v with the parameters of member cls[v]
+// (device, n_vol class indices in [0, members)).  The first member lends stream and settings, as to every group call.
+static void launch_grid_decode_group(qsp_decoder_group* g, const float* codes, const int32_t* cls, const float* xyz, int64_t n, int n_vol,
+                                     float* y) {
+    const qsp_decoder* d = g->m[0];
+    const int64_t tiles = (n + TILE_P - 1) / TILE_P * n_vol;
+    const int chunk = (int)((tiles + 4095) / 4096);
+    const int grid = (int)((tiles + chunk - 1) / chunk);
+    launch(group_grid_decode_form(d->fwd_bf3, d->P.narrow), grid, d->stream, codes, xyz, n, n_vol, chunk, g->Pd, cls, y);
 }
 
 static int decode_once(qsp_decoder* d, const float* code, const float* xyz, int64_t n, float* y, float* grad, bool* hit) {

@@ -3,8 +3,9 @@ types and failure behaviour; the numerics are batched HIP launches behind the C-
 
 Added on top of the reference interface (not replacing it): `reconstruct_objects_batched`, which runs many objects x
 yaw-flip hypotheses in one resident batch -- what src/LocalMapping_util.cc:705-760 does as 4 serial Python calls per
-object -- and `OptimizerGroup`, the reference's per-class optimizers (src/LocalMapping.cc:33-69) refining the objects of
-all classes in one batch over a decoder group."""
+object --, `OptimizerGroup`, the reference's per-class optimizers (src/LocalMapping.cc:33-69) refining the objects of
+all classes in one batch over a decoder group, and `MeshExtractorGroup`, its per-class mesh extractors
+(src/LocalMapping_util.cc:818-835) meshing the codes of all classes in one call."""
 import ctypes as C
 import math
 import time
@@ -219,7 +220,7 @@ class Optimizer(object):
         return _reconstruct_batched(self, self.decoder, objects, flip_sample_num, select, None)
 
     # ---- the caller's loop around reconstruct_object, on the device ---------------------------------
-    def refine_detections(self, detections, flip_sample_num=4, taps=False):
+    def refine_detections(self, detections, flip_sample_num=4, taps=False, mesh_extractor=None):
         """LocalMapping::ProcessDetectedObjects' marshalling + flip loop + keep rule (src/LocalMapping_util.cc:585-760) for a
         list of detections in ONE call (qsp_refine_detections, include/qsp_hip.h).  Each detection is a dict of WORLD-frame
         inputs, as the caller holds them:
@@ -227,8 +228,14 @@ class Optimizer(object):
             pts_world (M,3) map points on the object, fg_px (F,2) key-point pixels, fg_world (F,3) their map points,
             bg_rays (B,3), found_good_orientation (bool, default False -> flip_sample_num hypotheses, else one).
         Returns per detection the object the reference keeps in pyMapObjectLeastLoss (t_cam_obj None when not good), with
-        the extra keys kept_flip and losses; taps=True adds the assembled pts / rays / depth / initial poses."""
-        return _refine_detections(self, self.decoder, detections, flip_sample_num, taps, None)
+        the extra keys kept_flip and losses; taps=True adds the assembled pts / rays / depth / initial poses.
+        mesh_extractor (a MeshExtractor of this optimizer's decoder): every result also carries .vertices and .faces, the mesh
+        of its refined code -- what src/LocalMapping_util.cc:832-835 fetches next -- from one extract_meshes_from_codes call
+        over the kept results; None for both on a result that was not kept or whose code has no surface."""
+        out = _refine_detections(self, self.decoder, detections, flip_sample_num, taps, None)
+        if mesh_extractor is not None:
+            _attach_meshes(out, lambda codes, kept: mesh_extractor.extract_meshes_from_codes(codes))
+        return out
 
     def estimate_pose_cam_obj(self, t_co_se3, scale, pts, code):
         """reconstruct/optimizer.py:47-93 -> (4,4) float32 SE3 (the reference returns a torch tensor that C++ casts to
@@ -342,6 +349,18 @@ def _refine_detections(self, target, detections, flip_sample_num, taps, classes)
     return out
 
 
+def _attach_meshes(results, extract):
+    """.vertices / .faces on every result of a refine_detections call: the meshes extract(codes, kept) gives for the codes of the
+    kept results (kept = their positions in the list), None for both everywhere else"""
+    kept = [i for i, r in enumerate(results) if r.is_good]
+    meshes = extract([results[i].code for i in kept], kept) if kept else []
+    for r in results:
+        r["vertices"] = r["faces"] = None
+    for i, m in zip(kept, meshes):
+        if m is not None:
+            results[i]["vertices"], results[i]["faces"] = m.vertices, m.faces
+
+
 def _estimate_pose(self, target, items, classes):
     """Optimizer.estimate_pose_cam_obj over a list of dicts(t_co_se3, scale, pts, code) in one call on `target` (a decoder, or
     a DecoderGroup with one class per item) -> list of (4,4) float32"""
@@ -406,11 +425,18 @@ class OptimizerGroup(object):
         cls = self._class_index(objects, "object")
         return _reconstruct_batched(self._cfg, self.group, objects, flip_sample_num, select, cls)
 
-    def refine_detections(self, detections, flip_sample_num=4, taps=False):
+    def refine_detections(self, detections, flip_sample_num=4, taps=False, mesh_extractors=None):
         """Optimizer.refine_detections over the detections of several classes in one call: what LocalMapping_util.cc:585-760
-        does per detection with the optimizer of its class"""
+        does per detection with the optimizer of its class.  mesh_extractors (a MeshExtractorGroup over the same class ids):
+        every result also carries .vertices and .faces, the mesh of its refined code by the extractor of its class
+        (LocalMapping_util.cc:818-835), from one group mesh call over the kept results; None for both on a result that was
+        not kept or whose code has no surface."""
         cls = self._class_index(detections, "detection")
-        return _refine_detections(self._cfg, self.group, detections, flip_sample_num, taps, cls)
+        out = _refine_detections(self._cfg, self.group, detections, flip_sample_num, taps, cls)
+        if mesh_extractors is not None:
+            _attach_meshes(out, lambda codes, kept: mesh_extractors.extract_meshes_from_codes(
+                codes, [detections[i]["class_id"] for i in kept]))
+        return out
 
     def estimate_pose_cam_obj(self, items):
         """Optimizer.estimate_pose_cam_obj for a list of dicts(t_co_se3, scale, pts, code, class_id) in one call -> list of (4,4)"""
@@ -452,6 +478,53 @@ def split_batch_meshes(n_verts, n_faces, verts, faces, volumes=None):
             continue
         out.append((verts[v_end[i] - n_verts[i]:v_end[i]].copy(), faces[f_end[i] - n_faces[i]:f_end[i]].copy(),
                     None if volumes is None else volumes[i].copy()))
+    return out
+
+
+def _run_mesh_batch(handle, voxels_dim, n, volumes, call):
+    """a batch call on the extractor `handle` -- call(n_verts*, n_faces*) -> status -- and the fetch of its result:
+    split_batch_meshes' list"""
+    nv, nf = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    _lib.check(call(_lib.i64ptr(nv), _lib.i64ptr(nf)))
+    if n == 0:
+        return []
+    nv, nf = nv[:n], nf[:n]
+    verts = np.empty((int(nv.sum()), 3), np.float64)
+    faces = np.empty((int(nf.sum()), 3), np.int32)
+    vols = np.empty((n,) + (voxels_dim,) * 3, np.float32) if volumes else None
+    _lib.check(_lib.lib().qsp_mesh_fetch_batch(handle, None, verts.ctypes.data_as(C.POINTER(C.c_double)), _lib.i32ptr(faces),
+                                               _lib.fptr(vols) if volumes else None))
+    return split_batch_meshes(nv, nf, verts, faces, vols)
+
+
+def _volume_rows(volumes, voxels_dim):
+    """a sequence of (dim,dim,dim) volumes as the (n, dim^3) array the library reads, and n"""
+    vols = [np.asarray(v, np.float32).reshape(-1) for v in volumes]
+    if any(v.size != voxels_dim ** 3 for v in vols):
+        raise ValueError("volumes must be (%d,)*3" % voxels_dim)
+    return (_lib.f32c(np.stack(vols)) if vols else np.zeros(1, np.float32)), len(vols)
+
+
+def _code_rows(codes, code_len, width):
+    """a sequence of codes, each cut to code_len, as the zero-padded (n, width) array the library reads (width = the decoder's
+    code length), and n"""
+    rows = [np.asarray(c, np.float32).reshape(-1)[:code_len] for c in codes]
+    host = np.zeros((max(len(rows), 1), width), np.float32)
+    for i, c in enumerate(rows):
+        host[i, :min(c.size, width)] = c[:width]
+    return host, len(rows)
+
+
+def _mesh_dicts(res, return_volumes):
+    """split_batch_meshes' tuples as the objects extract_mesh_from_code returns (None stays None)"""
+    out = []
+    for r in res:
+        if r is not None:
+            d = ForceKeyErrorDict(vertices=r[0], faces=r[1])
+            if return_volumes:
+                d["sdf_volume"] = r[2]
+            r = d
+        out.append(r)
     return out
 
 
@@ -534,26 +607,14 @@ class MeshExtractor(object):
         _lib.check(_lib.lib().qsp_mesh_extractor_set_batch_limit(self.handle, int(max_volumes_per_pass)))
 
     def _batch(self, entry, host, n, volumes):
-        nv, nf = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-        _lib.check(entry(self.handle, n, _lib.fptr(host), _lib.i64ptr(nv), _lib.i64ptr(nf)))
-        if n == 0:
-            return []
-        nv, nf = nv[:n], nf[:n]
-        verts = np.empty((int(nv.sum()), 3), np.float64)
-        faces = np.empty((int(nf.sum()), 3), np.int32)
-        vols = np.empty((n,) + (self.voxels_dim,) * 3, np.float32) if volumes else None
-        _lib.check(_lib.lib().qsp_mesh_fetch_batch(self.handle, None, verts.ctypes.data_as(C.POINTER(C.c_double)), _lib.i32ptr(faces),
-                                                   _lib.fptr(vols) if volumes else None))
-        return split_batch_meshes(nv, nf, verts, faces, vols)
+        return _run_mesh_batch(self.handle, self.voxels_dim, n, volumes,
+                               lambda nv, nf: entry(self.handle, n, _lib.fptr(host), nv, nf))
 
     def meshes_from_volumes(self, volumes):
         """mesh_from_volume on a sequence of (dim,dim,dim) volumes in one call: a list of (vertices, faces) in input order, the
         values mesh_from_volume gives for each -- or None for a volume without a surface, where the single call raises."""
-        vols = [np.asarray(v, np.float32).reshape(-1) for v in volumes]
-        if any(v.size != self.voxels_dim ** 3 for v in vols):
-            raise ValueError("volumes must be (%d,)*3" % self.voxels_dim)
-        host = _lib.f32c(np.stack(vols)) if vols else np.zeros(1, np.float32)
-        return [r if r is None else r[:2] for r in self._batch(_lib.lib().qsp_mesh_from_volumes, host, len(vols), False)]
+        host, n = _volume_rows(volumes, self.voxels_dim)
+        return [r if r is None else r[:2] for r in self._batch(_lib.lib().qsp_mesh_from_volumes, host, n, False)]
 
     def extract_meshes_from_codes(self, codes, return_volumes=False):
         """extract_mesh_from_code for a sequence of codes in one call (one grid decode and one marching-cubes launch chain for
@@ -563,19 +624,100 @@ class MeshExtractor(object):
         One difference: a code whose volume has no surface yields None at its place in the list -- the single call raises like
         scikit-image, which would lose the other meshes of the batch.  Lewiner's method only (method="table" is not batched)."""
         start = time.time()
-        rows = [np.asarray(c, np.float32).reshape(-1)[: self.code_len] for c in codes]
-        width = self.decoder.code_len                     # the row length the library reads
-        host = np.zeros((max(len(rows), 1), width), np.float32)
-        for i, c in enumerate(rows):
-            host[i, :min(c.size, width)] = c[:width]
-        res = self._batch(_lib.lib().qsp_mesh_extract_batch, host, len(rows), return_volumes)
-        print("Extract %d meshes takes %f seconds" % (len(rows), time.time() - start))
-        out = []
-        for r in res:
-            if r is not None:
-                d = ForceKeyErrorDict(vertices=r[0], faces=r[1])
-                if return_volumes:
-                    d["sdf_volume"] = r[2]
-                r = d
-            out.append(r)
-        return out
+        host, n = _code_rows(codes, self.code_len, self.decoder.code_len)
+        res = self._batch(_lib.lib().qsp_mesh_extract_batch, host, n, return_volumes)
+        print("Extract %d meshes takes %f seconds" % (n, time.time() - start))
+        return _mesh_dicts(res, return_volumes)
+
+
+class MeshExtractorGroup(object):
+    """The reference's per-class mesh extractors (src/LocalMapping_util.cc:818-835: the MeshExtractor of the detection's class,
+    mmPyMeshExtractors) meshing the codes of ALL classes in one call over a decoder group (qsp_mesh_extract_batch_group,
+    include/qsp_hip.h) instead of one call per class.  `extractors` = {class_id: MeshExtractor}, the dictionary the embedder
+    holds; a code's class index is the position of its class id among the sorted ids, as in OptimizerGroup.  The members share
+    one voxel grid, so they must agree on voxels_dim, code_len and method: ValueError otherwise.  decoder_group: a DecoderGroup
+    over the members' decoders in that order (an OptimizerGroup's .group) to use instead of building one; it is then the
+    caller's to close.  Every item is bit for bit what extract_mesh_from_code of its class's extractor returns (the fp16x2
+    range fallback repeats a pass for all classes in it: include/qsp_hip.h).  close() before the decoders go."""
+
+    def __init__(self, extractors, decoder_group=None):
+        if not extractors:
+            raise ValueError("MeshExtractorGroup needs at least one extractor")
+        self.class_ids = sorted(extractors)
+        self.extractors = dict(extractors)
+        first = self.extractors[self.class_ids[0]]
+        for cid in self.class_ids[1:]:
+            e = self.extractors[cid]
+            for what in ("voxels_dim", "code_len", "method"):
+                if getattr(e, what) != getattr(first, what):
+                    raise ValueError("MeshExtractorGroup: %s of class %r differs from that of class %r (the classes of a group "
+                                     "share one voxel grid)" % (what, cid, self.class_ids[0]))
+        self.voxels_dim, self.code_len, self.method = first.voxels_dim, first.code_len, first.method
+        self._index = {cid: i for i, cid in enumerate(self.class_ids)}
+        self._own_group = decoder_group is None
+        if decoder_group is None:
+            from .. import decoder
+            decoder_group = decoder.DecoderGroup([self.extractors[cid].decoder for cid in self.class_ids])
+        self.group = decoder_group
+        self._handle = None
+
+    @property
+    def handle(self):
+        """the qsp_mesh_extractor* over the group, created at first use"""
+        if self._handle is None:
+            h = C.c_void_p()
+            pts = _lib.f32c(create_voxel_grid(vol_dim=self.voxels_dim))
+            _lib.check(_lib.lib().qsp_mesh_extractor_create_group(self.group.handle, self.voxels_dim, _lib.fptr(pts), C.byref(h)))
+            self._handle = h
+            _lib.check(_lib.lib().qsp_mesh_extractor_set_method(h, 0 if self.method == "lewiner" else 1))
+        return self._handle
+
+    def _class_index(self, class_ids, n):
+        class_ids = list(class_ids)
+        if len(class_ids) != n:
+            raise ValueError("MeshExtractorGroup: %d class ids for %d codes (one per code)" % (len(class_ids), n))
+        for i, cid in enumerate(class_ids):
+            if cid not in self._index:
+                raise ValueError("code %d: class_id %r has no extractor in this group" % (i, cid))
+        return np.array([self._index[cid] for cid in class_ids], np.int32)
+
+    def set_batch_limit(self, max_volumes_per_pass):
+        """volumes a call holds scratch memory for at a time (1 .. 64, the default); results do not depend on it"""
+        _lib.check(_lib.lib().qsp_mesh_extractor_set_batch_limit(self.handle, int(max_volumes_per_pass)))
+
+    def extract_meshes_from_codes(self, codes, class_ids, return_volumes=False):
+        """MeshExtractor.extract_meshes_from_codes over codes of several classes in one call: class_ids[i] is the class of
+        codes[i].  A list in input order of ForceKeyErrorDict(vertices (V,3) float64, faces (F,3) int32[, sdf_volume]), None
+        where a code's volume has no surface."""
+        start = time.time()
+        codes = list(codes)
+        cls = self._class_index(class_ids, len(codes))
+        host, n = _code_rows(codes, self.code_len, self.group.code_len)
+        res = _run_mesh_batch(self.handle, self.voxels_dim, n, return_volumes,
+                              lambda nv, nf: _lib.lib().qsp_mesh_extract_batch_group(self.handle, n, _lib.fptr(host), _lib.i32ptr(cls),
+                                                                                    nv, nf))
+        print("Extract %d meshes of %d classes takes %f seconds" % (n, len(self.class_ids), time.time() - start))
+        return _mesh_dicts(res, return_volumes)
+
+    def meshes_from_volumes(self, volumes):
+        """MeshExtractor.meshes_from_volumes on the group's extractor (marching cubes alone: no class is involved)"""
+        host, n = _volume_rows(volumes, self.voxels_dim)
+        res = _run_mesh_batch(self.handle, self.voxels_dim, n, False,
+                              lambda nv, nf: _lib.lib().qsp_mesh_from_volumes(self.handle, n, _lib.fptr(host), nv, nf))
+        return [r if r is None else r[:2] for r in res]
+
+    def close(self):
+        """the extractor first, then the decoder group when this object built it"""
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            _lib.lib().qsp_mesh_extractor_destroy(h)
+        self._handle = None
+        if getattr(self, "_own_group", False) and getattr(self, "group", None) is not None:
+            self.group.close()
+        self.group = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
