@@ -669,6 +669,32 @@ int qsp_ellipsoid_fit_prior(int device, int32_t n, const double* ellipsoid_in, c
                             const double* ground_plane_weight, double angle_sigma_deg, int32_t n_iter, double* ellipsoid_out,
                             double* chi2_out, int32_t* iters_out, double* trace);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sim3 refinement of loop candidates, batched: Optimizer::OptimizeSim3, src/Optimizer.cc:1050-1245, for every candidate key
+ * frame of LoopClosing::ComputeSim3 in ONE launch (one wave per candidate) -- per candidate one free Sim3 S12 (7 unknowns, or 6
+ * with fix_scale), per match the edge pair
+ *     e12 = obs1 - cam1(project(S12 * P2c)),   e21 = obs2 - cam2(project(S12^-1 * P1c)),   chi2 = invSigma2 |e|^2,
+ * Huber with delta = (double)sqrtf(th2) on both, g2o's numeric Jacobians (central differences through the vertex's oplus, delta
+ * 1e-9; with fix_scale the scale column is exactly 0), dense Levenberg-Marquardt: optimize(5); a pair leaves when either chi2
+ * exceeds th2; fewer than 10 pairs left: 0 inliers and S12 as it came (the flags are still reported); otherwise
+ * optimize(nBad > 0 ? 10 : 5) on the remaining pairs and the final count.
+ *   match_off (n_cand + 1): candidate c owns the matches [match_off[c], match_off[c+1]); starts at 0, never decreases
+ *   K1, K2 (n_cand,4) fx fy cx cy of the two key frames; sim3_in / sim3_out (n_cand,8) tx ty tz qx qy qz qw s
+ *   P1c, P2c (n_match,3): the matched points in their OWN camera frames (R1w X1 + t1w, R2w X2 + t2w, as doubles);
+ *   obs1, obs2 (n_match,2) undistorted key points; info1, info2 (n_match) invSigma2 of their octaves
+ *   inlier (n_match) out: 1 = the pair survived every check made; n_inliers (n_cand) out; trace (n_cand) out or NULL.
+ * A candidate's result has the same bits alone, in any batch and at any position.  Host pointers.  n_cand == 0 is QSP_OK and
+ * touches nothing; a candidate without matches returns 0 inliers and its input.  Null pointers, n_cand < 0, offsets that do not
+ * start at 0 or decrease: QSP_ERR_INVALID.  No output is written unless the call returns QSP_OK. */
+typedef struct {
+    int32_t iters[2];          /* LM iterations run in each of the two optimize calls         */
+    double trace[2][10][3];    /* chi2, lambda, trials after each (optimize call, iteration)   */
+} qsp_sim3_trace;
+int qsp_sim3_optimize_batch(int device, int32_t n_cand, const int32_t* match_off, const double* K1, const double* K2,
+                            const double* sim3_in, const double* P1c, const double* P2c, const double* obs1, const double* obs2,
+                            const double* info1, const double* info2, double th2, int32_t fix_scale, double* sim3_out,
+                            uint8_t* inlier, int32_t* n_inliers, qsp_sim3_trace* trace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@
 // Usage in the reference tree: NOTHING changes at the call sites.  qsp_slam_amd/orbslam/Optimizer_hip.cc (this repository)
 // takes the place of src/Optimizer.cc + src/Optimizer_util.cc in the CMake source list and defines the members of
 // `class Optimizer` exactly as include/Optimizer.h:75-107 declares them, forwarding the bundle adjustments and
-// PoseOptimization to OptimizerHip below, OptimizeSim3 / OptimizeEssentialGraph to the reference's own g2o code, and any call
+// PoseOptimization to OptimizerHip below, OptimizeEssentialGraph to the reference's own g2o code, OptimizeSim3 to it as well
+// unless QSP_SHIM_SIM3_HIP=1 asks for OptimizerHip::OptimizeSim3, and any call
 // the GPU path reports an error for to that g2o code as well.  OptimizerHip's entry points
 // return a qsp status (QSP_OK / QSP_ERR_*) instead of void so that the caller can tell; on error the map is left exactly as
 // it was found (the BA bookkeeping marks mnBALocalForKF / mnBAFixedForKF are rolled back) and qsp_last_error() is logged.
@@ -27,6 +28,7 @@
 #include <map>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "qsp_hip.h"
@@ -106,7 +108,8 @@ struct Marks {
 //   QSP_SHIM_ALLOW_G2O_FALLBACK=1   hand the failed call to the reference's own g2o code compiled into the drop-in (counted in
 //                                   `fallback_count()`, one stderr line per call);
 //   QSP_SHIM_NO_FALLBACK=1          strictest: std::abort() after the message.
-// OptimizeSim3 / OptimizeEssentialGraph are CPU pass-throughs by design and are not affected.
+// OptimizeEssentialGraph is a CPU pass-through by design and is not affected; OptimizeSim3 is one by
+// default and follows the table above where QSP_SHIM_SIM3_HIP=1 routes it to the library (0 inliers, matches and g2oS12 untouched).
 inline std::atomic<long>& failure_counter() {
     static std::atomic<long> n{0};
     return n;
@@ -256,6 +259,77 @@ struct Flat {   // the flattened graph + back-references for the write-back
         s->stereo_pt = st_pt.data(); s->stereo_kf = st_kf.data(); s->stereo_obs = st_obs.data(); s->stereo_info = st_info.data();
         s->objedge_kf = oe_kf.data(); s->objedge_obj = oe_obj.data(); s->objedge_meas = oe_meas.data();
         s->objedge_info = 1e3;   // const float invSigmaObject = 1e3, src/Optimizer_util.cc:447
+    }
+};
+
+// ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1050-1245) -----------------------------------------------------------------
+// The drop-in sends OptimizeSim3 to the library only where the deployment asked for it; the default stays the reference's g2o.
+inline bool sim3_on_gpu() {
+    const char* e = std::getenv("QSP_SHIM_SIM3_HIP");
+    return e && *e == '1';
+}
+
+// g2o::Sim3 <-> (tx ty tz qx qy qz qw s).  Templates on the Sim3 type: this header does not include g2o.
+template <typename S3>
+inline void sim3_to8(const S3& S, double* v) {
+    for (int i = 0; i < 3; ++i) v[i] = S.translation()[i];
+    v[3] = S.rotation().x(); v[4] = S.rotation().y(); v[5] = S.rotation().z(); v[6] = S.rotation().w();
+    v[7] = S.scale();
+}
+template <typename S3>
+inline void sim3_from8(const double* v, S3& S) {
+    typedef typename std::decay<decltype(S.rotation())>::type Q;
+    typedef typename std::decay<decltype(S.translation())>::type V;
+    S = S3(Q(v[6], v[3], v[4], v[5]), V(v[0], v[1], v[2]), v[7]);
+}
+
+// The candidates of one call, flattened: the walk and the filters of :1089-1182, edges in the order of the match slots.
+struct Sim3Flat {
+    std::vector<int32_t> off{0};
+    std::vector<double> K1, K2, S, P1, P2, o1, o2, i1, i2;
+    std::vector<std::vector<size_t>> index;          // per candidate: vnIndexEdge
+
+    // cv::Mat R (3x3) * X (3x1) + t in float32, then Converter::toVector3d: the product is rounded to float once per row
+    static void to_camera(const cv::Mat& R, const cv::Mat& t, const cv::Mat& X, std::vector<double>& out) {
+        for (int r = 0; r < 3; ++r) {
+            const float rx = (float)((double)R.at<float>(r, 0) * X.at<float>(0) + (double)R.at<float>(r, 1) * X.at<float>(1) +
+                                     (double)R.at<float>(r, 2) * X.at<float>(2));
+            out.push_back((double)(float)(rx + t.at<float>(r)));
+        }
+    }
+
+    template <typename KF, typename MP, typename S3>
+    void add(KF* pKF1, KF* pKF2, const std::vector<MP*>& vpMatches1, const S3& g2oS12) {
+        const cv::Mat& mK1 = pKF1->mK;
+        const cv::Mat& mK2 = pKF2->mK;
+        const double k1[4] = {mK1.template at<float>(0, 0), mK1.template at<float>(1, 1), mK1.template at<float>(0, 2), mK1.template at<float>(1, 2)};
+        const double k2[4] = {mK2.template at<float>(0, 0), mK2.template at<float>(1, 1), mK2.template at<float>(0, 2), mK2.template at<float>(1, 2)};
+        K1.insert(K1.end(), k1, k1 + 4);
+        K2.insert(K2.end(), k2, k2 + 4);
+        double s8[8];
+        sim3_to8(g2oS12, s8);
+        S.insert(S.end(), s8, s8 + 8);
+        const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+        const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+        index.emplace_back();
+        const int N = (int)vpMatches1.size();
+        for (int i = 0; i < N; ++i) {
+            if (!vpMatches1[i]) continue;
+            MP* pMP1 = vpMapPoints1[i];
+            MP* pMP2 = vpMatches1[i];
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (!pMP1 || pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+            to_camera(R1w, t1w, pMP1->GetWorldPos(), P1);
+            to_camera(R2w, t2w, pMP2->GetWorldPos(), P2);
+            const cv::KeyPoint& kpUn1 = pKF1->mvKeysUn[i];
+            const cv::KeyPoint& kpUn2 = pKF2->mvKeysUn[i2];
+            o1.push_back(kpUn1.pt.x); o1.push_back(kpUn1.pt.y);
+            o2.push_back(kpUn2.pt.x); o2.push_back(kpUn2.pt.y);
+            i1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
+            this->i2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);
+            index.back().push_back((size_t)i);
+        }
+        off.push_back((int32_t)o1.size() / 2);
     }
 };
 
@@ -496,6 +570,59 @@ public:
             for (int c = 0; c < 4; ++c) M.at<float>(r, c) = T[4 * r + c];
         pFrame->SetPose(M);
         return n_inliers;
+    }
+
+    // Optimizer::OptimizeSim3 for ALL candidate key frames of LoopClosing::ComputeSim3 in one library call
+    // (qsp_sim3_optimize_batch: one launch, one wave per candidate).  vvpMatches1[c] / vS12[c] / nInliers[c] belong to vpKF2[c]
+    // and are read and written as OptimizeSim3 does for one: vpMatches1[idx] = NULL for every pair that left, also where fewer than
+    // 10 pairs remained after the first pass (0 inliers); g2oS12 is written only where the second pass ran.  Returns the qsp
+    // status; on error nothing has been written.
+    template <typename KF, typename MP, typename S3>
+    static int OptimizeSim3Batch(KF* pKF1, const std::vector<KF*>& vpKF2, std::vector<std::vector<MP*>>& vvpMatches1,
+                                 std::vector<S3>& vS12, const float th2, const bool bFixScale, std::vector<int>& nInliers) {
+        using namespace qsp_shim;
+        const size_t nc = vpKF2.size();
+        if (vvpMatches1.size() != nc || vS12.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] OptimizeSim3Batch: %zu candidates, %zu match vectors, %zu Sim3\n", nc, vvpMatches1.size(), vS12.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { nInliers.clear(); return QSP_OK; }
+        Sim3Flat F;
+        for (size_t c = 0; c < nc; ++c) F.add(pKF1, vpKF2[c], vvpMatches1[c], vS12[c]);
+        std::vector<double> out(8 * nc);
+        std::vector<uint8_t> inlier(F.i1.size() + 1);
+        std::vector<int32_t> n_in(nc);
+        std::vector<qsp_sim3_trace> tr(nc);
+        const int rc = report("qsp_sim3_optimize_batch",
+                              qsp_sim3_optimize_batch(device(), (int32_t)nc, F.off.data(), F.K1.data(), F.K2.data(), F.S.data(), F.P1.data(),
+                                                      F.P2.data(), F.o1.data(), F.o2.data(), F.i1.data(), F.i2.data(), (double)th2,
+                                                      bFixScale ? 1 : 0, out.data(), inlier.data(), n_in.data(), tr.data()));
+        if (rc != QSP_OK) return rc;
+        nInliers.assign(nc, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t e = 0; e < F.index[c].size(); ++e)
+                if (!inlier[F.off[c] + e]) vvpMatches1[c][F.index[c][e]] = static_cast<MP*>(NULL);       // :1199-1200, :1233-1234
+            if (tr[c].iters[1] > 0) sim3_from8(&out[8 * c], vS12[c]);                                    // :1241-1242, full path only
+            nInliers[c] = n_in[c];
+        }
+        return QSP_OK;
+    }
+
+    // Optimizer::OptimizeSim3, src/Optimizer.cc:1050-1245: the batch of one.  *status (optional) receives the qsp status; on error
+    // neither the matches nor g2oS12 have been touched and 0 is returned.
+    template <typename KF, typename MP, typename S3>
+    static int OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, S3& g2oS12, const float th2, const bool bFixScale,
+                            int* status = nullptr) {
+        std::vector<KF*> kf(1, pKF2);
+        std::vector<std::vector<MP*>> m(1, vpMatches1);
+        std::vector<S3> s(1, g2oS12);
+        std::vector<int> n;
+        const int rc = OptimizeSim3Batch(pKF1, kf, m, s, th2, bFixScale, n);
+        if (status) *status = rc;
+        if (rc != QSP_OK) return 0;
+        vpMatches1 = m[0];
+        g2oS12 = s[0];
+        return n[0];
     }
 
     // src/Optimizer.cc:54-242

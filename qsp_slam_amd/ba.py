@@ -206,3 +206,50 @@ class PoseOptimizer(object):
                                                 C.byref(ninl), C.byref(tr)))
         trace = np.array(tr.trace[:], np.float64).reshape(4, 10, 3)
         return dict(pose=out, outlier=outlier[:n], n_inliers=int(ninl.value), iters=np.array(tr.iters[:], np.int32), trace=trace)
+
+
+def optimize_sim3_batch(candidates, th2, fix_scale, device=0, trace=False):
+    """Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1050-1245) for every loop candidate in ONE kernel launch
+    (qsp_sim3_optimize_batch, include/qsp_hip.h).  `candidates`: list of dicts with K1, K2 (4,) fx fy cx cy; sim3 (8,) tx ty tz
+    qx qy qz qw s of S12; P1c, P2c (n,3) the matched points in their own camera frames; obs1, obs2 (n,2); info1, info2 (n,).
+    Returns one dict per candidate: sim3 (8,), inlier (n,) uint8, n_inliers and, with trace=True, iters (2,) and trace (2,10,3)
+    chi2 / lambda / trials of the two optimize calls."""
+    nc = len(candidates)
+    if nc == 0:
+        return []
+    f64 = lambda key, w: [np.asarray(c[key], np.float64).reshape(-1, w) for c in candidates]
+    P1, P2, o1, o2 = f64("P1c", 3), f64("P2c", 3), f64("obs1", 2), f64("obs2", 2)
+    i1, i2 = f64("info1", 1), f64("info2", 1)
+    counts = [len(a) for a in P1]
+    for arrs in (P2, o1, o2, i1, i2):
+        if [len(a) for a in arrs] != counts:
+            raise ValueError("optimize_sim3_batch: the match arrays of a candidate differ in length")
+    off = np.zeros(nc + 1, np.int32)
+    off[1:] = np.cumsum(counts)
+    nm = int(off[-1])
+    cat = lambda arrs: _arr(np.concatenate(arrs), np.float64)
+    P1, P2, o1, o2, i1, i2 = cat(P1), cat(P2), cat(o1), cat(o2), cat(i1), cat(i2)
+    K1 = _arr(np.stack([np.asarray(c["K1"], np.float64).reshape(4) for c in candidates]), np.float64)
+    K2 = _arr(np.stack([np.asarray(c["K2"], np.float64).reshape(4) for c in candidates]), np.float64)
+    S0 = _arr(np.stack([np.asarray(c["sim3"], np.float64).reshape(8) for c in candidates]), np.float64)
+    out = np.zeros((nc, 8))
+    inlier = np.zeros(max(nm, 1), np.uint8)
+    ninl = np.zeros(nc, np.int32)
+    tr = (_lib.Sim3Trace * nc)() if trace else None
+    _lib.check(_lib.lib().qsp_sim3_optimize_batch(int(device), nc, _lib.i32ptr(off), _lib.dptr(K1), _lib.dptr(K2), _lib.dptr(S0),
+                                                  _lib.dptr(P1), _lib.dptr(P2), _lib.dptr(o1), _lib.dptr(o2), _lib.dptr(i1),
+                                                  _lib.dptr(i2), float(th2), 1 if fix_scale else 0, _lib.dptr(out),
+                                                  _lib.u8ptr(inlier), _lib.i32ptr(ninl), tr))
+    res = []
+    for c in range(nc):
+        r = dict(sim3=out[c].copy(), inlier=inlier[off[c]:off[c + 1]].copy(), n_inliers=int(ninl[c]))
+        if trace:
+            r["iters"] = np.array(tr[c].iters[:], np.int32)
+            r["trace"] = np.array(tr[c].trace[:], np.float64).reshape(2, 10, 3)
+        res.append(r)
+    return res
+
+
+def optimize_sim3(candidate, th2, fix_scale, device=0, trace=False):
+    """the batch of one"""
+    return optimize_sim3_batch([candidate], th2, fix_scale, device=device, trace=trace)[0]

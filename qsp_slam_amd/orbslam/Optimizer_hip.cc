@@ -9,7 +9,8 @@
 //   JointBundleAdjustment / GlobalJointBundleAdjustemnt        MI355X
 //   LocalBundleAdjustment / LocalJointBundleAdjustment         MI355X
 //   PoseOptimization                                           MI355X
-//   OptimizeEssentialGraph / OptimizeSim3                      CPU: the reference's own g2o code (loop closing; out of the hot path)
+//   OptimizeEssentialGraph                                     CPU: the reference's own g2o code (loop closing; out of the hot path)
+//   OptimizeSim3                                               CPU by default; MI355X (OptimizerHip::OptimizeSim3) with QSP_SHIM_SIM3_HIP=1
 //   Optimizer(), SetGroundPlane, nBAdone                       as src/Optimizer.cc:41-44, src/Optimizer_util.cc:34,773-776
 //
 // The reference's two source files are compiled INTO this unit, unchanged, under the class name OptimizerG2O (they stay on
@@ -132,7 +133,7 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
     return qsp_shim::allow_g2o_fallback() ? OptimizerG2O::PoseOptimization(pFrame) : 0;   // 0 inliers: Tracking sees a lost frame
 }
 
-// ---- loop closing: CPU pass-through to the reference's g2o code -----------------------------
+// ---- loop closing: CPU pass-through to the reference's g2o code; OptimizeSim3 on request --------
 void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
                                        const KeyFrameAndPose& CorrectedSim3,
                                        const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool& bFixScale) {
@@ -141,6 +142,15 @@ void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* p
 
 int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12,
                             const float th2, const bool bFixScale) {
+// (compiled out against tests/shim_mock, whose KeyFrame / MapPoint stand-ins lack mK, GetRotation, GetTranslation, GetIndexInKeyFrame)
+#if !defined(QSP_SHIM_MOCK_TYPES) || defined(QSP_SHIM_MOCK_SIM3)
+    if (qsp_shim::sim3_on_gpu()) {                       // opt-in: QSP_SHIM_SIM3_HIP=1
+        int status = QSP_OK;
+        const int nInliers = OptimizerHip::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, &status);
+        if (status == QSP_OK) return nInliers;
+        if (!qsp_shim::allow_g2o_fallback()) return 0;   // matches and g2oS12 untouched: ComputeSim3 drops the candidate
+    }
+#endif
     return OptimizerG2O::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale);
 }
 
