@@ -695,6 +695,33 @@ int qsp_sim3_optimize_batch(int device, int32_t n_cand, const int32_t* match_off
                             const double* info1, const double* info2, double th2, int32_t fix_scale, double* sim3_out,
                             uint8_t* inlier, int32_t* n_inliers, qsp_sim3_trace* trace);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Essential-graph optimisation: Optimizer::OptimizeEssentialGraph, src/Optimizer.cc:785-1048, from initializeOptimization() to
+ * the corrected map points.  n_kf VertexSim3Expmap in hessian order (ascending key-frame id), n_edge EdgeSim3 in insertion
+ * order with error log(meas * S[v0] * S[v1]^-1), identity information, no robust kernel, g2o's numeric Jacobians (central
+ * differences through the vertex's oplus, delta 1e-9), g2o's Levenberg-Marquardt over a dense FP64 Cholesky of the
+ * 7 n_free (fix_scale: 6 n_free, the scale rows carry nothing) unknowns, optimize(n_iter) (reference: 20), then
+ * pt_out[p] = S_out[r]^-1.map(S_in[r].map(pt_in[p])), r = pt_ref[p].
+ *   sim3_in / sim3_out (n_kf,8) tx ty tz qx qy qz qw s; fixed (n_kf) 1 = the vertex does not move (reference: the loop key frame)
+ *   edge_v0, edge_v1 (n_edge) vertex indices (setVertex(0,.), setVertex(1,.)); meas (n_edge,8); duplicate edges all count
+ *   lambda_init > 0: LM's first lambda (reference: 1e-16); <= 0: g2o's 1e-5 max |H_jj|, which is what computeLambdaInit() does
+ *   when no user value is set (optimization_algorithm_levenberg.cpp:166-180) -- the same function, not an extension
+ *   n_pt, pt_in / pt_out (n_pt,3), pt_ref (n_pt) vertex indices; n_pt == 0 with NULL point arrays is valid
+ *   trace out or NULL: iterations run and, for the first 32, chi2, lambda, trials and whether the last trial was accepted.
+ * No floating-point atomics: two calls on the same input return the same bits.  Host pointers.  n_kf == 0 is QSP_OK and touches
+ * nothing; n_edge == 0 or no free vertex returns the input.  Null pointers, negative counts, indices out of range, edge_v0 ==
+ * edge_v1, n_iter < 0: QSP_ERR_INVALID.  More than 10208 unknowns (or 2^30 edges, or a graph the host cannot stage): QSP_ERR_UNSUPPORTED before anything is enqueued.  No output
+ * is written unless the call returns QSP_OK. */
+typedef struct {
+    int32_t iters;             /* LM iterations run                                                           */
+    int32_t reserved;
+    double trace[32][4];       /* chi2, lambda, trials, last trial accepted (0/1) after each iteration         */
+} qsp_essential_trace;
+int qsp_essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge,
+                                 const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale,
+                                 int32_t n_iter, double lambda_init, int32_t n_pt, const double* pt_in, const int32_t* pt_ref,
+                                 double* sim3_out, double* pt_out, qsp_essential_trace* trace);
+
 #ifdef __cplusplus
 }
 #endif

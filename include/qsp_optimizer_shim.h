@@ -11,7 +11,8 @@
 // Usage in the reference tree: NOTHING changes at the call sites.  qsp_slam_amd/orbslam/Optimizer_hip.cc (this repository)
 // takes the place of src/Optimizer.cc + src/Optimizer_util.cc in the CMake source list and defines the members of
 // `class Optimizer` exactly as include/Optimizer.h:75-107 declares them, forwarding the bundle adjustments and
-// PoseOptimization to OptimizerHip below, OptimizeEssentialGraph to the reference's own g2o code, OptimizeSim3 to it as well
+// PoseOptimization to OptimizerHip below, OptimizeEssentialGraph to the reference's own g2o code unless
+// QSP_SHIM_ESSENTIAL_HIP=1 asks for OptimizerHip::OptimizeEssentialGraph, OptimizeSim3 to it as well
 // unless QSP_SHIM_SIM3_HIP=1 asks for OptimizerHip::OptimizeSim3, and any call
 // the GPU path reports an error for to that g2o code as well.  OptimizerHip's entry points
 // return a qsp status (QSP_OK / QSP_ERR_*) instead of void so that the caller can tell; on error the map is left exactly as
@@ -19,6 +20,7 @@
 #ifndef QSP_OPTIMIZER_SHIM_H
 #define QSP_OPTIMIZER_SHIM_H
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cmath>
@@ -108,7 +110,8 @@ struct Marks {
 //   QSP_SHIM_ALLOW_G2O_FALLBACK=1   hand the failed call to the reference's own g2o code compiled into the drop-in (counted in
 //                                   `fallback_count()`, one stderr line per call);
 //   QSP_SHIM_NO_FALLBACK=1          strictest: std::abort() after the message.
-// OptimizeEssentialGraph is a CPU pass-through by design and is not affected; OptimizeSim3 is one by
+// OptimizeEssentialGraph is a CPU pass-through by default and follows the table above where QSP_SHIM_ESSENTIAL_HIP=1 routes it to
+// the library (the map untouched on a failed call); OptimizeSim3 is one by
 // default and follows the table above where QSP_SHIM_SIM3_HIP=1 routes it to the library (0 inliers, matches and g2oS12 untouched).
 inline std::atomic<long>& failure_counter() {
     static std::atomic<long> n{0};
@@ -330,6 +333,59 @@ struct Sim3Flat {
             index.back().push_back((size_t)i);
         }
         off.push_back((int32_t)o1.size() / 2);
+    }
+};
+
+
+// ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:785-1048) -----------------------------------------------------------
+// The drop-in sends OptimizeEssentialGraph to the library only where the deployment asked for it; the default stays g2o.
+inline bool essential_on_gpu() {
+    const char* e = std::getenv("QSP_SHIM_ESSENTIAL_HIP");
+    return e && *e == '1';
+}
+
+// g2o::Sim3 products on (tx ty tz qx qy qz qw s), Eigen's quaternion formulas (sim3.h operator*, inverse)
+inline void s8_rot(const double* q, const double* v, double* o) {
+    double ux = q[1] * v[2] - q[2] * v[1], uy = q[2] * v[0] - q[0] * v[2], uz = q[0] * v[1] - q[1] * v[0];
+    ux += ux; uy += uy; uz += uz;
+    o[0] = (v[0] + q[3] * ux) + (q[1] * uz - q[2] * uy);
+    o[1] = (v[1] + q[3] * uy) + (q[2] * ux - q[0] * uz);
+    o[2] = (v[2] + q[3] * uz) + (q[0] * uy - q[1] * ux);
+}
+inline void s8_mul(const double* a, const double* b, double* c) {
+    double rt[3];
+    s8_rot(a + 3, b, rt);
+    const double *p = a + 3, *q = b + 3;
+    const double r[4] = {p[3] * q[0] + p[0] * q[3] + p[1] * q[2] - p[2] * q[1], p[3] * q[1] + p[1] * q[3] + p[2] * q[0] - p[0] * q[2],
+                         p[3] * q[2] + p[2] * q[3] + p[0] * q[1] - p[1] * q[0], p[3] * q[3] - p[0] * q[0] - p[1] * q[1] - p[2] * q[2]};
+    for (int i = 0; i < 3; ++i) c[i] = a[7] * rt[i] + a[i];
+    for (int i = 0; i < 4; ++i) c[3 + i] = r[i];
+    c[7] = a[7] * b[7];
+}
+inline void s8_inv(const double* a, double* c) {
+    const double qc[4] = {-a[3], -a[4], -a[5], a[6]}, f = -1.0 / a[7];
+    const double v[3] = {f * a[0], f * a[1], f * a[2]};
+    s8_rot(qc, v, c);
+    for (int i = 0; i < 4; ++i) c[3 + i] = qc[i];
+    c[7] = 1.0 / a[7];
+}
+
+// The essential graph, flattened: vertices in hessian order (ascending key-frame id), edges in the reference's insertion order
+struct EssentialFlat {
+    std::vector<double> S, meas;                     // vScw per vertex, the measurement per edge
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> v0, v1;
+    std::map<unsigned long, int> vertex;             // mnId -> vertex index; a bad key frame has none
+
+    const double* scw(unsigned long id) const { return &S[8 * (size_t)vertex.find(id)->second]; }
+    bool has(unsigned long id) const { return vertex.count(id) != 0; }
+    // e->setVertex(0, i), e->setVertex(1, j), e->setMeasurement(Sjw * Swi); dropped where g2o's addEdge would refuse it (no vertex)
+    void add_edge(unsigned long i, unsigned long j, const double* Sjw, const double* Swi) {
+        if (!has(i) || !has(j)) return;
+        double Z[8];
+        s8_mul(Sjw, Swi, Z);
+        v0.push_back(vertex[i]); v1.push_back(vertex[j]);
+        meas.insert(meas.end(), Z, Z + 8);
     }
 };
 
@@ -623,6 +679,136 @@ public:
         vpMatches1 = m[0];
         g2oS12 = s[0];
         return n[0];
+    }
+
+    // Optimizer::OptimizeEssentialGraph, src/Optimizer.cc:785-1048: the graph walk of :812-987, ONE library call
+    // (qsp_essential_graph_optimize: optimize(20) from lambda 1e-16 and the point correction), the write-back of :993-1047 under
+    // mMutexMapUpdate.  Templates on the caller's pose map (KeyFrameAndPose) and connection map.  Where the reference would hand
+    // g2o a NULL vertex (an endpoint that is a bad key frame: addEdge refuses the edge) the edge is left out; bad key frames and
+    // bad points are skipped in the write-back, and so is a point whose reference key frame has no vertex.  A key frame outside
+    // CorrectedSim3 enters as Sim3(Rcw, tcw, 1) with the quaternion of pose7_from_rt (normalised; g2o::Sim3(R, t, s) does not
+    // normalise the float rotation's quaternion).  Returns the qsp status; on error the map has not been touched.
+    template <typename MapT, typename KF, typename PoseMap, typename ConnMap>
+    static int OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const PoseMap& NonCorrectedSim3, const PoseMap& CorrectedSim3,
+                                      const ConnMap& LoopConnections, const bool& bFixScale) {
+        using namespace qsp_shim;
+        const std::vector<KF*> vpKFs = pMap->GetAllKeyFrames();
+        const auto vpMPs = pMap->GetAllMapPoints();
+        const int minFeat = 100;
+        // ---- vertices (:812-848), in hessian order ------------------------------------------------------------------------------
+        std::vector<KF*> order;
+        for (KF* pKF : vpKFs)
+            if (!pKF->isBad()) order.push_back(pKF);
+        std::sort(order.begin(), order.end(), [](KF* a, KF* b) { return a->mnId < b->mnId; });
+        EssentialFlat F;
+        for (KF* pKF : order) {
+            double s8[8];
+            typename PoseMap::const_iterator it = CorrectedSim3.find(pKF);
+            if (it != CorrectedSim3.end()) {
+                sim3_to8(it->second, s8);
+            } else {
+                const cv::Mat Tcw = pKF->GetPose();
+                pose7_from_rt([&](int r, int c) { return (double)Tcw.template at<float>(r, c); }, s8);
+                s8[7] = 1.0;
+            }
+            F.vertex[pKF->mnId] = (int)F.fixed.size();
+            F.S.insert(F.S.end(), s8, s8 + 8);
+            F.fixed.push_back(pKF == pLoopKF ? 1 : 0);
+        }
+        // ---- loop edges (:856-884) ------------------------------------------------------------------------------------------
+        std::set<std::pair<long unsigned int, long unsigned int>> sInsertedEdges;
+        for (typename ConnMap::const_iterator mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {
+            KF* pKF = mit->first;
+            const long unsigned int nIDi = pKF->mnId;
+            if (!F.has(nIDi)) continue;
+            double Swi[8];
+            s8_inv(F.scw(nIDi), Swi);
+            for (KF* pKFj : mit->second) {
+                const long unsigned int nIDj = pKFj->mnId;
+                if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat) continue;
+                if (!F.has(nIDj)) continue;
+                F.add_edge(nIDi, nIDj, F.scw(nIDj), Swi);
+                sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+            }
+        }
+        // ---- normal edges (:887-987): measurements from the NON-corrected poses where there are any ------------------------------
+        auto pose_of = [&](KF* k, double* out) {                   // NonCorrectedSim3[k], else vScw[k]; false: no vertex
+            typename PoseMap::const_iterator it = NonCorrectedSim3.find(k);
+            if (it != NonCorrectedSim3.end()) { sim3_to8(it->second, out); return true; }
+            if (!F.has(k->mnId)) return false;
+            for (int i = 0; i < 8; ++i) out[i] = F.scw(k->mnId)[i];
+            return true;
+        };
+        for (KF* pKF : vpKFs) {
+            if (!F.has(pKF->mnId)) continue;
+            double Siw[8], Swi[8], Sjw[8];
+            pose_of(pKF, Siw);
+            s8_inv(Siw, Swi);
+            KF* pParentKF = pKF->GetParent();
+            if (pParentKF && pose_of(pParentKF, Sjw)) F.add_edge(pKF->mnId, pParentKF->mnId, Sjw, Swi);       // spanning tree
+            const std::set<KF*> sLoopEdges = pKF->GetLoopEdges();
+            for (KF* pLKF : sLoopEdges)
+                if (pLKF->mnId < pKF->mnId && pose_of(pLKF, Sjw)) F.add_edge(pKF->mnId, pLKF->mnId, Sjw, Swi);
+            const std::vector<KF*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+            for (KF* pKFn : vpConnectedKFs) {
+                if (!pKFn || pKFn == pParentKF || pKF->hasChild(pKFn) || sLoopEdges.count(pKFn)) continue;
+                if (pKFn->isBad() || !(pKFn->mnId < pKF->mnId)) continue;
+                if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                if (pose_of(pKFn, Sjw)) F.add_edge(pKF->mnId, pKFn->mnId, Sjw, Swi);
+            }
+        }
+        // ---- points: position and reference key frame (:1017-1040) -----------------------------------------------------------
+        std::vector<double> P;
+        std::vector<int32_t> ref;
+        std::vector<size_t> which;
+        for (size_t i = 0; i < vpMPs.size(); ++i) {
+            auto pMP = vpMPs[i];
+            if (pMP->isBad()) continue;
+            long unsigned int nIDr;
+            if (pMP->mnCorrectedByKF == pCurKF->mnId) {
+                nIDr = pMP->mnCorrectedReference;
+            } else {
+                KF* pRefKF = pMP->GetReferenceKeyFrame();
+                if (!pRefKF) continue;
+                nIDr = pRefKF->mnId;
+            }
+            if (!F.has(nIDr)) continue;
+            const cv::Mat X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; ++r) P.push_back((double)X.template at<float>(r));
+            ref.push_back(F.vertex[nIDr]);
+            which.push_back(i);
+        }
+        // ---- optimizer.optimize(20), setUserLambdaInit(1e-16) ------------------------------------------------------------------
+        const size_t nk = F.fixed.size(), np = which.size();
+        std::vector<double> Sout(8 * nk + 8), Pout(3 * np + 3);
+        const int rc = report("qsp_essential_graph_optimize",
+                              qsp_essential_graph_optimize(device(), (int32_t)nk, F.S.data(), F.fixed.data(), (int32_t)F.v0.size(), F.v0.data(),
+                                                           F.v1.data(), F.meas.data(), bFixScale ? 1 : 0, 20, 1e-16, (int32_t)np,
+                                                           np ? P.data() : nullptr, np ? ref.data() : nullptr, Sout.data(),
+                                                           np ? Pout.data() : nullptr, nullptr));
+        if (rc != QSP_OK) return rc;
+        // ---- write-back (:993-1047): Sim3 [sR t; 0 1] -> SE3 [R t/s; 0 1] ----------------------------------------------------------
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+        for (KF* pKFi : vpKFs) {
+            if (!F.has(pKFi->mnId)) continue;
+            const double* c = &Sout[8 * (size_t)F.vertex[pKFi->mnId]];
+            const double is = 1. / c[7];
+            const double p7[7] = {c[0] * is, c[1] * is, c[2] * is, c[3], c[4], c[5], c[6]};
+            float T[16];
+            pose7_to_mat(p7, T);
+            cv::Mat Tiw(4, 4, CV_32F);
+            for (int r = 0; r < 4; ++r)
+                for (int q = 0; q < 4; ++q) Tiw.template at<float>(r, q) = T[4 * r + q];
+            pKFi->SetPose(Tiw);
+        }
+        for (size_t e = 0; e < np; ++e) {
+            auto pMP = vpMPs[which[e]];
+            cv::Mat X(3, 1, CV_32F);
+            for (int r = 0; r < 3; ++r) X.template at<float>(r) = (float)Pout[3 * e + r];
+            pMP->SetWorldPos(X);
+            pMP->UpdateNormalAndDepth();
+        }
+        return QSP_OK;
     }
 
     // src/Optimizer.cc:54-242

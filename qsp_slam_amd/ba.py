@@ -253,3 +253,34 @@ def optimize_sim3_batch(candidates, th2, fix_scale, device=0, trace=False):
 def optimize_sim3(candidate, th2, fix_scale, device=0, trace=False):
     """the batch of one"""
     return optimize_sim3_batch([candidate], th2, fix_scale, device=device, trace=trace)[0]
+
+
+def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
+                             device=0):
+    """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map
+    points, on the device (qsp_essential_graph_optimize, include/qsp_hip.h).  sim3 (n_kf,8) tx ty tz qx qy qz qw s in hessian
+    order; fixed (n_kf,) 1 = the vertex stays; edge_v0, edge_v1 (n_edge,) vertex indices and meas (n_edge,8) of the EdgeSim3 in
+    insertion order; pts (n_pt,3) with pt_ref (n_pt,) the vertex index of each point's reference key frame, or None.
+    Returns dict(sim3 (n_kf,8), pts (n_pt,3), iters, trace (iters,4): chi2, lambda, trials, last trial accepted)."""
+    S0 = _arr(np.reshape(sim3, (-1, 8)), np.float64)
+    n_kf = int(np.size(sim3)) // 8
+    fx = _arr(np.reshape(fixed, -1), np.uint8)
+    v0, v1 = _arr(np.reshape(edge_v0, -1), np.int32), _arr(np.reshape(edge_v1, -1), np.int32)
+    n_edge = int(np.size(edge_v0))
+    Z = _arr(np.reshape(meas, (-1, 8)), np.float64)
+    if int(np.size(fixed)) != n_kf or int(np.size(edge_v1)) != n_edge or int(np.size(meas)) != 8 * n_edge:
+        raise ValueError("essential_graph_optimize: array lengths do not agree")
+    n_pt = 0 if pts is None else int(np.size(pts)) // 3
+    if n_pt and (pt_ref is None or int(np.size(pt_ref)) != n_pt):
+        raise ValueError("essential_graph_optimize: pt_ref must name one reference key frame per point")
+    P = _arr(np.reshape(pts, (-1, 3)), np.float64) if n_pt else None
+    R = _arr(np.reshape(pt_ref, -1), np.int32) if n_pt else None
+    out, pout = np.zeros((n_kf, 8)), np.zeros((n_pt, 3))
+    tr = _lib.EssentialTrace()
+    _lib.check(_lib.lib().qsp_essential_graph_optimize(
+        int(device), n_kf, _lib.dptr(S0), _lib.u8ptr(fx), n_edge, _lib.i32ptr(v0), _lib.i32ptr(v1), _lib.dptr(Z), 1 if fix_scale else 0,
+        int(n_iter), float(lambda_init), n_pt, _lib.dptr(P) if n_pt else None, _lib.i32ptr(R) if n_pt else None, _lib.dptr(out),
+        _lib.dptr(pout) if n_pt else None, C.byref(tr)))
+    iters = int(tr.iters)
+    trace = np.array(tr.trace[:], np.float64).reshape(32, 4)[:min(iters, 32)]
+    return dict(sim3=out, pts=pout, iters=iters, trace=trace)

@@ -4273,6 +4273,7 @@ extern "C" int qsp_ba_set_deterministic(qsp_ba_problem* p, int on) {
 
 #include "ellipsoid_fit.hpp"
 #include "sim3_opt.hpp"
+#include "essential_graph.hpp"
 
 #ifdef QSP_CB_STAMPS
 extern "C" int qsp_debug_chain_stamps(unsigned long long* out) {

@@ -8,6 +8,11 @@ std::string& last_error_ref() {
     static thread_local std::string e;
     return e;
 }
+// csrc/essential_graph.hpp (compiled with the solver's kernels in ba_solver.hip)
+int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
+                             const int32_t* edge_v1, const double* meas, int32_t fix_scale, int32_t n_iter, double lambda_init,
+                             int32_t n_pt, const double* pt_in, const int32_t* pt_ref, double* sim3_out, double* pt_out,
+                             qsp_essential_trace* trace);
 }  // namespace qsp
 
 extern "C" const char* qsp_last_error(void) { return qsp::last_error_ref().c_str(); }
@@ -16,4 +21,11 @@ extern "C" int qsp_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+extern "C" int qsp_essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge,
+                                            const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale,
+                                            int32_t n_iter, double lambda_init, int32_t n_pt, const double* pt_in,
+                                            const int32_t* pt_ref, double* sim3_out, double* pt_out, qsp_essential_trace* trace) {
+    return qsp::essential_graph_optimize(device, n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, n_iter, lambda_init,
+                                         n_pt, pt_in, pt_ref, sim3_out, pt_out, trace);
 }

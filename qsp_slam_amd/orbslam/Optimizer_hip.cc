@@ -9,7 +9,7 @@
 //   JointBundleAdjustment / GlobalJointBundleAdjustemnt        MI355X
 //   LocalBundleAdjustment / LocalJointBundleAdjustment         MI355X
 //   PoseOptimization                                           MI355X
-//   OptimizeEssentialGraph                                     CPU: the reference's own g2o code (loop closing; out of the hot path)
+//   OptimizeEssentialGraph                                     CPU by default; MI355X (OptimizerHip::OptimizeEssentialGraph) with QSP_SHIM_ESSENTIAL_HIP=1
 //   OptimizeSim3                                               CPU by default; MI355X (OptimizerHip::OptimizeSim3) with QSP_SHIM_SIM3_HIP=1
 //   Optimizer(), SetGroundPlane, nBAdone                       as src/Optimizer.cc:41-44, src/Optimizer_util.cc:34,773-776
 //
@@ -133,10 +133,17 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
     return qsp_shim::allow_g2o_fallback() ? OptimizerG2O::PoseOptimization(pFrame) : 0;   // 0 inliers: Tracking sees a lost frame
 }
 
-// ---- loop closing: CPU pass-through to the reference's g2o code; OptimizeSim3 on request --------
+// ---- loop closing: CPU pass-through to the reference's g2o code by default; the library on request ------------------------------
 void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
                                        const KeyFrameAndPose& CorrectedSim3,
                                        const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool& bFixScale) {
+// (compiled out against stand-in map types that lack GetParent, GetLoopEdges, GetCovisiblesByWeight, GetWeight, mnCorrectedByKF)
+#if !defined(QSP_SHIM_MOCK_TYPES) || defined(QSP_SHIM_MOCK_ESSENTIAL)
+    if (qsp_shim::essential_on_gpu()) {                  // opt-in: QSP_SHIM_ESSENTIAL_HIP=1
+        const int rc = OptimizerHip::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale);
+        if (rc == QSP_OK || !qsp_shim::allow_g2o_fallback()) return;      // a failed call has left the map untouched
+    }
+#endif
     OptimizerG2O::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale);
 }
 
