@@ -722,6 +722,26 @@ int qsp_essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in
                                  int32_t n_iter, double lambda_init, int32_t n_pt, const double* pt_in, const int32_t* pt_ref,
                                  double* sim3_out, double* pt_out, qsp_essential_trace* trace);
 
+/* A read-only window on one linearisation and one trial of qsp_essential_graph_optimize, for tests; nothing in the drop-in calls
+ * it.  Same graph arguments (no points) and one lambda > 0.  It runs once what the optimise loop runs per iteration (errors,
+ * numeric Jacobians, assembly, reductions) and per trial (damping, factorisation, back-substitution, update, errors at the trial
+ * states, reductions) -- the same kernels, grids and buffers, through the same host code -- and copies the buffers down:
+ *   E (n_edge,7), chi (n_edge)   the errors and their squared norms at sim3_in
+ *   J (n_edge,2,7,7)             [edge][side][direction][error row]; the side of a fixed vertex, which the device never writes,
+ *                                is reported as zeros
+ *   H (dim,dim), b (dim)         dim = (fix_scale ? 6 : 7) * number of free vertices, row-major without the padding of the
+ *                                factorisation's 64-wide blocks
+ *   x (dim)                      the solution of (H + lambda I) x = b
+ *   sim3_trial (n_kf,8)          exp(x) * sim3_in; fixed vertices are copies
+ *   info (7)                     after the linearisation: chi2, max |H_jj|; after the trial: chi2 at sim3_trial, computeScale(),
+ *                                the factorisation's failure flag (0 = it succeeded), as the device wrote them; then dim and nb
+ *                                (the number of 64-wide blocks)
+ * Refusals as for qsp_essential_graph_optimize; also QSP_ERR_INVALID for a null output, a lambda that is not positive and
+ * finite, n_edge == 0 and no free vertex (nothing to show).  No output is written unless the call returns QSP_OK. */
+int qsp_essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge,
+                               const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale, double lambda,
+                               double* E, double* chi, double* J, double* H, double* b, double* x, double* sim3_trial, double* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,3 +284,26 @@ def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_i
     iters = int(tr.iters)
     trace = np.array(tr.trace[:], np.float64).reshape(32, 4)[:min(iters, 32)]
     return dict(sim3=out, pts=pout, iters=iters, trace=trace)
+
+
+def essential_graph_stages(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, lam, device=0):
+    """One linearisation and one trial of essential_graph_optimize at `sim3` and the damping `lam`, every device buffer copied down
+    (qsp_essential_graph_stages, include/qsp_hip.h): a window for tests.  Returns dict(E (n_edge,7), chi (n_edge,), J (n_edge,2,7,7)
+    [edge][side][direction][error row], H (dim,dim), b (dim,), x (dim,), sim3_trial (n_kf,8), chi2, max_diag, chi2_trial, scale,
+    failed, dim, nb)."""
+    S0 = _arr(np.reshape(sim3, (-1, 8)), np.float64)
+    n_kf = int(np.size(sim3)) // 8
+    fx = _arr(np.reshape(fixed, -1), np.uint8)
+    v0, v1 = _arr(np.reshape(edge_v0, -1), np.int32), _arr(np.reshape(edge_v1, -1), np.int32)
+    n_edge = int(np.size(edge_v0))
+    Z = _arr(np.reshape(meas, (-1, 8)), np.float64)
+    if int(np.size(fixed)) != n_kf or int(np.size(edge_v1)) != n_edge or int(np.size(meas)) != 8 * n_edge:
+        raise ValueError("essential_graph_stages: array lengths do not agree")
+    dim = (6 if fix_scale else 7) * int(np.count_nonzero(fx == 0))
+    E, chi, J = np.zeros((n_edge, 7)), np.zeros(n_edge), np.zeros((n_edge, 2, 7, 7))
+    H, b, x, St, info = np.zeros((dim, dim)), np.zeros(dim), np.zeros(dim), np.zeros((n_kf, 8)), np.zeros(7)
+    _lib.check(_lib.lib().qsp_essential_graph_stages(
+        int(device), n_kf, _lib.dptr(S0), _lib.u8ptr(fx), n_edge, _lib.i32ptr(v0), _lib.i32ptr(v1), _lib.dptr(Z), 1 if fix_scale else 0,
+        float(lam), *[_lib.dptr(a) for a in (E, chi, J, H, b, x, St, info)]))
+    return dict(E=E, chi=chi, J=J, H=H, b=b, x=x, sim3_trial=St, chi2=float(info[0]), max_diag=float(info[1]), chi2_trial=float(info[2]),
+                scale=float(info[3]), failed=float(info[4]), dim=int(info[5]), nb=int(info[6]))

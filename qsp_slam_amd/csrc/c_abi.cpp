@@ -13,6 +13,9 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
                              const int32_t* edge_v1, const double* meas, int32_t fix_scale, int32_t n_iter, double lambda_init,
                              int32_t n_pt, const double* pt_in, const int32_t* pt_ref, double* sim3_out, double* pt_out,
                              qsp_essential_trace* trace);
+int essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
+                           const int32_t* edge_v1, const double* meas, int32_t fix_scale, double lambda, double* E, double* chi, double* J,
+                           double* H, double* b, double* x, double* sim3_trial, double* info);
 }  // namespace qsp
 
 extern "C" const char* qsp_last_error(void) { return qsp::last_error_ref().c_str(); }
@@ -28,4 +31,11 @@ extern "C" int qsp_essential_graph_optimize(int device, int32_t n_kf, const doub
                                             const int32_t* pt_ref, double* sim3_out, double* pt_out, qsp_essential_trace* trace) {
     return qsp::essential_graph_optimize(device, n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, n_iter, lambda_init,
                                          n_pt, pt_in, pt_ref, sim3_out, pt_out, trace);
+}
+extern "C" int qsp_essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge,
+                                          const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale,
+                                          double lambda, double* E, double* chi, double* J, double* H, double* b, double* x,
+                                          double* sim3_trial, double* info) {
+    return qsp::essential_graph_stages(device, n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, lambda, E, chi, J, H, b, x,
+                                       sim3_trial, info);
 }

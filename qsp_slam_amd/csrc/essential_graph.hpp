@@ -343,6 +343,134 @@ inline int validate(int32_t n_kf, const double* sim3_in, const uint8_t* fixed, i
     return QSP_OK;
 }
 
+// The device side of one call: the set-up that qsp_essential_graph_optimize and qsp_essential_graph_stages share, and the two
+// steps the Levenberg-Marquardt loop is made of.  Device block: [S0 | Z | P | ints] (one upload from one staging buffer)
+// [Sa Sb E chi J b bs y x scal Pout Winv H A Uf]; it goes back to the buffer cache when the call ends.
+struct Run {
+    int device = 0, n_kf = 0, n_edge = 0, n_free = 0, n_pt = 0, D = 7, dim = 0, dimp = 0, nb = 0, chol_lds = 0;
+    size_t mat = 0, cache_bytes = 0;
+    char* d = nullptr;
+    Graph g;
+    double *S0 = nullptr, *Sa = nullptr, *Sb = nullptr, *P = nullptr, *Po = nullptr, *H = nullptr, *A = nullptr, *Uf = nullptr, *W = nullptr,
+           *bv = nullptr, *bs = nullptr, *y = nullptr, *x = nullptr, *scal = nullptr;
+    const int32_t* ref = nullptr;
+    Run() = default;
+    Run(const Run&) = delete;
+    Run& operator=(const Run&) = delete;
+    ~Run() { if (d && !buf_cache_put(g_dev_cache, device, d, cache_bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
+
+    // a validated graph with n_edge > 0 and n_free > 0: device, layout, host side of the graph, upload; Sa = S0
+    int setup(int device_, int32_t n_kf_, const double* sim3_in, const uint8_t* fixed, int n_free_, int32_t n_edge_, const int32_t* edge_v0,
+              const int32_t* edge_v1, const double* meas, int32_t fix_scale, int32_t n_pt_, const double* pt_in, const int32_t* pt_ref) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
+        if (device_ < 0 || device_ >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_optimize: device out of range");
+        QSP_HIP(hipSetDevice(device_));
+        device = device_; n_kf = n_kf_; n_edge = n_edge_; n_free = n_free_; n_pt = n_pt_;
+        constexpr int NB = ba::NB;
+        D = fix_scale ? 6 : 7; dim = D * n_free; dimp = (dim + NB - 1) / NB * NB; nb = dimp / NB;
+        const size_t nk = (size_t)n_kf, ne = (size_t)n_edge, np = (size_t)n_pt;
+        mat = (size_t)dimp * dimp;
+        const size_t i_v0 = 0, i_v1 = ne, i_slot = 2 * ne, i_free = i_slot + nk, i_off = i_free + (size_t)n_free, i_inc = i_off + nk + 1,
+                     i_ref = i_inc + 2 * ne, n_int = i_ref + np;
+        size_t at = 0;
+        auto take = [&](size_t n) { const size_t o = at; at += (n + 1) & ~(size_t)1; return o; };
+        const size_t oS0 = take(8 * nk), oZ = take(8 * ne), oP = take(3 * np), oI = take((n_int + 1) / 2), n_up = at;
+        const size_t oSa = take(8 * nk), oSb = take(8 * nk), oE = take(7 * ne), oChi = take(ne), oJ = take(98 * ne), oB = take(dimp),
+                     oBs = take(dimp), oY = take(dimp), oX = take(dimp), oScal = take(8), oPo = take(3 * np),
+                     oW = take((size_t)nb * NB * NB), oH = take(mat), oA = take(mat), oUf = take(mat);
+        const size_t bytes = (sizeof(double) * at + 255) & ~(size_t)255;
+        std::vector<double> hd;                                    // (no exception may leave an extern "C" function)
+        try {
+            hd.assign(n_up, 0.0);
+            // host side of the graph: free list, slots, CSR of incident edges in insertion order
+            int32_t* hi = (int32_t*)(hd.data() + oI);
+            memcpy(hi + i_v0, edge_v0, sizeof(int32_t) * ne);
+            memcpy(hi + i_v1, edge_v1, sizeof(int32_t) * ne);
+            for (int v = 0, f = 0; v < n_kf; ++v) {
+                hi[i_slot + v] = fixed[v] ? -1 : f;
+                if (!fixed[v]) hi[i_free + f++] = v;
+            }
+            int32_t* off = hi + i_off;
+            for (size_t k = 0; k < ne; ++k) { off[edge_v0[k] + 1]++; off[edge_v1[k] + 1]++; }
+            for (size_t v = 0; v < nk; ++v) off[v + 1] += off[v];
+            std::vector<int32_t> cur(off, off + nk);
+            for (size_t k = 0; k < ne; ++k) {
+                hi[i_inc + cur[edge_v0[k]]++] = (int32_t)(k << 1);
+                hi[i_inc + cur[edge_v1[k]]++] = (int32_t)(k << 1) | 1;
+            }
+            if (np) memcpy(hi + i_ref, pt_ref, sizeof(int32_t) * np);
+        } catch (const std::exception&) {
+            return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_essential_graph_optimize: out of host memory for a graph of this size");
+        }
+        memcpy(&hd[oS0], sim3_in, sizeof(double) * 8 * nk);
+        memcpy(&hd[oZ], meas, sizeof(double) * 8 * ne);
+        if (np) memcpy(&hd[oP], pt_in, sizeof(double) * 3 * np);
+        size_t got = bytes;
+        char* q = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
+        if (!q) QSP_HIP(hipMalloc((void**)&q, bytes));
+        d = q;
+        cache_bytes = got;
+        double* dd = (double*)d;
+        const int32_t* di = (const int32_t*)(dd + oI);
+        QSP_HIP(hipMemcpy(dd, hd.data(), sizeof(double) * n_up, hipMemcpyHostToDevice));
+        QSP_HIP(hipMemcpy(dd + oSa, dd + oS0, sizeof(double) * 8 * nk, hipMemcpyDeviceToDevice));
+        chol_lds = (int)(sizeof(double) * ba::CHOL_LDS_DOUBLES);
+        {   // the factorisation kernels' LDS size: once per device and process
+            static std::mutex mu;
+            static bool done[64];
+            std::lock_guard<std::mutex> lk(mu);
+            if (!done[device & 63]) {
+                QSP_HIP(hipFuncSetAttribute((const void*)ba::k_chol_first, hipFuncAttributeMaxDynamicSharedMemorySize, chol_lds));
+                QSP_HIP(hipFuncSetAttribute((const void*)ba::k_chol_step, hipFuncAttributeMaxDynamicSharedMemorySize, chol_lds));
+                done[device & 63] = true;
+            }
+        }
+        g.n_kf = n_kf; g.n_edge = n_edge; g.n_free = n_free; g.D = D; g.fix_scale = fix_scale ? 1 : 0; g.ld = dimp;
+        g.v0 = di + i_v0; g.v1 = di + i_v1; g.slot = di + i_slot; g.free_v = di + i_free; g.inc_off = di + i_off; g.inc = di + i_inc;
+        g.Z = dd + oZ; g.E = dd + oE; g.chi = dd + oChi; g.J = dd + oJ;
+        S0 = dd + oS0; Sa = dd + oSa; Sb = dd + oSb; P = dd + oP; Po = dd + oPo; H = dd + oH; A = dd + oA; Uf = dd + oUf; W = dd + oW;
+        bv = dd + oB; bs = dd + oBs; y = dd + oY; x = dd + oX; scal = dd + oScal;
+        ref = di + i_ref;
+        return QSP_OK;
+    }
+
+    // computeActiveErrors, activeRobustChi2, buildSystem at S: E, chi, J, H, b; h[0] = chi2, h[2] = max |H_jj|
+    int linearise(const double* S, double* h) {
+        const dim3 ge((n_edge + 63) / 64), gl((n_edge + 1) / 2);
+        hipLaunchKernelGGL(k_eg_err, ge, dim3(64), 0, 0, g, S);
+        hipLaunchKernelGGL(k_eg_lin, gl, dim3(64), 0, 0, g, S);
+        QSP_HIP(hipMemsetAsync(H, 0, sizeof(double) * mat, 0));
+        QSP_HIP(hipMemsetAsync(scal, 0, sizeof(double) * 8, 0));
+        hipLaunchKernelGGL(k_eg_asm, dim3(n_free), dim3(64), 0, 0, g, H, bv);
+        hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(64), 0, 0, g, (const double*)nullptr, (const double*)nullptr, 0.0, (const double*)H, scal);
+        QSP_HIP(hipGetLastError());
+        QSP_HIP(hipMemcpy(h, scal, sizeof(double) * 4, hipMemcpyDeviceToHost));
+        return QSP_OK;
+    }
+
+    // one trial: (H + lambda I) x = b, St = exp(x) S, the errors at St (E and chi are overwritten); h[0] = chi2 at St,
+    // h[1] = computeScale(), h[3] != 0: the factorisation failed
+    int trial(const double* S, double* St, double lambda, double* h) {
+        const dim3 ge((n_edge + 63) / 64), gk((n_kf + 63) / 64);
+        const dim3 gd((unsigned)std::min<size_t>((mat + 255) / 256, 4096));
+        QSP_HIP(hipMemsetAsync(scal, 0, sizeof(double) * 8, 0));
+        hipLaunchKernelGGL(k_eg_damp, gd, dim3(256), 0, 0, (const double*)H, (const double*)bv, A, bs, dim, dimp, lambda);
+        hipLaunchKernelGGL(ba::k_chol_first, dim3(1), dim3(ba::CHOL_THREADS), (size_t)chol_lds, 0, (const double*)A, W, (const double*)bs, y, dimp,
+                           scal);
+        for (int k = 0; k + 1 < nb; ++k)
+            hipLaunchKernelGGL(ba::k_chol_step, dim3(nb - k - 1, nb - k - 1), dim3(ba::CHOL_THREADS), (size_t)chol_lds, 0, A, Uf, W, bs, y, dimp, k,
+                               scal);
+        hipLaunchKernelGGL(k_eg_back, dim3(1), dim3(1024), 0, 0, (const double*)Uf, (const double*)W, (const double*)y, x, dimp, nb);
+        hipLaunchKernelGGL(k_eg_update, gk, dim3(64), 0, 0, g, (const double*)x, (const double*)scal, S, St);
+        hipLaunchKernelGGL(k_eg_err, ge, dim3(64), 0, 0, g, (const double*)St);
+        hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(64), 0, 0, g, (const double*)x, (const double*)bv, lambda, (const double*)nullptr, scal);
+        QSP_HIP(hipGetLastError());
+        QSP_HIP(hipMemcpy(h, scal, sizeof(double) * 4, hipMemcpyDeviceToHost));
+        return QSP_OK;
+    }
+};
+
 }  // namespace eg
 
 int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
@@ -352,8 +480,7 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
     using namespace eg;
     if (n_kf == 0) return QSP_OK;
     int n_free = 0;
-    const int rc = validate(n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, n_iter, n_pt, pt_in, pt_ref, sim3_out, pt_out,
-                            &n_free);
+    int rc = validate(n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, n_iter, n_pt, pt_in, pt_ref, sim3_out, pt_out, &n_free);
     if (rc) return rc;
     qsp_essential_trace tr;
     memset(&tr, 0, sizeof(tr));
@@ -363,92 +490,20 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
         if (trace) *trace = tr;
         return QSP_OK;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_optimize: device out of range");
-    QSP_HIP(hipSetDevice(device));
-    constexpr int NB = ba::NB;
-    const int D = fix_scale ? 6 : 7, dim = D * n_free, dimp = (dim + NB - 1) / NB * NB, nb = dimp / NB;
-    const size_t nk = (size_t)n_kf, ne = (size_t)n_edge, np = (size_t)n_pt, mat = (size_t)dimp * dimp;
-    // device block: [S0 | Z | P | ints] (one upload from one staging buffer) [Sa Sb E chi J b bs y x scal Pout Winv H A Uf]
-    const size_t i_v0 = 0, i_v1 = ne, i_slot = 2 * ne, i_free = i_slot + nk, i_off = i_free + (size_t)n_free, i_inc = i_off + nk + 1,
-                 i_ref = i_inc + 2 * ne, n_int = i_ref + np;
-    size_t at = 0;
-    auto take = [&](size_t n) { const size_t o = at; at += (n + 1) & ~(size_t)1; return o; };
-    const size_t oS0 = take(8 * nk), oZ = take(8 * ne), oP = take(3 * np), oI = take((n_int + 1) / 2), n_up = at;
-    const size_t oSa = take(8 * nk), oSb = take(8 * nk), oE = take(7 * ne), oChi = take(ne), oJ = take(98 * ne), oB = take(dimp),
-                 oBs = take(dimp), oY = take(dimp), oX = take(dimp), oScal = take(8), oPo = take(3 * np),
-                 oW = take((size_t)nb * NB * NB), oH = take(mat), oA = take(mat), oUf = take(mat);
-    const size_t bytes = (sizeof(double) * at + 255) & ~(size_t)255;
-    std::vector<double> hd, down;                              // (no exception may leave an extern "C" function)
+    const size_t nk = (size_t)n_kf, np = (size_t)n_pt;
+    std::vector<double> down;                                  // (no exception may leave an extern "C" function)
     try {
-        hd.assign(n_up, 0.0);
         down.resize(8 * nk + 3 * np);
-        // host side of the graph: free list, slots, CSR of incident edges in insertion order
-        int32_t* hi = (int32_t*)(hd.data() + oI);
-        memcpy(hi + i_v0, edge_v0, sizeof(int32_t) * ne);
-        memcpy(hi + i_v1, edge_v1, sizeof(int32_t) * ne);
-        for (int v = 0, f = 0; v < n_kf; ++v) {
-            hi[i_slot + v] = fixed[v] ? -1 : f;
-            if (!fixed[v]) hi[i_free + f++] = v;
-        }
-        int32_t* off = hi + i_off;
-        for (size_t k = 0; k < ne; ++k) { off[edge_v0[k] + 1]++; off[edge_v1[k] + 1]++; }
-        for (size_t v = 0; v < nk; ++v) off[v + 1] += off[v];
-        std::vector<int32_t> cur(off, off + nk);
-        for (size_t k = 0; k < ne; ++k) {
-            hi[i_inc + cur[edge_v0[k]]++] = (int32_t)(k << 1);
-            hi[i_inc + cur[edge_v1[k]]++] = (int32_t)(k << 1) | 1;
-        }
-        if (np) memcpy(hi + i_ref, pt_ref, sizeof(int32_t) * np);
     } catch (const std::exception&) {
         return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_essential_graph_optimize: out of host memory for a graph of this size");
     }
-    memcpy(&hd[oS0], sim3_in, sizeof(double) * 8 * nk);
-    memcpy(&hd[oZ], meas, sizeof(double) * 8 * ne);
-    if (np) memcpy(&hd[oP], pt_in, sizeof(double) * 3 * np);
-    size_t got = bytes;
-    char* d = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
-    if (!d) QSP_HIP(hipMalloc((void**)&d, bytes));
-    struct Back {
-        int device; char* d; size_t bytes;
-        ~Back() { if (!buf_cache_put(g_dev_cache, device, d, bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
-    } back{device, d, got};
-    double* dd = (double*)d;
-    const int32_t* di = (const int32_t*)(dd + oI);
-    QSP_HIP(hipMemcpy(dd, hd.data(), sizeof(double) * n_up, hipMemcpyHostToDevice));
-    QSP_HIP(hipMemcpy(dd + oSa, dd + oS0, sizeof(double) * 8 * nk, hipMemcpyDeviceToDevice));
-    const int chol_lds = (int)(sizeof(double) * ba::CHOL_LDS_DOUBLES);
-    {   // the factorisation kernels' LDS size: once per device and process
-        static std::mutex mu;
-        static bool done[64];
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done[device & 63]) {
-            QSP_HIP(hipFuncSetAttribute((const void*)ba::k_chol_first, hipFuncAttributeMaxDynamicSharedMemorySize, chol_lds));
-            QSP_HIP(hipFuncSetAttribute((const void*)ba::k_chol_step, hipFuncAttributeMaxDynamicSharedMemorySize, chol_lds));
-            done[device & 63] = true;
-        }
-    }
-    Graph g;
-    g.n_kf = n_kf; g.n_edge = n_edge; g.n_free = n_free; g.D = D; g.fix_scale = fix_scale ? 1 : 0; g.ld = dimp;
-    g.v0 = di + i_v0; g.v1 = di + i_v1; g.slot = di + i_slot; g.free_v = di + i_free; g.inc_off = di + i_off; g.inc = di + i_inc;
-    g.Z = dd + oZ; g.E = dd + oE; g.chi = dd + oChi; g.J = dd + oJ;
-    double *S = dd + oSa, *St = dd + oSb, *H = dd + oH, *A = dd + oA, *Uf = dd + oUf, *W = dd + oW, *bv = dd + oB, *bs = dd + oBs, *y = dd + oY,
-           *x = dd + oX, *scal = dd + oScal;
-    const dim3 ge((n_edge + 63) / 64), gl((n_edge + 1) / 2), gk((n_kf + 63) / 64);
-    const dim3 gd((unsigned)std::min<size_t>((mat + 255) / 256, 4096));
+    Run r;
+    if ((rc = r.setup(device, n_kf, sim3_in, fixed, n_free, n_edge, edge_v0, edge_v1, meas, fix_scale, n_pt, pt_in, pt_ref))) return rc;
+    double *S = r.Sa, *St = r.Sb;
     double h[4], lambda = 0, ni = 2;
     int nbad = 0, done = 0;
     for (int it = 0; it < n_iter; ++it) {
-        // computeActiveErrors, activeRobustChi2, buildSystem
-        hipLaunchKernelGGL(k_eg_err, ge, dim3(64), 0, 0, g, S);
-        hipLaunchKernelGGL(k_eg_lin, gl, dim3(64), 0, 0, g, S);
-        QSP_HIP(hipMemsetAsync(H, 0, sizeof(double) * mat, 0));
-        QSP_HIP(hipMemsetAsync(scal, 0, sizeof(double) * 8, 0));
-        hipLaunchKernelGGL(k_eg_asm, dim3(n_free), dim3(64), 0, 0, g, H, bv);
-        hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(64), 0, 0, g, (const double*)nullptr, (const double*)nullptr, 0.0, (const double*)H, scal);
-        QSP_HIP(hipGetLastError());
-        QSP_HIP(hipMemcpy(h, scal, sizeof(h), hipMemcpyDeviceToHost));
+        if ((rc = r.linearise(S, h))) return rc;
         double cur = h[0];
         const double ini = cur;
         if (it == 0) {                                         // computeLambdaInit: the user's value when it is positive
@@ -459,19 +514,7 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
         int qmax = 0, accepted = 0;
         double rho = 0;
         do {
-            QSP_HIP(hipMemsetAsync(scal, 0, sizeof(double) * 8, 0));
-            hipLaunchKernelGGL(k_eg_damp, gd, dim3(256), 0, 0, (const double*)H, (const double*)bv, A, bs, dim, dimp, lambda);
-            hipLaunchKernelGGL(ba::k_chol_first, dim3(1), dim3(ba::CHOL_THREADS), (size_t)chol_lds, 0, (const double*)A, W, (const double*)bs, y, dimp,
-                               scal);
-            for (int k = 0; k + 1 < nb; ++k)
-                hipLaunchKernelGGL(ba::k_chol_step, dim3(nb - k - 1, nb - k - 1), dim3(ba::CHOL_THREADS), (size_t)chol_lds, 0, A, Uf, W, bs, y, dimp, k,
-                                   scal);
-            hipLaunchKernelGGL(k_eg_back, dim3(1), dim3(1024), 0, 0, (const double*)Uf, (const double*)W, (const double*)y, x, dimp, nb);
-            hipLaunchKernelGGL(k_eg_update, gk, dim3(64), 0, 0, g, (const double*)x, (const double*)scal, (const double*)S, St);
-            hipLaunchKernelGGL(k_eg_err, ge, dim3(64), 0, 0, g, (const double*)St);
-            hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(64), 0, 0, g, (const double*)x, (const double*)bv, lambda, (const double*)nullptr, scal);
-            QSP_HIP(hipGetLastError());
-            QSP_HIP(hipMemcpy(h, scal, sizeof(h), hipMemcpyDeviceToHost));
+            if ((rc = r.trial(S, St, lambda, h))) return rc;
             const bool ok = h[3] == 0.0;
             const double tempChi = ok ? h[0] : DBL_MAX;
             double scale = ok ? h[1] : 0.0;                    // (a failed solve leaves x = 0)
@@ -505,15 +548,61 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
         if (nbad >= 3) break;
     }
     tr.iters = done;
-    if (np) hipLaunchKernelGGL(k_eg_points, dim3((n_pt + 255) / 256), dim3(256), 0, 0, n_pt, (const double*)(dd + oP), di + i_ref,
-                               (const double*)(dd + oS0), (const double*)S, dd + oPo);
+    if (np) hipLaunchKernelGGL(k_eg_points, dim3((n_pt + 255) / 256), dim3(256), 0, 0, n_pt, (const double*)r.P, r.ref, (const double*)r.S0,
+                               (const double*)S, r.Po);
     QSP_HIP(hipGetLastError());
     // outputs are written only once everything has succeeded
     QSP_HIP(hipMemcpy(down.data(), S, sizeof(double) * 8 * nk, hipMemcpyDeviceToHost));
-    if (np) QSP_HIP(hipMemcpy(down.data() + 8 * nk, dd + oPo, sizeof(double) * 3 * np, hipMemcpyDeviceToHost));
+    if (np) QSP_HIP(hipMemcpy(down.data() + 8 * nk, r.Po, sizeof(double) * 3 * np, hipMemcpyDeviceToHost));
     memcpy(sim3_out, down.data(), sizeof(double) * 8 * nk);
     if (np) memcpy(pt_out, down.data() + 8 * nk, sizeof(double) * 3 * np);
     if (trace) *trace = tr;
+    return QSP_OK;
+}
+
+// qsp_essential_graph_stages: one Run::linearise and one Run::trial at the input states, every buffer copied down
+int essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
+                           const int32_t* edge_v1, const double* meas, int32_t fix_scale, double lambda, double* E, double* chi, double* J,
+                           double* H, double* b, double* x, double* sim3_trial, double* info) {
+    using namespace eg;
+    if (!E || !chi || !J || !H || !b || !x || !sim3_trial || !info) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_stages: null output");
+    if (!(lambda > 0) || !std::isfinite(lambda)) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_stages: lambda must be positive and finite");
+    int n_free = 0;
+    int rc = validate(n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, 0, 0, nullptr, nullptr, sim3_trial, nullptr, &n_free);
+    if (rc) return rc;
+    if (n_edge == 0 || n_free == 0) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_stages: no edge or no free vertex, nothing to show");
+    const size_t nk = (size_t)n_kf, ne = (size_t)n_edge, dim = (size_t)(fix_scale ? 6 : 7) * n_free;
+    const size_t oE = 0, oChi = oE + 7 * ne, oJ = oChi + ne, oH = oJ + 98 * ne, oB = oH + dim * dim, oX = oB + dim, oS = oX + dim, n_down = oS + 8 * nk;
+    std::vector<double> down;
+    try {
+        down.resize(n_down);
+    } catch (const std::exception&) {
+        return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_essential_graph_stages: out of host memory for a graph of this size");
+    }
+    Run r;
+    if ((rc = r.setup(device, n_kf, sim3_in, fixed, n_free, n_edge, edge_v0, edge_v1, meas, fix_scale, 0, nullptr, nullptr))) return rc;
+    double hl[4], ht[4];
+    if ((rc = r.linearise(r.Sa, hl))) return rc;
+    // the trial's k_eg_err overwrites E and chi: what the linearisation wrote comes down first
+    QSP_HIP(hipMemcpy(&down[oE], r.g.E, sizeof(double) * 7 * ne, hipMemcpyDeviceToHost));
+    QSP_HIP(hipMemcpy(&down[oChi], r.g.chi, sizeof(double) * ne, hipMemcpyDeviceToHost));
+    QSP_HIP(hipMemcpy(&down[oJ], r.g.J, sizeof(double) * 98 * ne, hipMemcpyDeviceToHost));
+    QSP_HIP(hipMemcpy2D(&down[oH], sizeof(double) * dim, r.H, sizeof(double) * r.dimp, sizeof(double) * dim, dim, hipMemcpyDeviceToHost));
+    QSP_HIP(hipMemcpy(&down[oB], r.bv, sizeof(double) * dim, hipMemcpyDeviceToHost));
+    if ((rc = r.trial(r.Sa, r.Sb, lambda, ht))) return rc;
+    QSP_HIP(hipMemcpy(&down[oX], r.x, sizeof(double) * dim, hipMemcpyDeviceToHost));
+    QSP_HIP(hipMemcpy(&down[oS], r.Sb, sizeof(double) * 8 * nk, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < ne; ++k)                            // k_eg_lin writes nothing for a fixed vertex: that side reads as zeros
+        for (int s = 0; s < 2; ++s)
+            if (fixed[s ? edge_v1[k] : edge_v0[k]]) memset(&down[oJ + (2 * k + s) * 49], 0, sizeof(double) * 49);
+    memcpy(E, &down[oE], sizeof(double) * 7 * ne);
+    memcpy(chi, &down[oChi], sizeof(double) * ne);
+    memcpy(J, &down[oJ], sizeof(double) * 98 * ne);
+    memcpy(H, &down[oH], sizeof(double) * dim * dim);
+    memcpy(b, &down[oB], sizeof(double) * dim);
+    memcpy(x, &down[oX], sizeof(double) * dim);
+    memcpy(sim3_trial, &down[oS], sizeof(double) * 8 * nk);
+    info[0] = hl[0]; info[1] = hl[2]; info[2] = ht[0]; info[3] = ht[1]; info[4] = ht[3]; info[5] = (double)r.dim; info[6] = (double)r.nb;
     return QSP_OK;
 }
 

@@ -89,6 +89,13 @@ def lu3_solve_b(W, t):
     return np.stack([x0, x1, x2], -1)
 
 
+def log_branches(S):
+    """(small sigma, small angle) of every row: the two conditions Sim3::log branches on, as log_b evaluates them"""
+    R = rotmat_b(S[:, 3:7])
+    d = 0.5 * (((R[:, 0, 0] + R[:, 1, 1]) + R[:, 2, 2]) - 1)
+    return np.abs(np.log(S[:, 7])) < EPS, d > 1 - EPS
+
+
 def log_b(S):
     """Sim3::log of every row: omega (3), upsilon (3), sigma; the four branches (small sigma x small angle) by masks"""
     dt = S.dtype
@@ -97,7 +104,7 @@ def log_b(S):
     R = rotmat_b(S[:, 3:7])
     d = 0.5 * (((R[:, 0, 0] + R[:, 1, 1]) + R[:, 2, 2]) - 1)
     dR = np.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], -1)
-    small_s, small_a = np.abs(sigma) < EPS, d > 1 - EPS
+    small_s, small_a = log_branches(S)
     with np.errstate(all="ignore"):
         theta = np.arccos(d)
         theta2 = theta * theta
@@ -258,12 +265,24 @@ def solve_spd(H, b, lam, longdouble=False):
     return x.astype(np.float64)
 
 
-def correct_points(S_in, S_out, pts, ref):
+def correct_points(S_in, S_out, pts, ref, longdouble=False):
     pts = np.asarray(pts, np.float64).reshape(-1, 3)
     if len(pts) == 0:
         return pts.copy()
     ref = np.asarray(ref, np.int64)
-    return map_b(inv_b(S_out[ref]), map_b(S_in[ref], pts))
+    dt = np.longdouble if longdouble else np.float64
+    S_in, S_out, pts = (np.asarray(a, np.float64).astype(dt) for a in (S_in, S_out, pts))
+    return map_b(inv_b(S_out[ref]), map_b(S_in[ref], pts)).astype(np.float64)
+
+
+def graph_of(sc):
+    """what numeric_jacobian and build_system take: the edges, the fixed mask, the slot of every vertex among the free ones"""
+    fixed = np.asarray(sc["fixed"], np.uint8)
+    free_v = np.flatnonzero(fixed == 0)
+    slot = np.full(len(fixed), -1, np.int64)
+    slot[free_v] = np.arange(len(free_v))
+    return dict(v0=np.asarray(sc["v0"], np.int64), v1=np.asarray(sc["v1"], np.int64), meas=np.asarray(sc["meas"], np.float64).reshape(-1, 8),
+                fixed=fixed, fix_scale=bool(sc["fix_scale"]), slot=slot, D=6 if sc["fix_scale"] else 7, n_free=len(free_v), free_v=free_v)
 
 
 def optimize(sc, n_iter=None, fix_scale=None, lambda_init=None, longdouble=False, longdouble_solve=False):
@@ -277,11 +296,8 @@ def optimize(sc, n_iter=None, fix_scale=None, lambda_init=None, longdouble=False
     v0, v1 = np.asarray(sc["v0"], np.int64), np.asarray(sc["v1"], np.int64)
     meas = np.asarray(sc["meas"], np.float64).reshape(-1, 8)
     n_kf, ne = len(S0), len(v0)
-    free_v = np.flatnonzero(fixed == 0)
-    slot = np.full(n_kf, -1, np.int64)
-    slot[free_v] = np.arange(len(free_v))
-    D = 6 if fix_scale else 7
-    g = dict(v0=v0, v1=v1, meas=meas, fixed=fixed, fix_scale=bool(fix_scale), slot=slot, D=D, n_free=len(free_v))
+    g = graph_of(dict(sc, fix_scale=fix_scale))
+    free_v, D = g["free_v"], g["D"]
     out = dict(sim3=S0.copy(), pts=np.asarray(sc["pts"], np.float64).reshape(-1, 3).copy(), iters=0, trace=np.zeros((0, 4)), accepts=[])
     if n_kf == 0 or ne == 0 or len(free_v) == 0:
         return out
@@ -529,7 +545,313 @@ def bars(name):
     return {k: FACTOR * v for k, v in _measured()[name].items()}
 
 
-if __name__ == "__main__":          # python -m tests.essential_oracle: rewrites the CPU half of profiles/essential_margins.json
+# ---- one linearisation and one trial, stage by stage: the oracle of qsp_essential_graph_stages ------------------------------
+def exp_ld(u):
+    """sim3_oracle.s_exp in np.longdouble (the same formulas and branches): Sim3(update) -> (8,) longdouble"""
+    ld = np.longdouble
+    u = np.asarray(u, np.float64).astype(ld)
+    om, up, sigma = u[:3], u[3:6], u[6]
+    theta = np.sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2])
+    z = ld(0)
+    Om = np.array([[z, -om[2], om[1]], [om[2], z, -om[0]], [-om[1], om[0], z]], ld)
+    Om2 = Om @ Om
+    s = np.exp(sigma)
+    I = np.eye(3, dtype=ld)
+    small_s, small_a = abs(sigma) < EPS, theta < EPS
+    sn, cs, theta2, sigma2 = np.sin(theta), np.cos(theta), theta * theta, sigma * sigma
+    R = (I + Om) + Om2 if small_a else (I + (sn / theta) * Om) + ((1 - cs) / theta2) * Om2
+    C = ld(1) if small_s else (s - 1) / sigma
+    if small_s:
+        A, B = (ld(1) / 2, ld(1) / 6) if small_a else ((1 - cs) / theta2, (theta - sn) / (theta2 * theta))
+    elif small_a:
+        A, B = ((sigma - 1) * s + 1) / sigma2, ((sigma2 / 2 - sigma + 1) * s) / (sigma2 * sigma)
+    else:
+        a, b, c = s * sn, s * cs, theta2 + sigma2
+        A, B = (a * sigma + (1 - b) * theta) / (theta * c), (C - ((b - 1) * sigma + a * theta) / c) / theta2
+    W = (A * Om + B * Om2) + C * I
+    out = np.empty(8, ld)
+    out[:3] = W @ up
+    q = np.zeros(4, ld)                                            # Eigen's Quaterniond(Matrix3d), as sim3_oracle.quat_of
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        r = np.sqrt(tr + 1)
+        q[3] = r / 2
+        r = ld(1) / 2 / r
+        q[0], q[1], q[2] = (R[2, 1] - R[1, 2]) * r, (R[0, 2] - R[2, 0]) * r, (R[1, 0] - R[0, 1]) * r
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        r = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1)
+        q[i] = r / 2
+        r = ld(1) / 2 / r
+        q[3], q[j], q[k] = (R[k, j] - R[j, k]) * r, (R[j, i] + R[i, j]) * r, (R[k, i] + R[i, k]) * r
+    out[3:7] = q
+    out[7] = s
+    return out
+
+
+def linearise(sc, S, longdouble=False):
+    """E (n_edge,7), chi (n_edge), J (n_edge,2,7,7), H (dim,dim), b (dim) at the states S: what one iteration builds"""
+    g = graph_of(sc)
+    S = np.asarray(S, np.float64).reshape(-1, 8)
+    E = edge_errors(g["meas"], S[g["v0"]], S[g["v1"]], longdouble)
+    J = numeric_jacobian(S, g, longdouble)
+    H, b = build_system(J, E, g)
+    return E, _chi(E), J, H, b
+
+
+def update(sc, S, x, longdouble=False):
+    """oplus on every free vertex: exp(x_v) * S[v] (update[6] = 0 under fix_scale); fixed vertices are copies"""
+    g = graph_of(sc)
+    S = np.asarray(S, np.float64).reshape(-1, 8)
+    St = S.copy()
+    for fi, v in enumerate(g["free_v"]):
+        u = np.zeros(7)
+        u[:g["D"]] = x[fi * g["D"]:fi * g["D"] + g["D"]]
+        St[v] = s_mul(exp_ld(u), S[v].astype(np.longdouble)).astype(np.float64) if longdouble else s_mul(s_exp(u), S[v])
+    return St
+
+
+def trial(sc, S, H, b, lam, x=None, longdouble=False, longdouble_solve=False):
+    """x, St, chi2, scale of one Levenberg-Marquardt trial: (H + lam I) x = b (or the x given), St = exp(x) S, chi2 at St and
+    computeScale() in the lane order of the device (edge k on lane k % 64; unknown a of free vertex fi on lane (7 fi + a) % 64)"""
+    g = graph_of(sc)
+    if x is None:
+        x = solve_spd(H, b, lam, longdouble_solve)
+    St = update(sc, S, x, longdouble)
+    E = edge_errors(g["meas"], St[g["v0"]], St[g["v1"]], longdouble)
+    return x, St, chi2_lanes(_chi(E)), scale_lanes(g, x, b, lam)
+
+
+def chi2_lanes(chi):
+    return float(lane_sum([chi], np.arange(len(chi)) % 64))
+
+
+def scale_lanes(g, x, b, lam):
+    j7 = (7 * np.arange(g["n_free"])[:, None] + np.arange(g["D"])[None, :]).reshape(-1)
+    return float(lane_sum([x * (lam * x + b)], j7 % 64))
+
+
+def _factor_gauss(S):
+    """W = L^-1 of a symmetric positive definite block as ba::factor_tile64 grows it: Gauss steps on [S | I], row q scaled by
+    1 / sqrt of its pivot, then taken off every row below in proportion to its entry of column q"""
+    n = len(S)
+    M = np.concatenate([S, np.eye(n)], 1)
+    for q in range(n):
+        M[q] = M[q] * (1.0 / np.sqrt(M[q, q]))
+        if q + 1 < n:
+            M[q + 1:] -= np.outer(M[q, q + 1:n], M[q])
+    return M[:, n:]
+
+
+def solve_blocked(H, b, lam, nb_size=64):
+    """(H + lam I) x = b in float64 by the device's algorithm (k_chol_first / k_chol_step / k_eg_back): padded to the 64-wide block
+    with an identity tail; per block step k the explicit inverse W_k = L_kk^-1 grown beside the factor (_factor_gauss), y_k = W_k b_k,
+    P_j = W_k A_kj, A_ij -= P_i^T P_j, b_j -= P_j^T y_k; then x_k = W_k^T (y_k - sum_{j > k} P_kj x_j), k descending.  The order
+    inside a block product is numpy's.  Multiplying by explicit inverses is not backward stable the way LAPACK's substitutions are:
+    this restatement, not LAPACK, is the yardstick where the device's x lies beyond LAPACK's own distance to the longdouble solve."""
+    n = len(b)
+    nb = (n + nb_size - 1) // nb_size
+    m = nb * nb_size
+    A = np.eye(m)
+    A[:n, :n] = H
+    A[np.arange(n), np.arange(n)] += lam
+    r = np.zeros(m)
+    r[:n] = b
+    blk = lambda k: slice(k * nb_size, (k + 1) * nb_size)
+    W, P, y = [], {}, np.zeros(m)
+    for k in range(nb):
+        Wk = _factor_gauss(A[blk(k), blk(k)])
+        W.append(Wk)
+        y[blk(k)] = Wk @ r[blk(k)]
+        for j in range(k + 1, nb):
+            P[k, j] = Wk @ A[blk(k), blk(j)]
+        for j in range(k + 1, nb):
+            for i in range(k + 1, j + 1):
+                A[blk(i), blk(j)] -= P[k, i].T @ P[k, j]
+            A[blk(j), blk(j)] = np.triu(A[blk(j), blk(j)]) + np.triu(A[blk(j), blk(j)], 1).T
+            r[blk(j)] -= P[k, j].T @ y[blk(k)]
+    x = np.zeros(m)
+    for k in range(nb - 1, -1, -1):
+        acc = y[blk(k)].copy()
+        for j in range(k + 1, nb):
+            acc -= P[k, j] @ x[blk(j)]
+        x[blk(k)] = W[k].T @ acc
+    return x[:n]
+
+
+# name -> (make_scene arguments, edits of its result).  One linearisation and one trial need no comparable accept decisions, so
+# these scenes carry measurement noise and any fixed mask; every stage is compared on its own (tests/test_gpu_essential_stages.py).
+#   kf2 / kf2_fs        one free vertex: dim 7 / 6, one block, 57 / 58 padded rows
+#   kf10 / kf11         dim 63 / 70: just under and just across one 64-wide block
+#   kf33_fs / kf65      dim 192 = 3 x 64 / 448 = 7 x 64: NO padding -- k_eg_damp's identity tail is empty, the last block is full
+#   hub4 / hub4_fs      the hub ring (24 key frames, 70 more edges on vertex 9, five duplicates, 142 edges) with the vertices
+#                       3, 10, 11, 23 fixed: slots that are neither v nor v - 1, edges with both ends fixed (10 - 11), the first
+#                       and the last stretch of the ring fixed, a free vertex with more than 64 incident edges as v0 and as v1;
+#                       with the scale fixed the rows drop to 6 while the lanes keep the 7-wide numbering
+#   kf40_4fs            40 key frames, 0, 20, 21, 39 fixed, scale fixed: the same at four blocks (dim 216)
+#   isolated            12 key frames and a thirteenth, free, without an edge: a zero block row of H, x exactly 0 there
+#   branches            9 key frames in a chain of 8 hand-made edges whose error Sim3 is exp of (rotation 0 / 1e-4 / 0.3 / 1.0 rad)
+#                       x (sigma exactly 0 / 0.1) with a translation: each of Sim3::log's four branches twice
+# Rotation errors stay below 2.5 rad (f = theta / (2 sqrt(1 - d^2)) loses its digits towards pi) and away from the small-angle
+# threshold d = 1 - 1e-5, theta ~ 4.5e-3: just above it (1 - cos theta) / theta^2 cancels five digits in the reference itself, in
+# float64 and in longdouble alike, and no bar against longdouble means anything there.  1e-4 rad is well inside the small-angle
+# branch (d = 1 - 5e-9), 0.3 rad well outside.  The seeds are those at which no edge of a noisy scene has an error rotation between
+# 3e-3 and 7e-3 rad, nor, with the scale free, an error |sigma| below 1e-4: Sim3::log's small-sigma threshold is 1e-5, and the wide-step
+# Jacobian (steps to 2e-5) must not cross it (tests/test_oracle_essential_stages.py asserts both).
+STAGE_SCENES = {
+    "kf2": (dict(seed=1, n_kf=2, fixed_at=0, noise=0.02), {}),
+    "kf2_fs": (dict(seed=1, n_kf=2, fixed_at=0, noise=0.02, fix_scale=True), {}),
+    "kf10": (dict(seed=1, n_kf=10, fixed_at=4, noise=0.02), {}),
+    "kf11": (dict(seed=1, n_kf=11, fixed_at=10, noise=0.02), {}),
+    "kf33_fs": (dict(seed=3, n_kf=33, fixed_at=0, noise=0.02, fix_scale=True), {}),
+    "kf65": (dict(seed=9, n_kf=65, fixed_at=30, noise=0.02), {}),
+    "hub4": (dict(seed=13, n_kf=24, fixed_at=3, noise=0.02, hub=(9, 70), dup=5), dict(fixed=(3, 10, 11, 23))),
+    "hub4_fs": (dict(seed=3, n_kf=24, fixed_at=3, noise=0.02, hub=(9, 70), dup=5, fix_scale=True), dict(fixed=(3, 10, 11, 23))),
+    "kf40_4fs": (dict(seed=8, n_kf=40, fixed_at=0, noise=0.02, fix_scale=True), dict(fixed=(0, 20, 21, 39))),
+    "isolated": (dict(seed=1, n_kf=12, fixed_at=5, noise=0.02), dict(isolated=True)),
+    "branches": (dict(seed=3, n_kf=9, fixed_at=0, consistent=True), dict(branches=True)),
+}
+MULTI_FIXED = ("hub4", "hub4_fs", "kf40_4fs")
+EXACT_BLOCKS = {"kf33_fs": 192, "kf65": 448}
+BRANCH_ROT, BRANCH_SIGMA = (0.0, 1e-4, 0.3, 1.0), (0.0, 0.1)
+# the dampings of the solve: the reference's first lambda, g2o's own (1e-5 max |H_jj|, `None` here) and a large one
+STAGE_LAMBDAS = (1e-16, None, 30.0)
+
+
+@functools.lru_cache(maxsize=None)
+def stage_scene(name):
+    """the scene (inputs only; treat as read-only)"""
+    args, edit = STAGE_SCENES[name]
+    sc = make_scene(**args)
+    if "fixed" in edit:
+        sc["fixed"] = np.zeros(len(sc["sim3"]), np.uint8)
+        sc["fixed"][list(edit["fixed"])] = 1
+    if edit.get("isolated"):
+        extra = s_mul(s_exp(np.array([0.1, -0.2, 0.05, 0.3, 0.1, -0.2, 0.02])), sc["sim3"][-1])
+        sc["sim3"] = np.concatenate([sc["sim3"], extra[None]])
+        sc["fixed"] = np.concatenate([sc["fixed"], np.zeros(1, np.uint8)])
+    if edit.get("branches"):
+        S = sc["sim3"]
+        v0, v1 = np.arange(1, 9, dtype=np.int32), np.arange(0, 8, dtype=np.int32)
+        meas = []
+        for k in range(8):
+            axis = np.array([0.6, -0.48, 0.64])                                           # a unit vector
+            u = np.concatenate([BRANCH_ROT[k % 4] * axis, [0.3, -0.2, 0.1], [BRANCH_SIGMA[k // 4]]])
+            meas.append(s_mul(s_exp(u), s_mul(S[v1[k]], s_inv(S[v0[k]]))))                # Z S0 S1^-1 = exp(u) up to rounding
+        sc.update(v0=v0, v1=v1, meas=np.array(meas))
+    return sc
+
+
+def stage_lambdas(H):
+    return [1e-5 * float(np.max(np.abs(np.diag(H)))) if lam is None else lam for lam in STAGE_LAMBDAS]
+
+
+def stage_points(sc, n, seed=11):
+    """n points with reference key frames spread over all vertices, the fixed ones among them"""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(-3, 3, (n, 3)), ((np.arange(n) * 7 + 3) % len(sc["sim3"])).astype(np.int32)
+
+
+def _absmax(a, b):
+    return float(np.max(np.abs(np.asarray(a) - np.asarray(b)))) if np.size(a) else 0.0
+
+
+def point_distance(sc, S_out):
+    """float64 against longdouble for correct_points between the scene's start and S_out.  The rounding of one point is a draw;
+    the yardstick of the pass on a scene is the largest over 600 points spread over all vertices, whatever the number of points a
+    test then runs (a fixture with one point would otherwise be held to the luck of that point)."""
+    P, R = stage_points(sc, 600)
+    return _absmax(correct_points(sc["sim3"], S_out, P, R), correct_points(sc["sim3"], S_out, P, R, longdouble=True))
+
+
+@functools.lru_cache(maxsize=None)
+def stage_reference(name):
+    """the references of one linearisation at the scene's states, computed once (treat as read-only): E, J, H, b in float64, E and J
+    with longdouble error evaluations (El, Jl), the wide-step longdouble Jacobian Ja and the mask of free sides (n_edge,2)"""
+    sc = stage_scene(name)
+    g = graph_of(sc)
+    E, chi, J, H, b = linearise(sc, sc["sim3"])
+    El, _, Jl, _, _ = linearise(sc, sc["sim3"], longdouble=True)
+    free = np.stack([g["fixed"][g["v0"]] == 0, g["fixed"][g["v1"]] == 0], -1)
+    return dict(E=E, chi=chi, J=J, H=H, b=b, El=El, Jl=Jl, Ja=analytic_jacobian(sc["sim3"], g), free=free)
+
+
+@functools.lru_cache(maxsize=None)
+def _stage_measured(name):
+    sc, r = stage_scene(name), stage_reference(name)
+    S, H, b, free = sc["sim3"], r["H"], r["b"], r["free"]
+    out = dict(E_abs=_absmax(r["E"], r["El"]), J_abs=_absmax(r["J"], r["Jl"]), J_analytic_abs=_absmax(r["J"][free], r["Ja"][free]), x_rel=[],
+               x_blocked_rel=[], lambdas=[])
+    out["update_abs"] = 0.0
+    for lam in stage_lambdas(H):
+        x, xl = solve_spd(H, b, lam), solve_spd(H, b, lam, longdouble=True)
+        top = float(np.max(np.abs(xl)))
+        out["lambdas"].append(lam)
+        out["x_rel"].append(_absmax(x, xl) / top)
+        out["x_blocked_rel"].append(_absmax(solve_blocked(H, b, lam), xl) / top)
+        out["update_abs"] = max(out["update_abs"], _absmax(update(sc, S, x), update(sc, S, x, longdouble=True)))   # (the largest of the three steps)
+    out["pt_abs"] = point_distance(sc, update(sc, S, solve_spd(H, b, out["lambdas"][1])))
+    return out
+
+
+def stage_distance(name, runs, lambdas):
+    """what a device's stage outputs (one dict of arrays per lambda, keys E J H b x sim3_trial) lie from the references, each stage
+    fed the device's own output of the stage before: the quantities of stage_sensitivity() but the point pass"""
+    sc, r = stage_scene(name), stage_reference(name)
+    free = r["free"]
+    d = dict(E_abs=_absmax(runs[0]["E"], r["El"]), J_abs=_absmax(runs[0]["J"], r["J"]), J_analytic_abs=_absmax(runs[0]["J"][free], r["Ja"][free]),
+             x_rel=[], update_abs=0.0)
+    for run, lam in zip(runs, lambdas):
+        xl = solve_spd(run["H"], run["b"], lam, longdouble=True)
+        d["x_rel"].append(_absmax(run["x"], xl) / float(np.max(np.abs(xl))))
+        d["update_abs"] = max(d["update_abs"], _absmax(run["sim3_trial"], update(sc, sc["sim3"], run["x"], longdouble=True)))
+    return d
+
+
+def stage_sensitivity(name):
+    """the reference's own distances on a stage scene, stage by stage: float64 against longdouble for the errors, the numeric
+    Jacobian, the update and the point pass; the float64 numeric Jacobian against the wide-step longdouble one on free sides;
+    LAPACK's solve and the float64 restatement of the device's blocked solve against the longdouble solve, relative to max |x|,
+    at each of stage_lambdas()"""
+    return {k: (list(v) if isinstance(v, list) else v) for k, v in _stage_measured(name).items()}
+
+
+def stage_bars(name):
+    """FACTOR x stage_sensitivity: what tests/test_gpu_essential_stages.py allows the GPU, stage by stage"""
+    return {k: ([FACTOR * a for a in v] if isinstance(v, list) else FACTOR * v) for k, v in _stage_measured(name).items() if k != "lambdas"}
+
+
+@functools.lru_cache(maxsize=None)
+def fixture_point_bar(name):
+    """the point pass of a parity fixture: FACTOR x point_distance at the oracle's final states"""
+    return FACTOR * point_distance(fixture(name), fixture_result(name)["sim3"])
+
+
+STAGE_MARGINS = os.path.join(os.path.dirname(MARGINS), "essential_stage_margins.json")
+
+
+def write_stage_margins(gpu_distance=None):
+    doc = json.load(open(STAGE_MARGINS)) if os.path.isfile(STAGE_MARGINS) else {}
+    doc["what"] = ("qsp_essential_graph_stages against tests/essential_oracle.py over essential_oracle.STAGE_SCENES, stage by stage, each "
+                   "stage fed the device's output of the stage before.  sensitivity: the oracle's own distances (CPU) -- E_abs, J_abs, "
+                   "update_abs, pt_abs: float64 against longdouble; J_analytic_abs: float64 numeric Jacobian against a wide-step "
+                   "longdouble one, free sides; x_rel / x_blocked_rel: LAPACK's solve / the float64 restatement of the device's "
+                   "blocked solve against the longdouble solve at `lambdas`, relative to max |x|.  bar = 4 x sensitivity: what "
+                   "tests/test_gpu_essential_stages.py allows.  fixture_pt_bar: the point pass of the parity fixtures.  gpu_distance: "
+                   "what the GPU measured (tools/time_essential.py).  Assembly and the reductions are compared bit for bit.")
+    doc["sensitivity"] = {name: stage_sensitivity(name) for name in STAGE_SCENES}
+    doc["bar"] = {name: stage_bars(name) for name in STAGE_SCENES}
+    doc["fixture_pt_bar"] = {name: fixture_point_bar(name) for name in FIXTURES}
+    if gpu_distance is not None:
+        doc["gpu_distance"] = gpu_distance
+    doc.setdefault("gpu_distance", None)
+    json.dump(doc, open(STAGE_MARGINS, "w"), indent=1, sort_keys=True)
+    return doc
+
+
+if __name__ == "__main__":          # python -m tests.essential_oracle: rewrites the CPU halves of profiles/essential_margins.json
+                                    # and profiles/essential_stage_margins.json
     sens = measured_sensitivity()
     doc = json.load(open(MARGINS)) if os.path.isfile(MARGINS) else {}
     doc["what"] = ("qsp_essential_graph_optimize against tests/essential_oracle.py over essential_oracle.FIXTURES.  sensitivity: the oracle's "
@@ -541,3 +863,4 @@ if __name__ == "__main__":          # python -m tests.essential_oracle: rewrites
     doc.setdefault("gpu_distance", None)
     json.dump(doc, open(MARGINS, "w"), indent=1, sort_keys=True)
     print(json.dumps(doc, indent=1, sort_keys=True))
+    print(json.dumps(write_stage_margins(), indent=1, sort_keys=True))
