@@ -415,7 +415,14 @@ void qsp_ba_destroy(qsp_ba_problem* p);
  * the process may be inside a call). */
 void qsp_ba_release_caches(void);
 
-/* g2o edge levels: 1 = excluded from optimisation (e->setLevel(1), src/Optimizer_util.cc:621-654).  NULL = all active. */
+/* g2o edge levels: 1 = excluded from optimisation (e->setLevel(1), src/Optimizer_util.cc:621-654).  NULL = all active.
+ * A problem is long-lived and may be driven in any order of calls.  What it holds for the caller:
+ *   levels     what the last qsp_ba_set_levels or qsp_ba_local_joint left (the latter: all active, then the outlier set of its
+ *              stage boundary; nothing when it returned at once on a raised stop flag);
+ *   estimates  what the last solve or qsp_ba_set_state left.
+ * qsp_ba_set_shard*, qsp_ba_set_deterministic and qsp_ba_set_option change how the NEXT solve is computed; they never change
+ * levels or estimates, whenever they are called -- also between a qsp_ba_set_levels / qsp_ba_local_joint and the solve that
+ * follows. */
 int qsp_ba_set_levels(qsp_ba_problem* p, const uint8_t* mono, const uint8_t* stereo, const uint8_t* objedge);
 
 /* optimizer.initializeOptimization(0); optimizer.optimize(n_iter) -- Levenberg-Marquardt with Schur complement over the
@@ -452,7 +459,11 @@ int qsp_ba_profile(qsp_ba_problem* p, int enable, qsp_ba_stats* out);
  * redundantly and updates its own landmarks.  `fn` must sum
  * `count` doubles at `device_buf` in place over all ranks and be complete (or ordered on `hip_stream`) when it returns;
  * with torch.distributed this is all_reduce on RCCL ("nccl" backend) over xGMI -- see qsp_slam_amd/parallel.py.
- * The reference has no counterpart (single process). */
+ * The reference has no counterpart (single process).
+ * May be called at any time between solves, again with another (rank, world), or with world == 1 to switch sharding off.  The
+ * sharding is not part of the caller's levels (see qsp_ba_set_levels): the levels and estimates the problem holds stay as they
+ * are, "belongs to another rank" never shows in qsp_ba_get_index (a landmark is inactive only if the CALLER's levels leave it no
+ * edge), and nothing of one (rank, world) survives the change to another. */
 typedef int (*qsp_allreduce_fn)(void* ctx, double* device_buf, int64_t count, void* hip_stream);
 int qsp_ba_set_shard(qsp_ba_problem* p, int32_t rank, int32_t world, qsp_allreduce_fn fn, void* ctx);
 

@@ -110,6 +110,7 @@ class BaProblem(object):
         o = Opts(delta_mono, delta_stereo, delta_obj, _p(flag, up))
         done = lib().ba_oracle_optimize(C.byref(self.c), n_iter, C.byref(o), C.byref(tr))
         n = tr.n
+        self._index = (kh[: self.c.n_kf].copy(), oh[: self.c.n_obj].copy(), ph[: self.c.n_pt].copy())
         return dict(iterations=done, chi2=chi2[:n].copy(), lam=lam[:n].copy(), trials=trials[:n].copy(),
                     accepted=acc[:n].copy(), kf_hidx=kh[: self.c.n_kf].copy(), obj_hidx=oh[: self.c.n_obj].copy(),
                     pt_hidx=ph[: self.c.n_pt].copy(), result=tr.result)
@@ -122,8 +123,13 @@ class BaProblem(object):
     def local_joint_ba(self, stop=None):
         """Optimizer::LocalJointBundleAdjustment schedule, src/Optimizer_util.cc:598-661: optimize(5) with Huber
         sqrt(5.991) / sqrt(7.815) / sqrt(1e3); mark chi2 > 5.991 / 7.815 / 1e3 or non-positive depth as level 1; drop
-        the robust kernels; optimize(10)."""
+        the robust kernels; optimize(10).  The reference builds its graph anew for every call, so every edge starts at
+        level 0 (a reused problem forgets the outlier set of its last call), and it returns with nothing touched when the stop
+        flag is already up (:588-595): (None, None)."""
         s = self.s
+        if stop is not None and stop[0]:
+            return None, None
+        self.set_levels(None, None, None)
         t1 = self.optimize(5, np.float32(np.sqrt(5.991)), np.float32(np.sqrt(7.815)), np.float32(np.sqrt(1e3)), stop)
         mp, sp = self.depth_positive()
         s["mono_level"][: self.nm] = ((s["mono_chi2"][: self.nm] > 5.991) | ~mp).astype(np.uint8)
@@ -134,6 +140,34 @@ class BaProblem(object):
 
     def state(self):
         return self.s["kf_pose"].copy(), self.s["pt_xyz"].copy(), self.s["obj_pose"].copy()
+
+    # The setters and getters below mirror qsp_slam_amd.ba.BaProblem so that one call sequence can drive either (tests/ba_sequences.py).
+    # They write INTO the arrays the C struct points at.
+
+    def set_state(self, kf=None, pt=None, ob=None):
+        for key, a in (("kf_pose", kf), ("pt_xyz", pt), ("obj_pose", ob)):
+            if a is not None and self.s[key].size:
+                self.s[key][...] = np.asarray(a, np.float64).reshape(self.s[key].shape)
+
+    def set_levels(self, mono=None, stereo=None, obj=None):
+        """e->setLevel() of every edge; None = that edge kind all active (qsp_ba_set_levels)"""
+        for key, n, a in (("mono_level", self.nm, mono), ("st_level", self.ns, stereo), ("oe_level", self.no, obj)):
+            self.s[key][:] = 0
+            if a is not None:
+                self.s[key][:n] = np.asarray(a).reshape(-1)[:n] != 0
+
+    def levels(self):
+        return self.s["mono_level"][: self.nm].copy(), self.s["st_level"][: self.ns].copy(), self.s["oe_level"][: self.no].copy()
+
+    def index(self):
+        """the hessian index tables of the last optimize() call (qsp_ba_get_index)"""
+        return tuple(a.copy() for a in self._index)
+
+    def edges(self):
+        """per-edge chi2 of the last error evaluation that had the edge active, and isDepthPositive() (qsp_ba_get_edges)"""
+        mp, sp = self.depth_positive()
+        return dict(mono_chi2=self.s["mono_chi2"][: self.nm].copy(), st_chi2=self.s["st_chi2"][: self.ns].copy(),
+                    oe_chi2=self.s["oe_chi2"][: self.no].copy(), mono_pos=mp, st_pos=sp)
 
 
 def pose_optimization(K, pose, X, obs, info, stereo):

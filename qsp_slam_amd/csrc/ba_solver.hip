@@ -3528,13 +3528,24 @@ static int read_scal(qsp_ba_problem* p, double* out4) {
 // device; whoever needs them (the next index build, qsp_ba_get_index) fetches the levels and rebuilds the tables -- host work
 // that is off the path of the bundle adjustment that produced them.
 static void build_index(qsp_ba_problem* p);
+// The device arrays hold "caller's level OR belongs to another rank" (upload_levels); the host's copies, build_index, qsp_ba_get_index
+// and the profile counts know caller levels only.  So what is read back is taken for the edges this rank owns; on an edge under the
+// mask that is on the device now the device byte says nothing about the caller's level and the host keeps its own.
 static int refresh_host_index(qsp_ba_problem* p) {
     if (!p->host_stale) return QSP_OK;
     const Dev& d = p->d;
     p->all_active = false;
     QSP_HIP(hipStreamSynchronize(p->stream));
-    if (d.n_edge) QSP_HIP(hipMemcpy(p->edge_level_h.data(), d.edge_level, d.n_edge, hipMemcpyDeviceToHost));
-    if (d.n_oe) QSP_HIP(hipMemcpy(p->oe_level_h.data(), d.oe_level, d.n_oe, hipMemcpyDeviceToHost));
+    if (p->world > 1) {
+        std::vector<uint8_t> le(std::max(d.n_edge, 1)), lo(std::max(d.n_oe, 1));
+        if (d.n_edge) QSP_HIP(hipMemcpy(le.data(), d.edge_level, d.n_edge, hipMemcpyDeviceToHost));
+        if (d.n_oe) QSP_HIP(hipMemcpy(lo.data(), d.oe_level, d.n_oe, hipMemcpyDeviceToHost));
+        for (int e = 0; e < d.n_edge; ++e) if (!p->edge_foreign[e]) p->edge_level_h[e] = le[e];
+        for (int e = 0; e < d.n_oe; ++e) if (!p->oe_foreign[e]) p->oe_level_h[e] = lo[e];
+    } else {
+        if (d.n_edge) QSP_HIP(hipMemcpy(p->edge_level_h.data(), d.edge_level, d.n_edge, hipMemcpyDeviceToHost));
+        if (d.n_oe) QSP_HIP(hipMemcpy(p->oe_level_h.data(), d.oe_level, d.n_oe, hipMemcpyDeviceToHost));
+    }
     p->host_stale = false;
     build_index(p);
     return QSP_OK;
@@ -3585,6 +3596,17 @@ static int allreduce_gather(qsp_ba_problem* p, double* a, size_t na, double* b, 
 static int set_shard_common(qsp_ba_problem* p, int32_t rank, int32_t world) {
     QSP_HIP(hipSetDevice(p->device));
     const Dev& d = p->d;
+    // Sharding changes how the next solve is computed, never the caller's levels.  upload_levels() below rewrites both device level
+    // arrays from the host's copies, so (1) the host's copies are brought up to date first, under the rank / world and the mask that
+    // are on the device NOW (a device-side stage boundary may have left them behind), (2) a zeroing that qsp_ba_set_levels(NULL..)
+    // left to the next k_edge_index is settled by that upload -- done later it would wipe the new mask -- and (3) a speculated stage
+    // boundary does not outlive the levels it was computed for.
+    {
+        const int rc = refresh_host_index(p);
+        if (rc) return rc;
+    }
+    p->levels_reset_pending = false;
+    p->tail_ready = false;
     p->rank = rank; p->world = world;
     p->edge_foreign.assign(std::max(d.n_edge, 1), 0);
     p->oe_foreign.assign(std::max(d.n_oe, 1), 0);
