@@ -753,6 +753,60 @@ int qsp_essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, 
                                const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale, double lambda,
                                double* E, double* chi, double* J, double* H, double* b, double* x, double* sim3_trial, double* info);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The map-point gate of LocalMapping::ProcessDetectedObjects (src/LocalMapping_util.cc:490-494, 508-511), batched: per
+ * object either MapObject::RemoveOutliersSimple + ComputeCuboidPCA (src/MapObject.cc:275-313, 361-475; mode QSP_GATE_PCA)
+ * or MapObject::RemoveOutliersModel (src/MapObject.cc:316-358; mode QSP_GATE_MODEL).  One workgroup per object, all objects
+ * of the call in one launch.  pts_world holds the world positions of each object's non-bad map points in
+ * GetMapPointsOnObject() order (the isBad / null filter stays with the caller, as for qsp_detections).
+ *   QSP_GATE_PCA:   erased[i] = |x_i - mean of all points| > 1 (the points RemoveOutliersSimple erases); no point at all, or
+ *     none left: status QSP_GATE_BAD (the reference calls SetBadFlag), every other output of the object 0.  Over the N
+ *     survivors: mean m and scatter sum (x-m)(x-m)^T, its eigenvectors v0 v1 v2 by ascending eigenvalue, R = [v1 | v0 | -v2],
+ *     column 0 negated if det R < 0, columns 0 and 1 negated if R[1][1] > 0.  SIGN CONVENTION: v2 enters with its
+ *     largest-magnitude component positive (the first such component on a tie); Eigen's own choice is an accident of its
+ *     iteration, and the other choice flips columns 0 and 2 of R together, which the yaw-flip hypotheses of the refinement
+ *     absorb.  X_o = R^-1 x; per axis the int(0.05 N)-th and int(0.95 N)-th order statistics (exactly the values std::sort
+ *     puts there, ties included; float32 keys taken about R^-1 m, which leaves the order and the differences as they are):
+ *     whl = x(hi) - x(lo), centre in the box = (x(hi) + x(lo)) / 2, centre_w = R centre; outlier[i] = on any axis
+ *     |X_o - centre| > 1.2 dim / 2, survivors only; T_wo_pca = [0.40 l R, centre_w; 0 0 0 1], the pose ComputeCuboidPCA(true)
+ *     would set -- the caller applies it or not.
+ *   QSP_GATE_MODEL: 10 vertices or fewer: status QSP_GATE_SKIPPED, no flag, whl 0.  Otherwise min / max per column of the
+ *     object's vertices, M = T_wo[:3,:3], whl = (max - min) cbrt(det M), x_o = M^-1 (x - T_wo[:3,3]) (what
+ *     invScale * Rwo.inverse() * x - invScale * Rwo.inverse() * two evaluates), outlier[i] = x_o outside
+ *     [1.2 xmin, 1.2 xmax] x [1.5 ymin, 1.5 ymax] x [1.2 zmin, 1.2 zmax] -- factors on the COORDINATES, as in the
+ *     reference.  erased is 0; R, centre_w and T_wo_pca are 0.
+ * Every sum is a double sum in a fixed order over the point index (no floating-point atomics), the eigenvectors are cyclic
+ * Jacobi in double, the inverses cofactors in double, and every output is rounded to float32 once: an object's outputs have
+ * the same bits alone, in any batch, at any position and next to objects of the other mode.  Up to QSP_GATE_LDS_POINTS
+ * points an object is staged on chip; beyond, every pass reads it again from memory (same results).  Host pointers.
+ * n_obj == 0 is QSP_OK and touches nothing.  Null in / out / mode / pts_off (or pts_world with points present), n_obj < 0,
+ * offsets that do not start at 0 or decrease, a mode outside {0, 1}, a MODEL object while T_wo, vert_off or verts is NULL:
+ * QSP_ERR_INVALID.  More than 2^20 points in one object: QSP_ERR_UNSUPPORTED, decided on the offsets before any point is
+ * read.  No output is written unless the call returns QSP_OK.  Non-finite coordinates are the caller's problem: the flags
+ * and boxes of an object that holds one are unspecified. */
+enum { QSP_GATE_PCA = 0, QSP_GATE_MODEL = 1 };
+enum { QSP_GATE_OK = 0, QSP_GATE_BAD = 1, QSP_GATE_SKIPPED = 2 };
+enum { QSP_GATE_LDS_POINTS = 4096, QSP_GATE_MAX_POINTS = 1 << 20 };
+typedef struct {
+    int32_t n_obj;
+    const int32_t* mode;      /* (n_obj) */
+    const int32_t* pts_off;   /* (n_obj+1) */
+    const float* pts_world;   /* (pts_off[n_obj],3) */
+    const float* T_wo;        /* (n_obj,4,4) Sim3Two, row-major; read in MODEL mode only; may be NULL if no object is MODEL */
+    const int32_t* vert_off;  /* (n_obj+1); may be NULL if no object is MODEL */
+    const float* verts;       /* (vert_off[n_obj],3) */
+} qsp_object_gate_in;
+typedef struct {              /* any pointer may be NULL */
+    uint8_t* erased;          /* (pts_off[n_obj]) */
+    uint8_t* outlier;         /* (pts_off[n_obj]) */
+    float* whl;               /* (n_obj,3) */
+    float* R;                 /* (n_obj,3,3) PCA */
+    float* centre_w;          /* (n_obj,3) PCA */
+    float* T_wo_pca;          /* (n_obj,4,4) PCA */
+    int32_t* status;          /* (n_obj) */
+} qsp_object_gate_out;
+int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out);
+
 #ifdef __cplusplus
 }
 #endif

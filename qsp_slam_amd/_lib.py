@@ -100,6 +100,16 @@ class DetectionResults(C.Structure):
                 ("depth_obs", c_float_p), ("t_cam_obj_init", c_float_p)]
 
 
+class ObjectGateIn(C.Structure):
+    _fields_ = [("n_obj", C.c_int32), ("mode", c_int32_p), ("pts_off", c_int32_p), ("pts_world", c_float_p), ("T_wo", c_float_p),
+                ("vert_off", c_int32_p), ("verts", c_float_p)]
+
+
+class ObjectGateOut(C.Structure):
+    _fields_ = [("erased", c_uint8_p), ("outlier", c_uint8_p), ("whl", c_float_p), ("R", c_float_p), ("centre_w", c_float_p),
+                ("T_wo_pca", c_float_p), ("status", c_int32_p)]
+
+
 SYMBOLS = [
     "qsp_last_error", "qsp_version", "qsp_device_count",
     "qsp_decoder_create", "qsp_decoder_destroy", "qsp_decoder_set_option", "qsp_decoder_get_counter", "qsp_decode_sdf",
@@ -114,7 +124,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages",
+    "qsp_sim3_optimize_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -204,6 +214,7 @@ def lib():
                                                c_double_p, C.POINTER(EssentialTrace)]
     L.qsp_essential_graph_stages.argtypes = [C.c_int, C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_int32_p, c_double_p,
                                              C.c_int32, C.c_double] + [c_double_p] * 8
+    L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]
     L.qsp_ba_destroy.restype = None

@@ -1,7 +1,8 @@
-// c_abi.cpp -- library-wide C-ABI entry points (version, error text, device count).
+// c_abi.cpp -- library-wide C-ABI entry points (version, error text, device count) and the object map-point gate.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "object_gate.hpp"
 
 namespace qsp {
 std::string& last_error_ref() {
@@ -38,4 +39,7 @@ extern "C" int qsp_essential_graph_stages(int device, int32_t n_kf, const double
                                           double* sim3_trial, double* info) {
     return qsp::essential_graph_stages(device, n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, lambda, E, chi, J, H, b, x,
                                        sim3_trial, info);
+}
+extern "C" int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out) {
+    return qsp::object_gates(device, in, out);
 }
