@@ -707,6 +707,34 @@ int qsp_sim3_optimize_batch(int device, int32_t n_cand, const int32_t* match_off
                             uint8_t* inlier, int32_t* n_inliers, qsp_sim3_trace* trace);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Sim3 RANSAC of loop candidates, batched: Sim3Solver (src/Sim3Solver.cc) for every candidate key frame of
+ * LoopClosing::ComputeSim3 in ONE call -- one wave per (candidate, hypothesis), then one wave per candidate.  Per hypothesis
+ * ComputeSim3 (:226-337: Horn's closed form on three pairs; FP64 from the float32 inputs, the eigenvector of N by cyclic Jacobi,
+ * T12 / T21 rounded to float32 once) and CheckInliers (:340-364: a match is an inlier when |p1 - cam1(T12 X2c)|^2 < maxErr1 and
+ * |cam2(T21 X1c) - p2|^2 < maxErr2, strict, in float32 as the reference evaluates it; p = cam(Xc) and maxErr = 9.210 sigma2 are
+ * derived on the device as the constructor does, :81-109).  The result of candidate c is its FIRST hypothesis with more than
+ * min_inliers inliers, which is what iterate() returns however its calls are sliced.
+ *   match_off (n_cand + 1): candidate c owns the matches [match_off[c], match_off[c+1]); starts at 0, never decreases
+ *   trip_off (n_cand + 1), triples (trip_off[n_cand],3): the caller's random triples, match indices local to the candidate, three
+ *       different ones each; n_its (n_cand): how many of them candidate c evaluates (mRansacMaxIts), at most 1024
+ *   K1, K2 (n_cand,4) fx fy cx cy; X1c, X2c (n_match,3) the matched points in their own camera frames; sigma2_1, sigma2_2
+ *       (n_match) mvLevelSigma2[octave] of the two key points
+ *   first_it (n_cand) out: the 1-based iteration of the first success, 0 = none; R12 (n_cand,9) row-major, t12 (n_cand,3), s12
+ *       (n_cand): mR12i, mt12i, ms12i of that hypothesis (zeros when none; s12 = 1 exactly under fix_scale); inlier (n_match):
+ *       its flags (zeros when none); n_inliers (n_cand): its count
+ *   hyp_inliers (trip_off[n_cand]) out or NULL: the count of every hypothesis evaluated (0 beyond n_its): the tests' tap.
+ * What the reference leaves in mBest* after a run that never succeeds is not reproduced.  A triple whose points coincide gives
+ * NaN and counts 0; so does every comparison against a point with z == 0.  A candidate's result has the same bits alone, in any
+ * batch and at any position.  Host pointers.  n_cand == 0 is QSP_OK and touches nothing; a candidate without matches or with
+ * n_its == 0 returns first_it 0.  Null pointers, n_cand < 0, offsets that do not start at 0 or decrease, n_its[c] < 0 or above
+ * trip_off[c+1] - trip_off[c] or above 1024, a triple index outside the candidate, a triple with two equal indices:
+ * QSP_ERR_INVALID.  No output is written unless the call returns QSP_OK. */
+int qsp_sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, const int32_t* n_its, const int32_t* trip_off,
+                          const int32_t* triples, const float* K1, const float* K2, const float* X1c, const float* X2c,
+                          const float* sigma2_1, const float* sigma2_2, int32_t min_inliers, int32_t fix_scale, int32_t* first_it,
+                          float* R12, float* t12, float* s12, uint8_t* inlier, int32_t* n_inliers, int32_t* hyp_inliers);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Essential-graph optimisation: Optimizer::OptimizeEssentialGraph, src/Optimizer.cc:785-1048, from initializeOptimization() to
  * the corrected map points.  n_kf VertexSim3Expmap in hessian order (ascending key-frame id), n_edge EdgeSim3 in insertion
  * order with error log(meas * S[v0] * S[v1]^-1), identity information, no robust kernel, g2o's numeric Jacobians (central

@@ -831,5 +831,139 @@ public:
     }
 };
 
+// Sim3Solver (src/Sim3Solver.cc) for ALL candidate key frames of LoopClosing::ComputeSim3 in one library call
+// (qsp_sim3_ransac_batch), in place of the round-robin of iterate(5) calls of src/LoopClosing.cc:292-352.  Not a member of
+// class Optimizer, so the drop-in does not change.
+class Sim3SolverHip {
+public:
+    struct Candidate {
+        int N = 0;                       // matches the constructor kept (mvpMapPoints1.size())
+        int nIterations = 0;             // mRansacMaxIts; 0 where iterate() returns at once (N < minInliers, :146-150)
+        int first_it = 0;                // the 1-based iteration iterate() returned a Sim3 at, 0 = never
+        float R[9] = {0}, t[3] = {0}, s = 0;     // GetEstimatedRotation / Translation / Scale of that iteration
+        std::vector<bool> vbInliers;     // size mN1, set through mvnIndices1 as :195-197 does
+        int nInliers = 0;
+    };
+    struct Result {
+        std::vector<Candidate> cand;     // per entry of vpKF2
+        std::vector<int> order;          // the successful candidates as the round-robin meets them: by ((first_it + 4) / 5, index)
+    };
+
+    // SetRansacParameters, :114-138
+    static int Iterations(int N, double probability = 0.99, int minInliers = 20, int maxIterations = 300) {
+        if (N < minInliers || N < 3) return 0;          // (fewer than three matches: no triple to draw, whatever minInliers says)
+        int nIterations;
+        if (minInliers == N) {
+            nIterations = 1;
+        } else {
+            const float epsilon = (float)minInliers / N;
+            nIterations = (int)std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3)));
+        }
+        return std::max(1, std::min(nIterations, maxIterations));
+    }
+
+    // vvpMatches12[c]: vpMatched12 of candidate vpKF2[c] (what the Sim3Solver constructor takes).  draw(lo, hi): an integer of
+    // [lo, hi], DUtils::Random::RandomInt in production; per candidate in turn it is asked for the three indices of every
+    // iteration, as :163-177 asks.  Returns the qsp status; on error `out` has not been touched.
+    template <typename KF, typename MP, typename Draw>
+    static int FindBatch(KF* pKF1, const std::vector<KF*>& vpKF2, const std::vector<std::vector<MP*>>& vvpMatches12, const bool bFixScale,
+                         Draw draw, Result& out, const int minInliers = 20, const int maxIterations = 300, const double probability = 0.99) {
+        using namespace qsp_shim;
+        const size_t nc = vpKF2.size();
+        if (vvpMatches12.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] Sim3SolverHip::FindBatch: %zu candidates, %zu match vectors\n", nc, vvpMatches12.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { out.cand.clear(); out.order.clear(); return QSP_OK; }
+        std::vector<int32_t> off(1, 0), its, toff(1, 0), triples;
+        std::vector<float> K1, K2, X1, X2, s1, s2;
+        std::vector<std::vector<int>> indices1(nc);                               // mvnIndices1
+        const std::vector<MP*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        const cv::Mat Rcw1 = pKF1->GetRotation(), tcw1 = pKF1->GetTranslation();
+        auto to_camera = [](const cv::Mat& R, const cv::Mat& t, const cv::Mat& X, std::vector<float>& o) {      // Rcw*X3Dw+tcw, float32
+            for (int r = 0; r < 3; ++r) {
+                const float rx = (float)((double)R.at<float>(r, 0) * X.at<float>(0) + (double)R.at<float>(r, 1) * X.at<float>(1) +
+                                         (double)R.at<float>(r, 2) * X.at<float>(2));
+                o.push_back(rx + t.at<float>(r));
+            }
+        };
+        for (size_t c = 0; c < nc; ++c) {
+            KF* pKF2 = vpKF2[c];
+            const std::vector<MP*>& vpMatched12 = vvpMatches12[c];
+            const cv::Mat Rcw2 = pKF2->GetRotation(), tcw2 = pKF2->GetTranslation();
+            const int mN1 = (int)vpMatched12.size();
+            for (int i1 = 0; i1 < mN1; ++i1) {                                     // :62-103
+                if (!vpMatched12[i1]) continue;
+                MP* pMP1 = vpKeyFrameMP1[i1];
+                MP* pMP2 = vpMatched12[i1];
+                if (!pMP1) continue;
+                if (pMP1->isBad() || pMP2->isBad()) continue;
+                const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1), indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+                if (indexKF1 < 0 || indexKF2 < 0) continue;
+                s1.push_back(pKF1->mvLevelSigma2[pKF1->mvKeysUn[indexKF1].octave]);
+                s2.push_back(pKF2->mvLevelSigma2[pKF2->mvKeysUn[indexKF2].octave]);
+                indices1[c].push_back(i1);
+                to_camera(Rcw1, tcw1, pMP1->GetWorldPos(), X1);
+                to_camera(Rcw2, tcw2, pMP2->GetWorldPos(), X2);
+            }
+            const cv::Mat& mK1 = pKF1->mK;
+            const cv::Mat& mK2 = pKF2->mK;
+            const float k1[4] = {mK1.template at<float>(0, 0), mK1.template at<float>(1, 1), mK1.template at<float>(0, 2), mK1.template at<float>(1, 2)};
+            const float k2[4] = {mK2.template at<float>(0, 0), mK2.template at<float>(1, 1), mK2.template at<float>(0, 2), mK2.template at<float>(1, 2)};
+            K1.insert(K1.end(), k1, k1 + 4);
+            K2.insert(K2.end(), k2, k2 + 4);
+            const int N = (int)indices1[c].size();
+            const int n_its = Iterations(N, probability, minInliers, maxIterations);
+            std::vector<int32_t> avail;
+            for (int it = 0; it < n_its; ++it) {                                   // :163-177
+                avail.resize(N);
+                for (int i = 0; i < N; ++i) avail[i] = i;
+                for (int i = 0; i < 3; ++i) {
+                    const int randi = draw(0, (int)avail.size() - 1);
+                    triples.push_back(avail[randi]);
+                    avail[randi] = avail.back();
+                    avail.pop_back();
+                }
+            }
+            off.push_back(off.back() + N);
+            its.push_back(n_its);
+            toff.push_back(toff.back() + n_its);
+        }
+        const size_t nm = (size_t)off.back();
+        std::vector<int32_t> first(nc), n_in(nc);
+        std::vector<float> R(9 * nc), t(3 * nc), s(nc);
+        std::vector<uint8_t> inlier(nm + 1);
+        for (std::vector<float>* v : {&X1, &X2, &s1, &s2}) v->push_back(0.f);      // data() of an empty vector may be null
+        triples.push_back(0);
+        const int rc = report("qsp_sim3_ransac_batch",
+                              qsp_sim3_ransac_batch(OptimizerHip::device(), (int32_t)nc, off.data(), its.data(), toff.data(), triples.data(),
+                                                    K1.data(), K2.data(), X1.data(), X2.data(), s1.data(), s2.data(), minInliers,
+                                                    bFixScale ? 1 : 0, first.data(), R.data(), t.data(), s.data(), inlier.data(),
+                                                    n_in.data(), nullptr));
+        if (rc != QSP_OK) return rc;
+        out.cand.assign(nc, Candidate());
+        out.order.clear();
+        for (size_t c = 0; c < nc; ++c) {
+            Candidate& C = out.cand[c];
+            C.N = (int)indices1[c].size();
+            C.nIterations = its[c];
+            C.first_it = first[c];
+            C.vbInliers.assign(vvpMatches12[c].size(), false);
+            if (!first[c]) continue;
+            for (int i = 0; i < 9; ++i) C.R[i] = R[9 * c + i];
+            for (int i = 0; i < 3; ++i) C.t[i] = t[3 * c + i];
+            C.s = s[c];
+            C.nInliers = n_in[c];
+            for (int e = 0; e < C.N; ++e)
+                if (inlier[off[c] + e]) C.vbInliers[indices1[c][e]] = true;        // :195-197
+            out.order.push_back((int)c);
+        }
+        // candidate c succeeds in the round-robin pass (first_it + 4) / 5 (five iterations per visit); within a pass in index order
+        std::stable_sort(out.order.begin(), out.order.end(),
+                         [&](int a, int b) { return (out.cand[a].first_it + 4) / 5 < (out.cand[b].first_it + 4) / 5; });
+        return QSP_OK;
+    }
+};
+
 }  // namespace ORB_SLAM2
 #endif  // QSP_OPTIMIZER_SHIM_H

@@ -124,7 +124,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -209,6 +209,9 @@ def lib():
                                           c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p, c_double_p, c_int32_p, c_double_p]
     L.qsp_sim3_optimize_batch.argtypes = [C.c_int, C.c_int32, c_int32_p] + [c_double_p] * 9 + [C.c_double, C.c_int32, c_double_p,
                                                                                                  c_uint8_p, c_int32_p, C.POINTER(Sim3Trace)]
+    L.qsp_sim3_ransac_batch.argtypes = [C.c_int, C.c_int32] + [c_int32_p] * 4 + [c_float_p] * 6 + [C.c_int32, C.c_int32, c_int32_p,
+                                                                                                    c_float_p, c_float_p, c_float_p,
+                                                                                                    c_uint8_p, c_int32_p, c_int32_p]
     L.qsp_essential_graph_optimize.argtypes = [C.c_int, C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_int32_p, c_double_p,
                                                C.c_int32, C.c_int32, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p,
                                                c_double_p, C.POINTER(EssentialTrace)]

@@ -255,6 +255,78 @@ def optimize_sim3(candidate, th2, fix_scale, device=0, trace=False):
     return optimize_sim3_batch([candidate], th2, fix_scale, device=device, trace=trace)[0]
 
 
+def sim3_ransac_iterations(n, prob=0.99, min_inliers=20, max_its=300):
+    """Sim3Solver::SetRansacParameters (reference src/Sim3Solver.cc:114-138): the iterations a candidate of n kept matches runs,
+    with the reference's float epsilon.  0 below min_inliers matches: iterate() returns nothing there (:146-150)."""
+    n = int(n)
+    if n < min_inliers:
+        return 0
+    if n == min_inliers:
+        its = 1
+    else:
+        eps = float(np.float32(min_inliers) / np.float32(n))                       # float epsilon = (float)mRansacMinInliers/N
+        its = int(np.ceil(np.log(1.0 - prob) / np.log(1.0 - eps ** 3)))
+    return max(1, min(its, int(max_its)))
+
+
+def draw_triples(n, its, rng):
+    """The minimal sets of `its` iterations over n matches, drawn as iterate() draws them (:163-177: an index of the available
+    list, which then takes the list's last entry and shrinks), from a numpy Generator.  (its,3) int32, three different indices."""
+    out = np.zeros((int(its), 3), np.int32)
+    for h in range(int(its)):
+        avail = list(range(int(n)))
+        for i in range(3):
+            r = int(rng.integers(0, len(avail)))                                   # RandomInt(0, size - 1)
+            out[h, i] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return out
+
+
+def sim3_ransac_batch(cands, min_inliers=20, fix_scale=False, counts=False, device=0):
+    """Sim3Solver (reference src/Sim3Solver.cc) for every loop candidate in ONE call (qsp_sim3_ransac_batch, include/qsp_hip.h).
+    `cands`: list of dicts with K1, K2 (4,) fx fy cx cy; X1c, X2c (n,3) the matched points in their own camera frames; sigma2_1,
+    sigma2_2 (n,) mvLevelSigma2 of the key points' octaves; triples (k,3) the minimal sets (draw_triples); n_its, the iterations
+    to run (default k; sim3_ransac_iterations).  Returns one dict per candidate: first_it (1-based, 0 = no hypothesis had more
+    than min_inliers inliers), R (3,3), t (3,), s, inlier (n,) uint8, n_inliers and, with counts=True, hyp_inliers (k,), the count
+    of every hypothesis."""
+    nc = len(cands)
+    if nc == 0:
+        return []
+    f32 = lambda key, w: [np.asarray(c[key], np.float32).reshape(-1, w) for c in cands]
+    X1, X2, s1, s2 = f32("X1c", 3), f32("X2c", 3), f32("sigma2_1", 1), f32("sigma2_2", 1)
+    n = [len(a) for a in X1]
+    for arrs in (X2, s1, s2):
+        if [len(a) for a in arrs] != n:
+            raise ValueError("sim3_ransac_batch: the match arrays of a candidate differ in length")
+    tri = [np.asarray(c["triples"], np.int32).reshape(-1, 3) for c in cands]
+    its = np.array([int(c.get("n_its", len(t))) for c, t in zip(cands, tri)], np.int32)
+    off, toff = np.zeros(nc + 1, np.int32), np.zeros(nc + 1, np.int32)
+    off[1:], toff[1:] = np.cumsum(n), np.cumsum([len(t) for t in tri])
+    nm, nt = int(off[-1]), int(toff[-1])
+    cat = lambda arrs, dt: _arr(np.concatenate(arrs), dt)
+    X1, X2, s1, s2, tri = cat(X1, np.float32), cat(X2, np.float32), cat(s1, np.float32), cat(s2, np.float32), cat(tri, np.int32)
+    K1 = _arr(np.stack([np.asarray(c["K1"], np.float32).reshape(4) for c in cands]), np.float32)
+    K2 = _arr(np.stack([np.asarray(c["K2"], np.float32).reshape(4) for c in cands]), np.float32)
+    first, ninl = np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+    R, t, s = np.zeros((nc, 9), np.float32), np.zeros((nc, 3), np.float32), np.zeros(nc, np.float32)
+    inlier = np.zeros(max(nm, 1), np.uint8)
+    hyp = np.zeros(max(nt, 1), np.int32) if counts else None
+    _lib.check(_lib.lib().qsp_sim3_ransac_batch(int(device), nc, _lib.i32ptr(off), _lib.i32ptr(its), _lib.i32ptr(toff), _lib.i32ptr(tri),
+                                                _lib.fptr(K1), _lib.fptr(K2), _lib.fptr(X1), _lib.fptr(X2), _lib.fptr(s1), _lib.fptr(s2),
+                                                int(min_inliers), 1 if fix_scale else 0, _lib.i32ptr(first), _lib.fptr(R), _lib.fptr(t),
+                                                _lib.fptr(s), _lib.u8ptr(inlier), _lib.i32ptr(ninl),
+                                                _lib.i32ptr(hyp) if counts else None))
+    res = []
+    for c in range(nc):
+        r = dict(first_it=int(first[c]), R=R[c].reshape(3, 3).copy(), t=t[c].copy(), s=np.float32(s[c]),
+                 inlier=inlier[off[c]:off[c + 1]].copy(), n_inliers=int(ninl[c]))
+        if counts:
+            r["hyp_inliers"] = hyp[toff[c]:toff[c + 1]].copy()
+        res.append(r)
+    return res
+
+
 def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
                              device=0):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map

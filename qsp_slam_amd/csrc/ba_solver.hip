@@ -4295,6 +4295,7 @@ extern "C" int qsp_ba_set_deterministic(qsp_ba_problem* p, int on) {
 
 #include "ellipsoid_fit.hpp"
 #include "sim3_opt.hpp"
+#include "sim3_ransac.hpp"
 #include "essential_graph.hpp"
 
 #ifdef QSP_CB_STAMPS

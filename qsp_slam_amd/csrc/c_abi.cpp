@@ -17,6 +17,11 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
 int essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
                            const int32_t* edge_v1, const double* meas, int32_t fix_scale, double lambda, double* E, double* chi, double* J,
                            double* H, double* b, double* x, double* sim3_trial, double* info);
+// csrc/sim3_ransac.hpp (compiled there as well)
+int sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, const int32_t* n_its, const int32_t* trip_off,
+                      const int32_t* triples, const float* K1, const float* K2, const float* X1c, const float* X2c, const float* sigma2_1,
+                      const float* sigma2_2, int32_t min_inliers, int32_t fix_scale, int32_t* first_it, float* R12, float* t12, float* s12,
+                      uint8_t* inlier, int32_t* n_inliers, int32_t* hyp_inliers);
 }  // namespace qsp
 
 extern "C" const char* qsp_last_error(void) { return qsp::last_error_ref().c_str(); }
@@ -39,6 +44,14 @@ extern "C" int qsp_essential_graph_stages(int device, int32_t n_kf, const double
                                           double* sim3_trial, double* info) {
     return qsp::essential_graph_stages(device, n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, lambda, E, chi, J, H, b, x,
                                        sim3_trial, info);
+}
+extern "C" int qsp_sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, const int32_t* n_its, const int32_t* trip_off,
+                                     const int32_t* triples, const float* K1, const float* K2, const float* X1c, const float* X2c,
+                                     const float* sigma2_1, const float* sigma2_2, int32_t min_inliers, int32_t fix_scale,
+                                     int32_t* first_it, float* R12, float* t12, float* s12, uint8_t* inlier, int32_t* n_inliers,
+                                     int32_t* hyp_inliers) {
+    return qsp::sim3_ransac_batch(device, n_cand, match_off, n_its, trip_off, triples, K1, K2, X1c, X2c, sigma2_1, sigma2_2, min_inliers,
+                                  fix_scale, first_it, R12, t12, s12, inlier, n_inliers, hyp_inliers);
 }
 extern "C" int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out) {
     return qsp::object_gates(device, in, out);
