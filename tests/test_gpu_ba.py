@@ -389,7 +389,9 @@ def test_cholesky_chain_and_step_forms_give_the_same_bits(size):
     """QSP_BA_OPT_CHOLESKY_CHAIN: the factorisation as one launch (a resident chain workgroup + tile workgroups that take
     tickets, k_chol_solve) against one launch per block step (2, 5 and 19 block rows): the same operations in the same order, so
     the whole two-stage BA -- chi2 and lambda per iteration, trials, final poses and points -- is identical to the bit.  The
-    chain form must be the one in use (a silent fall-back to the step form would make this test vacuous)."""
+    chain form must be the one in use (a silent fall-back to the step form would make this test vacuous).  The other block counts
+    (1, 2, 3, 4, 6, 18, the first with a second ticket per tile workgroup, 31 and 32), each also against the oracle:
+    tests/test_gpu_ba_blocks.py."""
     import bench
     from qsp_slam_amd.ba import BaProblem
     w = bench.WORKLOADS[size]
