@@ -835,6 +835,76 @@ typedef struct {              /* any pointer may be NULL */
 } qsp_object_gate_out;
 int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1102-1326) for every loop candidate of a key frame in ONE call: the step of
+ * LoopClosing::ComputeSim3 between qsp_sim3_ransac_batch and qsp_sim3_optimize_batch.  Key frame 1 (the current one) is given
+ * once, key frame 2 per candidate.  One wave per (candidate, direction, source slot), then one thread per slot of key frame 1
+ * for the agreement: two launches.
+ * Per direction (1 -> 2 with sR21 = (1.0 / s12) R12^T -- a double factor, rounded to float32 once -- and t21 = -sR21 t12;
+ * 2 -> 1 with sR12 = s12 R12 and t12) and per source slot with has_point && !pre, in the reference's float32 arithmetic (matrix
+ * rows summed in double and rounded once, t added in float32; 1.0 / z and the norm in double, rounded once; u = fx * x + cx as a
+ * separate multiply and add):
+ *   skip when z < 0, when (u, v) is outside [min_x, max_x) x [min_y, max_y) of the TARGET frame, when dist3D < dist_min_inv or
+ *   dist3D > dist_max_inv;  level = clamp(ceil(logf(dist_max / dist3D) / log_scale), 0, n_levels - 1) and radius = th *
+ *   scale_factors[level] with the TARGET frame's log_scale, n_levels and scale_factors (MapPoint::PredictScale);
+ *   a target key point is eligible when its own cell (round((x - min_x) * grid_w_inv), round((y - min_y) * grid_h_inv)) lies in
+ *   the grid (Frame::PosInGrid: others were never filed) and in the range KeyFrame::GetFeaturesInArea visits, |kx - u| < radius
+ *   && |ky - v| < radius (strict) and level - 1 <= octave <= level;  the best is the eligible key point of minimum Hamming
+ *   distance to mp_desc over the 256 bits, ties to the first in the reference's traversal order (cell x, cell y, index);  it is
+ *   kept when the distance is <= 100 (TH_HIGH).
+ * pre2 only keeps a slot from being a SOURCE of pass 2 -> 1; as a target it is matched like any other (as in the reference).
+ * match12[c][i1] = best1[i1] when best1[i1] >= 0 && best2[best1[i1]] == i1, else -1 (slots with pre1 set: -1, the caller keeps
+ * what it had); n_found[c] counts them.  K is key frame 1's, used for BOTH directions, as the reference does.
+ * A candidate's outputs have the same bits alone, in any batch and at any position.  Host pointers.  n_cand == 0 is QSP_OK and
+ * touches nothing.  Null pointers (arrays of a frame with n == 0 may be NULL; the tap is four arrays or four NULLs), n_cand < 0,
+ * n < 0 or n > 2^26, off2 that does not start at 0, decreases or does not step by kf2[c].n, a key point's octave outside
+ * [0, n_levels), n_levels outside [1, 16], a grid outside 1..64 x 1..64: QSP_ERR_INVALID.  More than 2^31 - 1 slots in one
+ * call: QSP_ERR_UNSUPPORTED.  No output is written unless the call returns QSP_OK. */
+typedef struct {
+    int32_t n;                    /* key points = map-point slots (KeyFrame::N), at most 2^26 */
+    const float* kp;              /* (n,2) mvKeysUn[i].pt */
+    const int32_t* octave;        /* (n) mvKeysUn[i].octave */
+    const uint8_t* desc;          /* (n,32) rows of mDescriptors */
+    float min_x, max_x, min_y, max_y;     /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    int32_t grid_cols, grid_rows;         /* mnGridCols, mnGridRows: at most 64 x 64 */
+    float grid_w_inv, grid_h_inv;         /* mfGridElementWidthInv, mfGridElementHeightInv */
+    int32_t n_levels;                     /* mnScaleLevels, at most 16 */
+    float log_scale;                      /* mfLogScaleFactor */
+    const float* scale_factors;   /* (n_levels) mvScaleFactors */
+    float Rcw[9], tcw[3];                 /* GetRotation() row-major, GetTranslation() */
+    /* the map point of each slot (GetMapPointMatches()[i]) */
+    const uint8_t* has_point;     /* (n) 1 = pMP && !pMP->isBad(); the rest of a slot without one is not read */
+    const float* Xw;              /* (n,3) GetWorldPos() */
+    const float* dist_min_inv;    /* (n) GetMinDistanceInvariance() */
+    const float* dist_max_inv;    /* (n) GetMaxDistanceInvariance() */
+    const float* dist_max;        /* (n) mfMaxDistance, what PredictScale divides */
+    const uint8_t* mp_desc;       /* (n,32) GetDescriptor() */
+} qsp_orb_frame;
+typedef struct {
+    int32_t n_cand;
+    const qsp_orb_frame* kf1;     /* one: shared by all candidates */
+    const qsp_orb_frame* kf2;     /* (n_cand) */
+    const int32_t* off2;          /* (n_cand+1): candidate c owns [off2[c], off2[c+1]) of pre2 / best2 / dist2; steps by kf2[c].n */
+    const float* K;               /* (n_cand,4) fx fy cx cy of key frame 1 */
+    const float* s12;             /* (n_cand) */
+    const float* R12;             /* (n_cand,9) row-major */
+    const float* t12;             /* (n_cand,3) */
+    const float* th;              /* (n_cand) the reference passes 7.5 */
+    const uint8_t* pre1;          /* (n_cand,kf1->n) vbAlreadyMatched1 */
+    const uint8_t* pre2;          /* (off2[n_cand]) vbAlreadyMatched2 */
+} qsp_search_sim3_in;
+typedef struct {
+    int32_t* match12;             /* (n_cand,kf1->n) index in key frame 2 of each newly agreed match, else -1 */
+    int32_t* n_found;             /* (n_cand) */
+    /* the tests' tap, all four or all NULL: vnMatch1 / vnMatch2 before the agreement step and their Hamming distances (-1 where no
+     * key point was eligible; a distance above 100 is reported with best -1) */
+    int32_t* best1;               /* (n_cand,kf1->n) */
+    int32_t* dist1;               /* (n_cand,kf1->n) */
+    int32_t* best2;               /* (off2[n_cand]) */
+    int32_t* dist2;               /* (off2[n_cand]) */
+} qsp_search_sim3_out;
+int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -965,5 +965,132 @@ public:
     }
 };
 
+// ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1102-1326) for ALL candidate key frames of LoopClosing::ComputeSim3 in one library
+// call (qsp_search_by_sim3_batch): the step between Sim3SolverHip::FindBatch and the batched OptimizeSim3.  Not a member of
+// class ORBmatcher, so the drop-in does not change.
+class OrbMatcherHip {
+    struct FrameArrays {                 // what a qsp_orb_frame points into
+        std::vector<float> kp, sf, Xw, dmin, dmaxi, dmax;
+        std::vector<int32_t> octave;
+        std::vector<uint8_t> desc, has, mpd;
+    };
+    // Gathers what SearchBySim3 reads of a key frame and of the map points in its slots, with the reference's getters.
+    // mfMaxDistance is protected in MapPoint.h: dist_max = GetMaxDistanceInvariance() / 1.2f (at most one float32 ulp off).
+    template <typename KF, typename MP>
+    static void gather(KF* pKF, const std::vector<MP*>& vpMP, FrameArrays& a, qsp_orb_frame& f) {
+        const int n = (int)vpMP.size();
+        a.kp.resize(2 * (size_t)n + 1); a.octave.resize((size_t)n + 1); a.desc.assign(32 * (size_t)n + 1, 0);
+        a.has.assign((size_t)n + 1, 0); a.Xw.assign(3 * (size_t)n + 1, 0.f); a.mpd.assign(32 * (size_t)n + 1, 0);
+        a.dmin.assign((size_t)n + 1, 0.f); a.dmaxi.assign((size_t)n + 1, 0.f); a.dmax.assign((size_t)n + 1, 0.f);
+        for (int i = 0; i < n; ++i) {
+            a.kp[2 * i] = pKF->mvKeysUn[i].pt.x;
+            a.kp[2 * i + 1] = pKF->mvKeysUn[i].pt.y;
+            a.octave[i] = pKF->mvKeysUn[i].octave;
+            const auto row = pKF->mDescriptors.row(i);
+            for (int b = 0; b < 32; ++b) a.desc[32 * (size_t)i + b] = row.template at<unsigned char>(0, b);
+            MP* pMP = vpMP[i];
+            if (!pMP || pMP->isBad()) continue;
+            a.has[i] = 1;
+            const cv::Mat X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; ++r) a.Xw[3 * (size_t)i + r] = X.template at<float>(r);
+            a.dmin[i] = pMP->GetMinDistanceInvariance();
+            a.dmaxi[i] = pMP->GetMaxDistanceInvariance();
+            a.dmax[i] = a.dmaxi[i] / 1.2f;
+            const auto d = pMP->GetDescriptor();
+            for (int b = 0; b < 32; ++b) a.mpd[32 * (size_t)i + b] = d.template at<unsigned char>(0, b);
+        }
+        a.sf.assign(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.end());
+        a.sf.push_back(0.f);
+        f.n = n;
+        f.kp = a.kp.data(); f.octave = a.octave.data(); f.desc = a.desc.data();
+        f.min_x = (float)pKF->mnMinX; f.max_x = (float)pKF->mnMaxX; f.min_y = (float)pKF->mnMinY; f.max_y = (float)pKF->mnMaxY;
+        f.grid_cols = pKF->mnGridCols; f.grid_rows = pKF->mnGridRows;
+        f.grid_w_inv = pKF->mfGridElementWidthInv; f.grid_h_inv = pKF->mfGridElementHeightInv;
+        f.n_levels = pKF->mnScaleLevels; f.log_scale = pKF->mfLogScaleFactor; f.scale_factors = a.sf.data();
+        const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) f.Rcw[3 * r + c] = R.template at<float>(r, c);
+            f.tcw[r] = t.template at<float>(r);
+        }
+        f.has_point = a.has.data(); f.Xw = a.Xw.data(); f.dist_min_inv = a.dmin.data(); f.dist_max_inv = a.dmaxi.data();
+        f.dist_max = a.dmax.data(); f.mp_desc = a.mpd.data();
+    }
+
+public:
+    // vvpMatches12[c]: vpMatches12 of candidate vpKF2[c] (size pKF1's N), updated in place as SearchBySim3 updates it; vnFound[c]:
+    // its return value.  Returns the qsp status; on error vvpMatches12 and vnFound have not been touched.
+    template <typename KF, typename MP>
+    static int SearchBySim3Batch(KF* pKF1, const std::vector<KF*>& vpKF2, std::vector<std::vector<MP*>>& vvpMatches12,
+                                 const std::vector<float>& vs12, const std::vector<cv::Mat>& vR12, const std::vector<cv::Mat>& vt12,
+                                 const float th, std::vector<int>& vnFound) {
+        using namespace qsp_shim;
+        const size_t nc = vpKF2.size();
+        if (vvpMatches12.size() != nc || vs12.size() != nc || vR12.size() != nc || vt12.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::SearchBySim3Batch: %zu candidates, but %zu / %zu / %zu / %zu arguments\n", nc,
+                         vvpMatches12.size(), vs12.size(), vR12.size(), vt12.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { vnFound.clear(); return QSP_OK; }
+        const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+        const size_t N1 = vpMapPoints1.size();
+        for (size_t c = 0; c < nc; ++c)
+            if (vvpMatches12[c].size() != N1) {
+                std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::SearchBySim3Batch: candidate %zu has %zu matches for %zu slots\n", c,
+                             vvpMatches12[c].size(), N1);
+                return QSP_ERR_INVALID;
+            }
+        FrameArrays a1;
+        std::vector<FrameArrays> a2(nc);
+        qsp_orb_frame f1;
+        std::vector<qsp_orb_frame> f2(nc);
+        std::vector<std::vector<MP*>> vvpMapPoints2(nc);
+        gather(pKF1, vpMapPoints1, a1, f1);
+        std::vector<int32_t> off2(1, 0);
+        std::vector<float> K, s12, R12, t12, vth;
+        std::vector<uint8_t> pre1(nc * N1 + 1, 0), pre2;
+        for (size_t c = 0; c < nc; ++c) {
+            vvpMapPoints2[c] = vpKF2[c]->GetMapPointMatches();
+            gather(vpKF2[c], vvpMapPoints2[c], a2[c], f2[c]);
+            const int N2 = (int)vvpMapPoints2[c].size();
+            pre2.resize(pre2.size() + N2, 0);
+            for (size_t i = 0; i < N1; ++i) {                                    // :1132-1142
+                MP* pMP = vvpMatches12[c][i];
+                if (!pMP) continue;
+                pre1[c * N1 + i] = 1;
+                const int idx2 = pMP->GetIndexInKeyFrame(vpKF2[c]);
+                if (idx2 >= 0 && idx2 < N2) pre2[(size_t)off2.back() + idx2] = 1;
+            }
+            off2.push_back(off2.back() + N2);
+            const float k[4] = {pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy};          // key frame 1's, for both directions (:1105-1108)
+            K.insert(K.end(), k, k + 4);
+            s12.push_back(vs12[c]);
+            for (int r = 0; r < 3; ++r) {
+                for (int q = 0; q < 3; ++q) R12.push_back(vR12[c].template at<float>(r, q));
+                t12.push_back(vt12[c].template at<float>(r));
+            }
+            vth.push_back(th);
+        }
+        pre2.push_back(0);                                                       // data() of an empty vector may be null
+        qsp_search_sim3_in in;
+        in.n_cand = (int32_t)nc; in.kf1 = &f1; in.kf2 = f2.data(); in.off2 = off2.data(); in.K = K.data(); in.s12 = s12.data();
+        in.R12 = R12.data(); in.t12 = t12.data(); in.th = vth.data(); in.pre1 = pre1.data(); in.pre2 = pre2.data();
+        std::vector<int32_t> match12(nc * N1 + 1), n_found(nc);
+        qsp_search_sim3_out out;
+        out.match12 = match12.data(); out.n_found = n_found.data();
+        out.best1 = out.dist1 = out.best2 = out.dist2 = nullptr;
+        const int rc = report("qsp_search_by_sim3_batch", qsp_search_by_sim3_batch(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        vnFound.assign(nc, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t i1 = 0; i1 < N1; ++i1) {
+                const int32_t idx2 = match12[c * N1 + i1];
+                if (idx2 >= 0) vvpMatches12[c][i1] = vvpMapPoints2[c][idx2];      // :1319
+            }
+            vnFound[c] = n_found[c];
+        }
+        return QSP_OK;
+    }
+};
+
 }  // namespace ORB_SLAM2
 #endif  // QSP_OPTIMIZER_SHIM_H

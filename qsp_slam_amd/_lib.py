@@ -110,6 +110,27 @@ class ObjectGateOut(C.Structure):
                 ("T_wo_pca", c_float_p), ("status", c_int32_p)]
 
 
+class OrbFrame(C.Structure):
+    _fields_ = [("n", C.c_int32), ("kp", c_float_p), ("octave", c_int32_p), ("desc", c_uint8_p),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("grid_w_inv", C.c_float), ("grid_h_inv", C.c_float),
+                ("n_levels", C.c_int32), ("log_scale", C.c_float), ("scale_factors", c_float_p),
+                ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
+                ("has_point", c_uint8_p), ("Xw", c_float_p), ("dist_min_inv", c_float_p), ("dist_max_inv", c_float_p),
+                ("dist_max", c_float_p), ("mp_desc", c_uint8_p)]
+
+
+class SearchSim3In(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("kf1", C.POINTER(OrbFrame)), ("kf2", C.POINTER(OrbFrame)), ("off2", c_int32_p),
+                ("K", c_float_p), ("s12", c_float_p), ("R12", c_float_p), ("t12", c_float_p), ("th", c_float_p),
+                ("pre1", c_uint8_p), ("pre2", c_uint8_p)]
+
+
+class SearchSim3Out(C.Structure):
+    _fields_ = [("match12", c_int32_p), ("n_found", c_int32_p), ("best1", c_int32_p), ("dist1", c_int32_p),
+                ("best2", c_int32_p), ("dist2", c_int32_p)]
+
+
 SYMBOLS = [
     "qsp_last_error", "qsp_version", "qsp_device_count",
     "qsp_decoder_create", "qsp_decoder_destroy", "qsp_decoder_set_option", "qsp_decoder_get_counter", "qsp_decode_sdf",
@@ -124,7 +145,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -217,6 +238,7 @@ def lib():
                                                c_double_p, C.POINTER(EssentialTrace)]
     L.qsp_essential_graph_stages.argtypes = [C.c_int, C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_int32_p, c_double_p,
                                              C.c_int32, C.c_double] + [c_double_p] * 8
+    L.qsp_search_by_sim3_batch.argtypes = [C.c_int, C.POINTER(SearchSim3In), C.POINTER(SearchSim3Out)]
     L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]

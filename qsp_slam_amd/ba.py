@@ -327,6 +327,78 @@ def sim3_ransac_batch(cands, min_inliers=20, fix_scale=False, counts=False, devi
     return res
 
 
+def _orb_frame(f, keep):
+    """qsp_orb_frame over the arrays of a frame dict (search_by_sim3_batch); `keep` holds what the pointers point into"""
+    n = int(np.size(f["octave"]))
+    a = dict(kp=_arr(np.reshape(f["kp"], (-1, 2)), np.float32), octave=_arr(np.reshape(f["octave"], -1), np.int32),
+             desc=_arr(np.reshape(f["desc"], (-1, 32)), np.uint8), sf=_arr(np.reshape(f["scale_factors"], -1), np.float32),
+             has_point=_arr(np.reshape(f["has_point"], -1), np.uint8), Xw=_arr(np.reshape(f["Xw"], (-1, 3)), np.float32),
+             dist_min_inv=_arr(np.reshape(f["dist_min_inv"], -1), np.float32), dist_max_inv=_arr(np.reshape(f["dist_max_inv"], -1), np.float32),
+             dist_max=_arr(np.reshape(f["dist_max"], -1), np.float32), mp_desc=_arr(np.reshape(f["mp_desc"], (-1, 32)), np.uint8))
+    for key, w in (("kp", 2), ("desc", 32), ("has_point", 1), ("Xw", 3), ("dist_min_inv", 1), ("dist_max_inv", 1), ("dist_max", 1),
+                   ("mp_desc", 32)):
+        if int(np.size(f[key])) != w * n:
+            raise ValueError("search_by_sim3_batch: %s does not hold %d values per key point" % (key, w))
+    keep.append(a)
+    o = _lib.OrbFrame()
+    o.n = n
+    o.kp, o.octave, o.desc = _lib.fptr(a["kp"]), _lib.i32ptr(a["octave"]), _lib.u8ptr(a["desc"])
+    o.min_x, o.max_x, o.min_y, o.max_y = [float(v) for v in f["bounds"]]
+    o.grid_cols, o.grid_rows = int(f["grid"][0]), int(f["grid"][1])
+    o.grid_w_inv, o.grid_h_inv = float(f["grid"][2]), float(f["grid"][3])
+    o.n_levels, o.log_scale, o.scale_factors = int(np.size(f["scale_factors"])), float(f["log_scale"]), _lib.fptr(a["sf"])
+    o.Rcw[:] = [float(v) for v in np.reshape(f["Rcw"], 9)]
+    o.tcw[:] = [float(v) for v in np.reshape(f["tcw"], 3)]
+    o.has_point, o.Xw, o.mp_desc = _lib.u8ptr(a["has_point"]), _lib.fptr(a["Xw"]), _lib.u8ptr(a["mp_desc"])
+    o.dist_min_inv, o.dist_max_inv, o.dist_max = _lib.fptr(a["dist_min_inv"]), _lib.fptr(a["dist_max_inv"]), _lib.fptr(a["dist_max"])
+    return o
+
+
+def search_by_sim3_batch(kf1, cands, tap=False, device=0):
+    """ORBmatcher::SearchBySim3 (reference src/ORBmatcher.cc:1102-1326) for every loop candidate in ONE call
+    (qsp_search_by_sim3_batch, include/qsp_hip.h).  A frame is a dict: kp (n,2), octave (n,), desc (n,32) uint8, bounds (min_x,
+    max_x, min_y, max_y), grid (cols, rows, width_inv, height_inv), log_scale, scale_factors (n_levels,), Rcw (3,3), tcw (3,) and
+    per slot has_point (n,), Xw (n,3), dist_min_inv, dist_max_inv, dist_max (n,), mp_desc (n,32) uint8.  `kf1` is the current key
+    frame; `cands`: list of dicts with kf2 (a frame), K (4,) fx fy cx cy of key frame 1, s12, R12 (3,3), t12 (3,), th (default 7.5),
+    pre1 (n1,), pre2 (n2,) (default: none set).  Returns one dict per candidate: match12 (n1,) int32 (-1 = none), n_found and,
+    with tap=True, best1, dist1 (n1,), best2, dist2 (n2,): the two passes before the agreement step."""
+    nc = len(cands)
+    if nc == 0:
+        return []
+    keep = []
+    f1 = _orb_frame(kf1, keep)
+    n1 = int(f1.n)
+    f2 = (_lib.OrbFrame * nc)(*[_orb_frame(c["kf2"], keep) for c in cands])
+    n2 = [int(f.n) for f in f2]
+    off2 = np.zeros(nc + 1, np.int32)
+    off2[1:] = np.cumsum(n2)
+    nm2 = int(off2[-1])
+    u8 = lambda c, key, n: (np.zeros(n, np.uint8) if c.get(key) is None else np.asarray(c[key]).astype(bool).astype(np.uint8).reshape(-1))
+    pre1, pre2 = [u8(c, "pre1", n1) for c in cands], [u8(c, "pre2", n) for c, n in zip(cands, n2)]
+    if [len(p) for p in pre1] != [n1] * nc or [len(p) for p in pre2] != n2:
+        raise ValueError("search_by_sim3_batch: pre1 / pre2 do not match the key-point counts")
+    pre1, pre2 = _arr(np.concatenate(pre1), np.uint8), _arr(np.concatenate(pre2), np.uint8)
+    K = _arr(np.stack([np.asarray(c["K"], np.float32).reshape(4) for c in cands]), np.float32)
+    s12 = _arr([c["s12"] for c in cands], np.float32)
+    R12 = _arr(np.stack([np.asarray(c["R12"], np.float32).reshape(9) for c in cands]), np.float32)
+    t12 = _arr(np.stack([np.asarray(c["t12"], np.float32).reshape(3) for c in cands]), np.float32)
+    th = _arr([c.get("th", 7.5) for c in cands], np.float32)
+    i = _lib.SearchSim3In(nc, C.pointer(f1), f2, _lib.i32ptr(off2), _lib.fptr(K), _lib.fptr(s12), _lib.fptr(R12), _lib.fptr(t12),
+                          _lib.fptr(th), _lib.u8ptr(pre1), _lib.u8ptr(pre2))
+    match, found = np.zeros(max(nc * n1, 1), np.int32), np.zeros(nc, np.int32)
+    b1, d1, b2, d2 = (np.zeros(max(n, 1), np.int32) for n in (nc * n1, nc * n1, nm2, nm2))
+    o = _lib.SearchSim3Out(_lib.i32ptr(match), _lib.i32ptr(found), *([_lib.i32ptr(a) for a in (b1, d1, b2, d2)] if tap else [None] * 4))
+    _lib.check(_lib.lib().qsp_search_by_sim3_batch(int(device), C.byref(i), C.byref(o)))
+    res = []
+    for c in range(nc):
+        r = dict(match12=match[c * n1:(c + 1) * n1].copy(), n_found=int(found[c]))
+        if tap:
+            r.update(best1=b1[c * n1:(c + 1) * n1].copy(), dist1=d1[c * n1:(c + 1) * n1].copy(),
+                     best2=b2[off2[c]:off2[c + 1]].copy(), dist2=d2[off2[c]:off2[c + 1]].copy())
+        res.append(r)
+    return res
+
+
 def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
                              device=0):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map

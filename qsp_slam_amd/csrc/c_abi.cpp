@@ -22,6 +22,8 @@ int sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, cons
                       const int32_t* triples, const float* K1, const float* K2, const float* X1c, const float* X2c, const float* sigma2_1,
                       const float* sigma2_2, int32_t min_inliers, int32_t fix_scale, int32_t* first_it, float* R12, float* t12, float* s12,
                       uint8_t* inlier, int32_t* n_inliers, int32_t* hyp_inliers);
+// csrc/search_sim3.hpp (compiled there as well)
+int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out);
 }  // namespace qsp
 
 extern "C" const char* qsp_last_error(void) { return qsp::last_error_ref().c_str(); }
@@ -52,6 +54,9 @@ extern "C" int qsp_sim3_ransac_batch(int device, int32_t n_cand, const int32_t* 
                                      int32_t* hyp_inliers) {
     return qsp::sim3_ransac_batch(device, n_cand, match_off, n_its, trip_off, triples, K1, K2, X1c, X2c, sigma2_1, sigma2_2, min_inliers,
                                   fix_scale, first_it, R12, t12, s12, inlier, n_inliers, hyp_inliers);
+}
+extern "C" int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out) {
+    return qsp::search_by_sim3_batch(device, in, out);
 }
 extern "C" int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out) {
     return qsp::object_gates(device, in, out);

@@ -1,0 +1,334 @@
+// search_sim3.hpp -- ORBmatcher::SearchBySim3 (reference src/ORBmatcher.cc:1102-1326) for ALL loop candidates of a key frame in one
+// call.  Included at the end of ba_solver.hip, beside sim3_ransac.hpp.
+//
+// The reference runs, per candidate, two serial passes (key frame 1 -> 2 and 2 -> 1): project a map point through the candidate
+// Sim3, walk the target frame's feature grid inside a level-dependent radius (KeyFrame::GetFeaturesInArea, KeyFrame.cc:570-609),
+// keep the Hamming-nearest ORB descriptor, then keep the mutual matches.  Neither pass writes anything the other iterations read,
+// so here ONE WAVE owns one (candidate, direction, source slot): all 64 lanes compute the slot's gates redundantly, then stride
+// over the target frame's key points.  No grid is built: a key point is eligible when its own cell (Frame::PosInGrid,
+// Frame.cc:419-429) lies inside the grid and inside the visited cell range, and the reference's traversal order -- ascending
+// (cell x, cell y, index) -- is carried in a 64-bit key next to the distance, so one wave min-reduction yields the reference's
+// `dist < bestDist` winner.  k_search_sim3_agree gathers the mutual matches and counts them.
+//
+// Every function below evaluates with contraction OFF: the float32 operations of the reference in its order.
+#pragma once
+#include <exception>
+
+namespace qsp {
+namespace search {
+
+constexpr int MAX_LEVELS = 16;
+constexpr int MAX_GRID = 64;
+constexpr int MAX_KEYPOINTS = 1 << 26;   // the key keeps the key-point index in 26 bits
+constexpr int TH_HIGH = 100;
+constexpr unsigned long long NO_KEY = ~0ull;
+
+struct FrameP {                       // one per frame: 0 is key frame 1, 1 + c key frame 2 of candidate c
+    int32_t off, n;                   // its key-point slots are [off, off + n) of the flat arrays
+    float min_x, max_x, min_y, max_y;
+    int32_t cols, rows;
+    float w_inv, h_inv;
+    int32_t n_levels;
+    float log_scale;
+    float sf[MAX_LEVELS];
+    float R[9], t[3];
+};
+
+struct CandP {
+    float K[4], s12, R12[9], t12[3], th;
+};
+
+struct In {
+    const FrameP* frame;              // [n_cand + 1]
+    const CandP* cand;                // [n_cand]
+    const int64_t* work_off;          // [n_cand + 1]: candidate c owns the waves [work_off[c], work_off[c + 1]): n1 + n2[c] of them
+    const int32_t* off2;              // [n_cand + 1]
+    const float* kp;                  // [n_slot][2]
+    const int32_t* octave;            // [n_slot]
+    const uint8_t* desc;              // [n_slot][32], 16-byte aligned
+    const uint8_t* has_point;         // [n_slot]
+    const float* Xw;                  // [n_slot][3]
+    const float *dist_min_inv, *dist_max_inv, *dist_max;   // [n_slot]
+    const uint8_t* mp_desc;           // [n_slot][32], 16-byte aligned
+    const uint8_t *pre1, *pre2;       // [n_cand][n1], [off2[n_cand]]
+    int32_t n_cand, n1;
+};
+
+// cv::Mat R * X as OpenCV's small-matrix product leaves it: the row product summed in double and rounded to float once
+__device__ inline float rowdot(const float* r, const float* X) {
+#pragma clang fp contract(off)
+    return (float)(((double)r[0] * (double)X[0] + (double)r[1] * (double)X[1]) + (double)r[2] * (double)X[2]);
+}
+
+// :1119-1121.  dir 0 (1 -> 2): M = sR21 = (1.0 / s12) * R12.t() (a double factor, rounded to float32 once), t = -sR21 * t12;
+// dir 1 (2 -> 1): M = sR12 = s12 * R12, t = t12
+__device__ inline void cand_transform(const CandP& C, int dir, float* M, float* t) {
+#pragma clang fp contract(off)
+    if (dir) {
+        for (int i = 0; i < 9; ++i) M[i] = C.s12 * C.R12[i];
+        for (int i = 0; i < 3; ++i) t[i] = C.t12[i];
+    } else {
+        const double is = 1.0 / (double)C.s12;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) M[3 * i + j] = (float)(is * (double)C.R12[3 * j + i]);
+        for (int i = 0; i < 3; ++i) t[i] = -rowdot(M + 3 * i, C.t12);
+    }
+}
+
+__device__ inline int popc128(const uint4& a, const uint4& b) {
+    return __popc(a.x ^ b.x) + __popc(a.y ^ b.y) + __popc(a.z ^ b.z) + __popc(a.w ^ b.w);
+}
+
+// 4 waves per workgroup, one wave per (candidate, direction, source slot)
+__global__ __launch_bounds__(256) void k_search_sim3_best(In in, int64_t n_work, int32_t* __restrict__ best1, int32_t* __restrict__ dist1,
+                                                          int32_t* __restrict__ best2, int32_t* __restrict__ dist2) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= n_work) return;
+    int lo = 0, hi = in.n_cand;                          // the candidate whose range holds w (empty ranges are stepped over)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (in.work_off[mid] <= w) lo = mid; else hi = mid;
+    }
+    const int c = lo;
+    const int32_t local = (int32_t)(w - in.work_off[c]);
+    const int dir = local >= in.n1;
+    const int32_t i = dir ? local - in.n1 : local;       // the source slot in its frame
+    const FrameP& S = in.frame[dir ? 1 + c : 0];         // source and target frames
+    const FrameP& T = in.frame[dir ? 0 : 1 + c];
+    const CandP& C = in.cand[c];
+    const int64_t out_at = dir ? (int64_t)in.off2[c] + i : (int64_t)c * in.n1 + i;
+    int32_t* const best = dir ? best2 : best1;
+    int32_t* const dist = dir ? dist2 : dist1;
+    const int64_t s = (int64_t)S.off + i;
+    int32_t res_best = -1, res_dist = -1;
+    bool go = in.has_point[s] && !(dir ? in.pre2[out_at] : in.pre1[out_at]);
+    float u = 0.f, v = 0.f, r = 0.f;
+    int level = 0, min_cx = 0, max_cx = 0, min_cy = 0, max_cy = 0;
+    if (go) {                                            // wave-uniform: every lane evaluates the slot's gates
+        float M[9], tt[3], pc[3], p[3];
+        cand_transform(C, dir, M, tt);
+        for (int k = 0; k < 3; ++k) pc[k] = rowdot(S.R + 3 * k, in.Xw + 3 * s) + S.t[k];     // Rcw * p3Dw + tcw
+        for (int k = 0; k < 3; ++k) p[k] = rowdot(M + 3 * k, pc) + tt[k];
+        go = !(p[2] < 0.0f);                             // :1163 (a NaN passes here and fails IsInImage)
+        const float invz = (float)(1.0 / (double)p[2]);
+        const float x = p[0] * invz, y = p[1] * invz;
+        u = C.K[0] * x + C.K[2];
+        v = C.K[1] * y + C.K[3];
+        go = go && u >= T.min_x && u < T.max_x && v >= T.min_y && v < T.max_y;
+        const float d3 = (float)sqrt(((double)p[0] * (double)p[0] + (double)p[1] * (double)p[1]) + (double)p[2] * (double)p[2]);
+        go = go && !(d3 < in.dist_min_inv[s] || d3 > in.dist_max_inv[s]);
+        if (go) {
+            // MapPoint::PredictScale(dist3D, target key frame), MapPoint.cc:391-406: the TARGET's mfLogScaleFactor and mnScaleLevels
+            const float ratio = in.dist_max[s] / d3;
+            const float fl = ceilf(logf(ratio) / T.log_scale);
+            level = fl < 0.f ? 0 : (fl >= (float)T.n_levels ? T.n_levels - 1 : (int)fl);
+            r = C.th * T.sf[level];
+            // KeyFrame::GetFeaturesInArea's cell range and early returns, KeyFrame.cc:575-589
+            min_cx = max(0, (int)floorf(((u - T.min_x) - r) * T.w_inv));
+            max_cx = min(T.cols - 1, (int)ceilf(((u - T.min_x) + r) * T.w_inv));
+            min_cy = max(0, (int)floorf(((v - T.min_y) - r) * T.h_inv));
+            max_cy = min(T.rows - 1, (int)ceilf(((v - T.min_y) + r) * T.h_inv));
+            go = !(min_cx >= T.cols || max_cx < 0 || min_cy >= T.rows || max_cy < 0);
+        }
+    }
+    if (go) {
+        const uint4* md = (const uint4*)(in.mp_desc + 32 * s);       // the map point's descriptor: once per wave, 8 dwords
+        const uint4 m0 = md[0], m1 = md[1];
+        unsigned long long key = NO_KEY;
+        for (int32_t j = lane; j < T.n; j += 64) {
+            const int64_t g = (int64_t)T.off + j;
+            const float2 k = ((const float2*)in.kp)[g];
+            const int cx = (int)roundf((k.x - T.min_x) * T.w_inv);   // Frame::PosInGrid: the cell the key point was filed under
+            const int cy = (int)roundf((k.y - T.min_y) * T.h_inv);
+            if (cx < 0 || cx >= T.cols || cy < 0 || cy >= T.rows) continue;          // never filed: never found
+            if (cx < min_cx || cx > max_cx || cy < min_cy || cy > max_cy) continue;
+            if (!(fabsf(k.x - u) < r && fabsf(k.y - v) < r)) continue;
+            const int oct = in.octave[g];
+            if (oct < level - 1 || oct > level) continue;
+            const uint4* d = (const uint4*)(in.desc + 32 * g);
+            const unsigned long long hd = (unsigned)(popc128(d[0], m0) + popc128(d[1], m1));
+            const unsigned long long kk = (hd << 40) | ((unsigned long long)cx << 33) | ((unsigned long long)cy << 26) | (unsigned long long)j;
+            key = kk < key ? kk : key;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const unsigned long long o = __shfl_xor(key, m, 64);
+            key = o < key ? o : key;
+        }
+        if (key != NO_KEY) {
+            res_dist = (int32_t)(key >> 40);
+            if (res_dist <= TH_HIGH) res_best = (int32_t)(key & (unsigned long long)(MAX_KEYPOINTS - 1));
+        }
+    }
+    if (lane == 0) {
+        best[out_at] = res_best;
+        dist[out_at] = res_dist;
+    }
+}
+
+// :1307-1323: one thread per (candidate, slot of key frame 1)
+__global__ __launch_bounds__(256) void k_search_sim3_agree(In in, const int32_t* __restrict__ best1, const int32_t* __restrict__ best2,
+                                                           int32_t* __restrict__ match12, int32_t* __restrict__ n_found) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= (int64_t)in.n_cand * in.n1) return;
+    const int c = (int)(k / in.n1);
+    const int32_t i1 = (int32_t)(k - (int64_t)c * in.n1);
+    const int32_t b = best1[k];
+    const bool ok = b >= 0 && best2[(int64_t)in.off2[c] + b] == i1;
+    match12[k] = ok ? b : -1;
+    if (ok) atomicAdd(n_found + c, 1);
+}
+
+}  // namespace search
+
+static const char* search_frame_problem(const qsp_orb_frame& f) {
+    if (f.n < 0) return "negative key-point count";
+    if (f.n > search::MAX_KEYPOINTS) return "more than 2^26 key points in a frame";
+    if (f.grid_cols < 1 || f.grid_cols > search::MAX_GRID || f.grid_rows < 1 || f.grid_rows > search::MAX_GRID) return "grid outside 1..64 x 1..64";
+    if (f.n_levels < 1 || f.n_levels > search::MAX_LEVELS) return "n_levels outside 1..16";
+    if (!f.scale_factors) return "null scale_factors";
+    if (f.n && (!f.kp || !f.octave || !f.desc || !f.has_point || !f.Xw || !f.dist_min_inv || !f.dist_max_inv || !f.dist_max || !f.mp_desc))
+        return "null frame array";
+    for (int32_t i = 0; i < f.n; ++i)
+        if (f.octave[i] < 0 || f.octave[i] >= f.n_levels) return "a key point's level outside [0, n_levels)";
+    return nullptr;
+}
+
+int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out) {
+    if (!in) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null input");
+    if (in->n_cand < 0) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: negative candidate count");
+    if (in->n_cand == 0) return QSP_OK;
+    if (!out || !out->match12 || !out->n_found) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null output");
+    if (!!out->best1 != !!out->dist1 || !!out->best1 != !!out->best2 || !!out->best1 != !!out->dist2)
+        return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: the tap is four arrays or none");
+    if (!in->kf1 || !in->kf2 || !in->K || !in->s12 || !in->R12 || !in->t12 || !in->th || !in->off2)
+        return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null argument");
+    const int32_t nc = in->n_cand;
+    const char* why = search_frame_problem(*in->kf1);
+    if (why) return qsp_fail(QSP_ERR_INVALID, (std::string("qsp_search_by_sim3_batch: key frame 1: ") + why).c_str());
+    const int32_t n1 = in->kf1->n;
+    if (in->off2[0] != 0) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: offsets start at 0");
+    for (int32_t c = 0; c < nc; ++c) {
+        if (in->off2[c + 1] < in->off2[c]) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: offsets must not decrease");
+        why = search_frame_problem(in->kf2[c]);
+        if (why) return qsp_fail(QSP_ERR_INVALID, (std::string("qsp_search_by_sim3_batch: key frame 2: ") + why).c_str());
+        if (in->off2[c + 1] - in->off2[c] != in->kf2[c].n)
+            return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: off2 does not step by the key-point count of key frame 2");
+    }
+    const int64_t n2_all = in->off2[nc];
+    if (n1 && !in->pre1) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null pre1");
+    if (n2_all && !in->pre2) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null pre2");
+    const int64_t n_slot = (int64_t)n1 + n2_all, n_out1 = (int64_t)nc * n1, n_work = n_out1 + n2_all;
+    if (n_slot > 0x7fffffff || n_work > 0x7fffffff)
+        return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_search_by_sim3_batch: more than 2^31 - 1 key-point slots in one call");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
+    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: device out of range");
+    QSP_HIP(hipSetDevice(device));
+    // one staging block up (every array starts on a 16-byte boundary), one down:
+    // up   [frame | cand | work_off | off2 | kp | octave | desc | has_point | Xw | dist_min_inv | dist_max_inv | dist_max | mp_desc | pre1 | pre2]
+    // down [match12 | best1 | dist1 | best2 | dist2 | n_found]
+    const size_t ns = (size_t)n_slot, no1 = (size_t)n_out1, no2 = (size_t)n2_all, nf = (size_t)nc + 1;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t a = at; at = (at + bytes + 15) & ~(size_t)15; return a; };
+    const size_t a_frame = take(nf * sizeof(search::FrameP)), a_cand = take((size_t)nc * sizeof(search::CandP)), a_work = take(nf * 8),
+                 a_off2 = take(nf * 4), a_kp = take(ns * 8), a_oct = take(ns * 4), a_desc = take(ns * 32), a_has = take(ns),
+                 a_Xw = take(ns * 12), a_dmin = take(ns * 4), a_dmaxi = take(ns * 4), a_dmax = take(ns * 4), a_mpd = take(ns * 32),
+                 a_pre1 = take(no1), a_pre2 = take(no2);
+    const size_t b_up = at;
+    const size_t a_match = take(no1 * 4), a_b1 = take(no1 * 4), a_d1 = take(no1 * 4), a_b2 = take(no2 * 4), a_d2 = take(no2 * 4),
+                 a_found = take((size_t)nc * 4);
+    const size_t b_all = at, bytes = (b_all + 255) & ~(size_t)255;
+    std::vector<char> up, down;                                            // (no exception may leave an extern "C" function)
+    try {
+        up.assign(b_up, 0);
+        down.resize(b_all - b_up);
+    } catch (const std::exception&) {
+        return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: out of host memory for the staging buffers");
+    }
+    search::FrameP* fp = (search::FrameP*)(up.data() + a_frame);
+    search::CandP* cp = (search::CandP*)(up.data() + a_cand);
+    int64_t* work = (int64_t*)(up.data() + a_work);
+    size_t slot = 0;
+    for (int32_t f = 0; f <= nc; ++f) {
+        const qsp_orb_frame& F = f ? in->kf2[f - 1] : *in->kf1;
+        search::FrameP& P = fp[f];
+        P.off = (int32_t)slot; P.n = F.n;
+        P.min_x = F.min_x; P.max_x = F.max_x; P.min_y = F.min_y; P.max_y = F.max_y;
+        P.cols = F.grid_cols; P.rows = F.grid_rows; P.w_inv = F.grid_w_inv; P.h_inv = F.grid_h_inv;
+        P.n_levels = F.n_levels; P.log_scale = F.log_scale;
+        for (int l = 0; l < F.n_levels; ++l) P.sf[l] = F.scale_factors[l];
+        memcpy(P.R, F.Rcw, sizeof P.R);
+        memcpy(P.t, F.tcw, sizeof P.t);
+        const size_t n = (size_t)F.n;
+        if (n) {
+            memcpy(up.data() + a_kp + 8 * slot, F.kp, 8 * n);
+            memcpy(up.data() + a_oct + 4 * slot, F.octave, 4 * n);
+            memcpy(up.data() + a_desc + 32 * slot, F.desc, 32 * n);
+            memcpy(up.data() + a_has + slot, F.has_point, n);
+            memcpy(up.data() + a_Xw + 12 * slot, F.Xw, 12 * n);
+            memcpy(up.data() + a_dmin + 4 * slot, F.dist_min_inv, 4 * n);
+            memcpy(up.data() + a_dmaxi + 4 * slot, F.dist_max_inv, 4 * n);
+            memcpy(up.data() + a_dmax + 4 * slot, F.dist_max, 4 * n);
+            memcpy(up.data() + a_mpd + 32 * slot, F.mp_desc, 32 * n);
+        }
+        slot += n;
+    }
+    for (int32_t c = 0; c < nc; ++c) {
+        search::CandP& C = cp[c];
+        memcpy(C.K, in->K + 4 * (size_t)c, sizeof C.K);
+        C.s12 = in->s12[c];
+        memcpy(C.R12, in->R12 + 9 * (size_t)c, sizeof C.R12);
+        memcpy(C.t12, in->t12 + 3 * (size_t)c, sizeof C.t12);
+        C.th = in->th[c];
+        work[c] = (int64_t)c * n1 + in->off2[c];
+    }
+    work[nc] = n_work;
+    memcpy(up.data() + a_off2, in->off2, nf * 4);
+    if (no1) memcpy(up.data() + a_pre1, in->pre1, no1);
+    if (no2) memcpy(up.data() + a_pre2, in->pre2, no2);
+    // the device block comes from (and returns to) the per-device cache the bundle adjustment keeps (qsp_ba_release_caches frees it)
+    size_t got = bytes;
+    char* d = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
+    if (!d) QSP_HIP(hipMalloc((void**)&d, bytes));
+    struct Back {
+        int device; char* d; size_t bytes;
+        ~Back() { if (!buf_cache_put(g_dev_cache, device, d, bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
+    } back{device, d, got};
+    QSP_HIP(hipMemcpy(d, up.data(), b_up, hipMemcpyHostToDevice));
+    search::In k;
+    k.frame = (const search::FrameP*)(d + a_frame); k.cand = (const search::CandP*)(d + a_cand);
+    k.work_off = (const int64_t*)(d + a_work); k.off2 = (const int32_t*)(d + a_off2);
+    k.kp = (const float*)(d + a_kp); k.octave = (const int32_t*)(d + a_oct); k.desc = (const uint8_t*)(d + a_desc);
+    k.has_point = (const uint8_t*)(d + a_has); k.Xw = (const float*)(d + a_Xw);
+    k.dist_min_inv = (const float*)(d + a_dmin); k.dist_max_inv = (const float*)(d + a_dmaxi); k.dist_max = (const float*)(d + a_dmax);
+    k.mp_desc = (const uint8_t*)(d + a_mpd); k.pre1 = (const uint8_t*)(d + a_pre1); k.pre2 = (const uint8_t*)(d + a_pre2);
+    k.n_cand = nc; k.n1 = n1;
+    int32_t* d_match = (int32_t*)(d + a_match);
+    int32_t *d_b1 = (int32_t*)(d + a_b1), *d_d1 = (int32_t*)(d + a_d1), *d_b2 = (int32_t*)(d + a_b2), *d_d2 = (int32_t*)(d + a_d2);
+    int32_t* d_found = (int32_t*)(d + a_found);
+    // two launches and one fill on one stream, no host round trip in between
+    QSP_HIP(hipMemsetAsync(d_found, 0, 4 * (size_t)nc, 0));
+    if (n_work) {
+        hipLaunchKernelGGL(search::k_search_sim3_best, dim3((unsigned)((n_work + 3) / 4)), dim3(256), 0, 0, k, n_work, d_b1, d_d1, d_b2, d_d2);
+        QSP_HIP(hipGetLastError());
+    }
+    if (n_out1) {
+        hipLaunchKernelGGL(search::k_search_sim3_agree, dim3((unsigned)((n_out1 + 255) / 256)), dim3(256), 0, 0, k, d_b1, d_b2, d_match, d_found);
+        QSP_HIP(hipGetLastError());
+    }
+    // outputs are written only once everything has succeeded
+    QSP_HIP(hipMemcpy(down.data(), d + b_up, b_all - b_up, hipMemcpyDeviceToHost));
+    const char* h = down.data();
+    if (no1) memcpy(out->match12, h + (a_match - b_up), 4 * no1);
+    memcpy(out->n_found, h + (a_found - b_up), 4 * (size_t)nc);
+    if (out->best1) {
+        if (no1) { memcpy(out->best1, h + (a_b1 - b_up), 4 * no1); memcpy(out->dist1, h + (a_d1 - b_up), 4 * no1); }
+        if (no2) { memcpy(out->best2, h + (a_b2 - b_up), 4 * no2); memcpy(out->dist2, h + (a_d2 - b_up), 4 * no2); }
+    }
+    return QSP_OK;
+}
+
+}  // namespace qsp
