@@ -905,6 +905,62 @@ typedef struct {
 } qsp_search_sim3_out;
 int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchByBoW for every candidate in ONE call: the loop that opens LoopClosing::ComputeSim3 (key-frame overload,
+ * src/ORBmatcher.cc:522-655; shared_is_source = 1: the shared frame is key frame 1, the SOURCE of every candidate) and the loop
+ * of Tracking::Relocalization (frame overload, :159-288; shared_is_source = 0: every candidate key frame is the source and the
+ * shared frame the TARGET; the reference's th is <= 50 there: th_inclusive = 1).  One wave per (candidate, node of the source
+ * frame), then one workgroup per candidate for the orientation check: two launches.
+ * A frame gives its descriptors, key-point angles, which slots are eligible (key-frame side: pMP && !pMP->isBad(); the frame of
+ * the frame overload: all, eligible = NULL) and its DBoW2::FeatureVector in CSR form: node ids strictly ascending, and per node
+ * the feature indices IN THE ORDER THE REFERENCE'S VECTOR HOLDS THEM (the greedy depends on it).  A feature index may appear
+ * once per frame: nodes are then independent of each other, which is what lets the device take them in parallel.
+ * Per node id both frames hold, the sources are walked in list order; a source that is eligible is compared with every target of
+ * the node that is eligible and not yet taken by an earlier source: bestDist1 with the first-in-list target under the strict
+ * `dist < bestDist1`, bestDist2 the second smallest distance (both start at 256; two equal minima give bestDist2 == bestDist1).
+ * It is matched when bestDist1 < th (<= th with th_inclusive), (float)bestDist1 < nn_ratio * (float)bestDist2 in float32 and a
+ * target was found at all; the target is then taken.  With check_orientation: rot = angle_src - angle_tgt, + 360.0f when below
+ * 0, bin = round(rot * (1.0f / 30)) half away from zero (so only bins 0..12 ever fill and the reference's `bin == 30` wrap never
+ * fires: kept); ComputeThreeMaxima (:1601-1642) as written; matches in no kept bin are set back to -1.  An angle pair whose bin
+ * would leave [0, 30] (the reference asserts) is counted in no bin and culled.
+ * Outputs are indexed by SOURCE slot: shared_is_source = 1: (n_cand, shared->n); 0: flat over the candidates' slots, candidate c
+ * at [sum of cand[0..c).n, + cand[c].n).  A candidate's outputs have the same bits alone, in any batch and at any position.
+ * Host pointers.  n_cand == 0 is QSP_OK and touches nothing.  QSP_ERR_INVALID: null required pointers (arrays of a frame with
+ * n == 0 or no nodes may be NULL, node_off never), negative sizes, node_off that does not start at 0, decreases or exceeds n, node
+ * ids not strictly ascending, a feature index outside its frame or listed twice in it, nn_ratio not finite, th outside [0, 256].
+ * More than 2^31 - 1 slots (or n_cand * shared->n, or nodes) in one call: QSP_ERR_UNSUPPORTED.  No output is written unless the
+ * call returns QSP_OK. */
+typedef struct {
+    int32_t n;                    /* key points (KeyFrame::N / Frame::N) */
+    const uint8_t* desc;          /* (n,32) rows of mDescriptors */
+    const float* angle;           /* (n) mvKeysUn[i].angle (key frame) / mvKeys[i].angle (frame) */
+    const uint8_t* eligible;      /* (n) 1 = the slot takes part; NULL = every slot does */
+    int32_t n_nodes;              /* mFeatVec.size() */
+    const int32_t* node_id;       /* (n_nodes) strictly ascending */
+    const int32_t* node_off;      /* (n_nodes+1) starts at 0 */
+    const int32_t* feat;          /* (node_off[n_nodes]) feature indices of each node, in the reference's order */
+} qsp_bow_frame;
+typedef struct {
+    int32_t n_cand;
+    int32_t shared_is_source;     /* 1: loop closing (key-frame overload); 0: relocalisation (frame overload) */
+    const qsp_bow_frame* shared;  /* one: shared by all candidates */
+    const qsp_bow_frame* cand;    /* (n_cand) */
+    int32_t th;                   /* TH_LOW: 50 */
+    int32_t th_inclusive;         /* 0: bestDist1 < th (key-frame overload); 1: <= th (frame overload) */
+    float nn_ratio;               /* mfNNratio */
+    int32_t check_orientation;    /* mbCheckOrientation */
+} qsp_search_bow_in;
+typedef struct {
+    int32_t* match;               /* per source slot: the target's index, else -1 */
+    int32_t* n_matches;           /* (n_cand) */
+    /* the tests' taps, each may be NULL */
+    int32_t* match_raw;           /* like match: before the rotation cull */
+    int32_t* dist;                /* like match: bestDist1 of each source accepted before the cull, else -1 */
+    int32_t* hist;                /* (n_cand,30) the rotation histogram (zeros without check_orientation) */
+    int32_t* ind;                 /* (n_cand,3) ind1 ind2 ind3 of ComputeThreeMaxima (-1 -1 -1 without check_orientation) */
+} qsp_search_bow_out;
+int qsp_search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_out* out);
+
 #ifdef __cplusplus
 }
 #endif

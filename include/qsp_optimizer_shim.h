@@ -1090,6 +1090,129 @@ public:
         }
         return QSP_OK;
     }
+
+private:
+    struct BowArrays {                   // what a qsp_bow_frame points into
+        std::vector<uint8_t> desc, elig;
+        std::vector<float> angle;
+        std::vector<int32_t> node_id, node_off, feat;
+    };
+    // Gathers what SearchByBoW reads of a key frame or frame: descriptor rows, key-point angles and the DBoW2::FeatureVector
+    // (a std::map, so ascending node ids; the indices of a node in the vector's own order).  Eligibility is the caller's.
+    template <typename FV, typename DM, typename KP>
+    static void gather_bow(const int n, const FV& featVec, const DM& descriptors, const std::vector<KP>& keys, BowArrays& a,
+                           qsp_bow_frame& f) {
+        a.desc.assign(32 * (size_t)n + 1, 0);
+        a.angle.assign((size_t)n + 1, 0.f);
+        for (int i = 0; i < n; ++i) {
+            const auto row = descriptors.row(i);
+            for (int b = 0; b < 32; ++b) a.desc[32 * (size_t)i + b] = row.template at<unsigned char>(0, b);
+            a.angle[i] = keys[i].angle;
+        }
+        a.node_off.assign(1, 0);
+        for (const auto& kv : featVec) {
+            a.node_id.push_back((int32_t)kv.first);
+            for (const auto idx : kv.second) a.feat.push_back((int32_t)idx);
+            a.node_off.push_back((int32_t)a.feat.size());
+        }
+        f.n = n;
+        f.n_nodes = (int32_t)a.node_id.size();
+        a.node_id.push_back(0);                                                  // data() of an empty vector may be null
+        a.feat.push_back(0);
+        f.desc = a.desc.data(); f.angle = a.angle.data(); f.eligible = nullptr;
+        f.node_id = a.node_id.data(); f.node_off = a.node_off.data(); f.feat = a.feat.data();
+    }
+    template <typename KF, typename MP>
+    static void gather_bow_kf(KF* pKF, const std::vector<MP*>& vpMP, BowArrays& a, qsp_bow_frame& f) {
+        gather_bow((int)vpMP.size(), pKF->mFeatVec, pKF->mDescriptors, pKF->mvKeysUn, a, f);
+        a.elig.assign(vpMP.size() + 1, 0);
+        for (size_t i = 0; i < vpMP.size(); ++i) a.elig[i] = (vpMP[i] && !vpMP[i]->isBad()) ? 1 : 0;
+        f.eligible = a.elig.data();
+    }
+    static int bow_call(const bool shared_is_source, const qsp_bow_frame& shared, const std::vector<qsp_bow_frame>& cand, const float nnratio,
+                        const bool checkOri, std::vector<int32_t>& match, std::vector<int32_t>& n_matches) {
+        qsp_search_bow_in in;
+        in.n_cand = (int32_t)cand.size(); in.shared_is_source = shared_is_source ? 1 : 0; in.shared = &shared; in.cand = cand.data();
+        in.th = 50;                                                              // ORBmatcher::TH_LOW
+        in.th_inclusive = shared_is_source ? 0 : 1;                              // :598 `<`, :228 `<=`
+        in.nn_ratio = nnratio; in.check_orientation = checkOri ? 1 : 0;
+        qsp_search_bow_out out;
+        out.match = match.data(); out.n_matches = n_matches.data();
+        out.match_raw = out.dist = out.hist = out.ind = nullptr;
+        return qsp_shim::report("qsp_search_by_bow_batch", qsp_search_by_bow_batch(OptimizerHip::device(), &in, &out));
+    }
+
+public:
+    // ORBmatcher::SearchByBoW(pKF1, vpKF2[c], vvpMatches12[c]) (src/ORBmatcher.cc:522-655) for ALL candidates of
+    // LoopClosing::ComputeSim3 in one library call: vvpMatches12[c] as the reference leaves it (size pKF1's N, map points of
+    // vpKF2[c]), vnMatches[c] its return value.  nnratio / checkOri: the ORBmatcher's constructor arguments (0.75, true there).
+    // Returns the qsp status; on error vvpMatches12 and vnMatches have not been touched.
+    template <typename KF, typename MP>
+    static int SearchByBoWBatch(KF* pKF1, const std::vector<KF*>& vpKF2, const float nnratio, const bool checkOri,
+                                std::vector<std::vector<MP*>>& vvpMatches12, std::vector<int>& vnMatches) {
+        const size_t nc = vpKF2.size();
+        if (nc == 0) { vvpMatches12.clear(); vnMatches.clear(); return QSP_OK; }
+        const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+        const size_t N1 = vpMapPoints1.size();
+        BowArrays a1;
+        std::vector<BowArrays> a2(nc);
+        qsp_bow_frame f1;
+        std::vector<qsp_bow_frame> f2(nc);
+        std::vector<std::vector<MP*>> vvpMapPoints2(nc);
+        gather_bow_kf(pKF1, vpMapPoints1, a1, f1);
+        for (size_t c = 0; c < nc; ++c) {
+            vvpMapPoints2[c] = vpKF2[c]->GetMapPointMatches();
+            gather_bow_kf(vpKF2[c], vvpMapPoints2[c], a2[c], f2[c]);
+        }
+        std::vector<int32_t> match(nc * N1 + 1), n_matches(nc);
+        const int rc = bow_call(true, f1, f2, nnratio, checkOri, match, n_matches);
+        if (rc != QSP_OK) return rc;
+        vvpMatches12.assign(nc, std::vector<MP*>(N1, static_cast<MP*>(nullptr)));
+        vnMatches.assign(nc, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t i1 = 0; i1 < N1; ++i1) {
+                const int32_t idx2 = match[c * N1 + i1];
+                if (idx2 >= 0) vvpMatches12[c][i1] = vvpMapPoints2[c][idx2];      // :602
+            }
+            vnMatches[c] = n_matches[c];
+        }
+        return QSP_OK;
+    }
+
+    // ORBmatcher::SearchByBoW(vpKF[c], F, vvpMapPointMatches[c]) (src/ORBmatcher.cc:159-288) for ALL candidate key frames of
+    // Tracking::Relocalization in one library call: vvpMapPointMatches[c] as the reference leaves it (size F.N, indexed by the
+    // frame's key point, map points of vpKF[c]), vnMatches[c] its return value.  On error both are untouched.
+    template <typename KF, typename FR, typename MP>
+    static int SearchByBoWBatch(const std::vector<KF*>& vpKF, FR& F, const float nnratio, const bool checkOri,
+                                std::vector<std::vector<MP*>>& vvpMapPointMatches, std::vector<int>& vnMatches) {
+        const size_t nc = vpKF.size();
+        if (nc == 0) { vvpMapPointMatches.clear(); vnMatches.clear(); return QSP_OK; }
+        BowArrays aF;
+        std::vector<BowArrays> aK(nc);
+        qsp_bow_frame fF;
+        std::vector<qsp_bow_frame> fK(nc);
+        std::vector<std::vector<MP*>> vvpMapPointsKF(nc);
+        gather_bow(F.N, F.mFeatVec, F.mDescriptors, F.mvKeys, aF, fF);           // every key point of the frame is a target: eligible = NULL
+        std::vector<size_t> off(1, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            vvpMapPointsKF[c] = vpKF[c]->GetMapPointMatches();
+            gather_bow_kf(vpKF[c], vvpMapPointsKF[c], aK[c], fK[c]);
+            off.push_back(off.back() + vvpMapPointsKF[c].size());
+        }
+        std::vector<int32_t> match(off.back() + 1), n_matches(nc);
+        const int rc = bow_call(false, fF, fK, nnratio, checkOri, match, n_matches);
+        if (rc != QSP_OK) return rc;
+        vvpMapPointMatches.assign(nc, std::vector<MP*>((size_t)F.N, static_cast<MP*>(nullptr)));
+        vnMatches.assign(nc, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t i = 0; i < vvpMapPointsKF[c].size(); ++i) {               // the result is indexed by the key frame's slot:
+                const int32_t idxF = match[off[c] + i];                          // inverted into vpMapPointMatches[idxF] = pMP (:232)
+                if (idxF >= 0) vvpMapPointMatches[c][idxF] = vvpMapPointsKF[c][i];
+            }
+            vnMatches[c] = n_matches[c];
+        }
+        return QSP_OK;
+    }
 };
 
 }  // namespace ORB_SLAM2

@@ -131,6 +131,21 @@ class SearchSim3Out(C.Structure):
                 ("best2", c_int32_p), ("dist2", c_int32_p)]
 
 
+class BowFrame(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc", c_uint8_p), ("angle", c_float_p), ("eligible", c_uint8_p), ("n_nodes", C.c_int32),
+                ("node_id", c_int32_p), ("node_off", c_int32_p), ("feat", c_int32_p)]
+
+
+class SearchBowIn(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("shared_is_source", C.c_int32), ("shared", C.POINTER(BowFrame)), ("cand", C.POINTER(BowFrame)),
+                ("th", C.c_int32), ("th_inclusive", C.c_int32), ("nn_ratio", C.c_float), ("check_orientation", C.c_int32)]
+
+
+class SearchBowOut(C.Structure):
+    _fields_ = [("match", c_int32_p), ("n_matches", c_int32_p), ("match_raw", c_int32_p), ("dist", c_int32_p), ("hist", c_int32_p),
+                ("ind", c_int32_p)]
+
+
 SYMBOLS = [
     "qsp_last_error", "qsp_version", "qsp_device_count",
     "qsp_decoder_create", "qsp_decoder_destroy", "qsp_decoder_set_option", "qsp_decoder_get_counter", "qsp_decode_sdf",
@@ -145,7 +160,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -239,6 +254,7 @@ def lib():
     L.qsp_essential_graph_stages.argtypes = [C.c_int, C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_int32_p, c_double_p,
                                              C.c_int32, C.c_double] + [c_double_p] * 8
     L.qsp_search_by_sim3_batch.argtypes = [C.c_int, C.POINTER(SearchSim3In), C.POINTER(SearchSim3Out)]
+    L.qsp_search_by_bow_batch.argtypes = [C.c_int, C.POINTER(SearchBowIn), C.POINTER(SearchBowOut)]
     L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]

@@ -399,6 +399,66 @@ def search_by_sim3_batch(kf1, cands, tap=False, device=0):
     return res
 
 
+def _bow_frame(f, keep):
+    """qsp_bow_frame over the arrays of a frame dict (search_by_bow_batch); `keep` holds what the pointers point into"""
+    n = int(np.size(f["angle"]))
+    a = dict(desc=_arr(np.reshape(f["desc"], (-1, 32)), np.uint8), angle=_arr(np.reshape(f["angle"], -1), np.float32),
+             node_id=_arr(np.reshape(f["node_id"], -1), np.int32), node_off=_arr(np.reshape(f["node_off"], -1), np.int32),
+             feat=_arr(np.reshape(f["feat"], -1), np.int32))
+    if int(np.size(f["desc"])) != 32 * n:
+        raise ValueError("search_by_bow_batch: desc does not hold 32 bytes per key point")
+    nn = int(np.size(f["node_id"]))
+    if int(np.size(f["node_off"])) != nn + 1:
+        raise ValueError("search_by_bow_batch: node_off holds one entry more than node_id")
+    if int(np.size(f["feat"])) < int(a["node_off"][nn]):
+        raise ValueError("search_by_bow_batch: feat is shorter than node_off says")
+    o = _lib.BowFrame()
+    o.n, o.n_nodes = n, nn
+    o.desc, o.angle = _lib.u8ptr(a["desc"]), _lib.fptr(a["angle"])
+    if f.get("eligible") is not None:
+        a["eligible"] = _arr(np.asarray(f["eligible"]).astype(bool).reshape(-1), np.uint8)
+        if int(np.size(f["eligible"])) != n:
+            raise ValueError("search_by_bow_batch: eligible does not hold one value per key point")
+        o.eligible = _lib.u8ptr(a["eligible"])
+    o.node_id, o.node_off, o.feat = _lib.i32ptr(a["node_id"]), _lib.i32ptr(a["node_off"]), _lib.i32ptr(a["feat"])
+    keep.append(a)
+    return o
+
+
+def search_by_bow_batch(shared, cands, *, shared_is_source=True, th=50, th_inclusive=False, nn_ratio=0.75, check_orientation=True,
+                        tap=False, device=0):
+    """ORBmatcher::SearchByBoW for every candidate in ONE call (qsp_search_by_bow_batch, include/qsp_hip.h).  A frame is a dict:
+    desc (n,32) uint8, angle (n,), eligible (n,) or None (= every slot), and its feature vector in CSR form: node_id (ascending),
+    node_off, feat (the indices of each node in the reference's order).  shared_is_source=True is the key-frame overload of loop
+    closing (reference src/ORBmatcher.cc:522-655): `shared` is key frame 1, the source of every candidate.  False is the frame
+    overload of relocalisation (:159-288, there with th_inclusive=True): every candidate is the source, `shared` the target.
+    Returns one dict per candidate: match (source slots,) int32 target index or -1, n_matches and, with tap=True, match_raw (before
+    the rotation cull), dist, hist (30,), ind (3,)."""
+    nc = len(cands)
+    if nc == 0:
+        return []
+    keep = []
+    f0 = _bow_frame(shared, keep)
+    fc = (_lib.BowFrame * nc)(*[_bow_frame(c, keep) for c in cands])
+    n0, n = int(f0.n), [int(f.n) for f in fc]
+    off = np.zeros(nc + 1, np.int64)
+    off[1:] = np.cumsum(n) if not shared_is_source else n0 * np.arange(1, nc + 1)
+    i = _lib.SearchBowIn(nc, 1 if shared_is_source else 0, C.pointer(f0), fc, int(th), 1 if th_inclusive else 0, float(nn_ratio),
+                         1 if check_orientation else 0)
+    n_out = max(int(off[-1]), 1)
+    match, count = np.zeros(n_out, np.int32), np.zeros(nc, np.int32)
+    raw, dist, hist, ind = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32), np.zeros((nc, 30), np.int32), np.zeros((nc, 3), np.int32)
+    o = _lib.SearchBowOut(_lib.i32ptr(match), _lib.i32ptr(count), *([_lib.i32ptr(a) for a in (raw, dist, hist, ind)] if tap else [None] * 4))
+    _lib.check(_lib.lib().qsp_search_by_bow_batch(int(device), C.byref(i), C.byref(o)))
+    res = []
+    for c in range(nc):
+        r = dict(match=match[off[c]:off[c + 1]].copy(), n_matches=int(count[c]))
+        if tap:
+            r.update(match_raw=raw[off[c]:off[c + 1]].copy(), dist=dist[off[c]:off[c + 1]].copy(), hist=hist[c].copy(), ind=ind[c].copy())
+        res.append(r)
+    return res
+
+
 def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
                              device=0):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map

@@ -4297,6 +4297,7 @@ extern "C" int qsp_ba_set_deterministic(qsp_ba_problem* p, int on) {
 #include "sim3_opt.hpp"
 #include "sim3_ransac.hpp"
 #include "search_sim3.hpp"
+#include "search_bow.hpp"
 #include "essential_graph.hpp"
 
 #ifdef QSP_CB_STAMPS

@@ -24,6 +24,8 @@ int sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, cons
                       uint8_t* inlier, int32_t* n_inliers, int32_t* hyp_inliers);
 // csrc/search_sim3.hpp (compiled there as well)
 int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out);
+// csrc/search_bow.hpp (compiled there as well)
+int search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_out* out);
 }  // namespace qsp
 
 extern "C" const char* qsp_last_error(void) { return qsp::last_error_ref().c_str(); }
@@ -57,6 +59,9 @@ extern "C" int qsp_sim3_ransac_batch(int device, int32_t n_cand, const int32_t* 
 }
 extern "C" int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out) {
     return qsp::search_by_sim3_batch(device, in, out);
+}
+extern "C" int qsp_search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_out* out) {
+    return qsp::search_by_bow_batch(device, in, out);
 }
 extern "C" int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out) {
     return qsp::object_gates(device, in, out);
