@@ -411,8 +411,10 @@ void qsp_ba_destroy(qsp_ba_problem* p);
 /* qsp_ba_destroy keeps what is expensive to make for the next problem on the same device: the problem's streams (a hardware queue
  * costs milliseconds to bring up), up to 16 device chunks / 512 MB and its pinned staging buffers.  A caller that builds a problem
  * per bundle adjustment -- Optimizer::LocalJointBundleAdjustment, src/Optimizer_util.cc:309-771, as LocalMapping calls it --
- * pays 1.3 ms instead of 7 ms per create + destroy.  qsp_ba_release_caches() gives everything back (any thread, no problem of
- * the process may be inside a call). */
+ * pays 1.3 ms instead of 7 ms per create + destroy.  The one-shot batch calls (Sim3 optimisation and RANSAC, SearchBySim3,
+ * SearchByBoW, the essential graph, the ellipsoid fits and the object gate) take their one device block from the same cache and
+ * give it back when they return.  qsp_ba_release_caches() gives everything back (any thread, no problem of the process may be
+ * inside a call). */
 void qsp_ba_release_caches(void);
 
 /* g2o edge levels: 1 = excluded from optimisation (e->setLevel(1), src/Optimizer_util.cc:621-654).  NULL = all active.

@@ -35,6 +35,7 @@
 #include "../../include/qsp_hip.h"
 #include "common.hpp"
 #include "comm_rccl.hpp"
+#include "staging.hpp"
 
 namespace qsp {
 namespace ba {
@@ -2880,34 +2881,8 @@ struct qsp_ba_problem {
 static int upload_levels(qsp_ba_problem* p);
 static void build_orders(qsp_ba_problem* p);
 
-// Freed device chunks and pinned host buffers are kept per device for the next problem (bounded: 16 entries each, 512 MB of device
-// memory): hipMalloc / hipFree and hipHostMalloc / hipHostFree cost 0.1-0.5 ms apiece, and a caller that builds a problem per bundle
-// adjustment (the drop-in Optimizer) asks for the same sizes again and again.  Nothing relies on fresh memory being zero.
-struct CachedBuf { void* p; size_t bytes; unsigned flags; };
-static std::mutex g_buf_cache_mu;
-static std::vector<CachedBuf> g_dev_cache[64], g_host_cache[64];
-static void* buf_cache_take(std::vector<CachedBuf>* cache, int dev, size_t bytes, unsigned flags, size_t* got) {
-    std::lock_guard<std::mutex> lk(g_buf_cache_mu);
-    auto& v = cache[dev & 63];
-    int best = -1;
-    for (int i = 0; i < (int)v.size(); ++i)
-        if (v[i].flags == flags && v[i].bytes >= bytes && v[i].bytes <= 2 * bytes + (1 << 16) && (best < 0 || v[i].bytes < v[best].bytes)) best = i;
-    if (best < 0) return nullptr;
-    void* q = v[best].p;
-    *got = v[best].bytes;
-    v.erase(v.begin() + best);
-    return q;
-}
-// false: the cache is full, the caller frees the buffer
-static bool buf_cache_put(std::vector<CachedBuf>* cache, int dev, void* q, size_t bytes, unsigned flags, size_t max_total) {
-    std::lock_guard<std::mutex> lk(g_buf_cache_mu);
-    auto& v = cache[dev & 63];
-    size_t tot = bytes;
-    for (const CachedBuf& c : v) tot += c.bytes;
-    if (v.size() >= 16 || tot > max_total) return false;
-    v.push_back({q, bytes, flags});
-    return true;
-}
+// Freed device chunks and pinned host buffers are kept per device for the next problem (buf_cache.hpp).  Nothing relies on fresh
+// memory being zero.
 static hipError_t host_alloc_cached(int dev, void** out, size_t bytes, unsigned flags, size_t* got) {
     *got = bytes;
     void* q = buf_cache_take(g_host_cache, dev, bytes, flags, got);
@@ -3360,7 +3335,7 @@ extern "C" void qsp_ba_destroy(qsp_ba_problem* p) {
     }
     // (behind the synchronisation: nothing of this problem is in flight any more)
     for (size_t i = 0; i < p->allocs.size(); ++i)
-        if (i >= p->alloc_bytes.size() || !p->alloc_bytes[i] || !buf_cache_put(g_dev_cache, p->device, p->allocs[i], p->alloc_bytes[i], 0, (size_t)512 << 20))
+        if (i >= p->alloc_bytes.size() || !p->alloc_bytes[i] || !buf_cache_put(g_dev_cache, p->device, p->allocs[i], p->alloc_bytes[i], 0, kDevCacheBytes))
             (void)hipFree(p->allocs[i]);
     void* hb[3] = {p->scal_host, p->lvl_host, p->idx_host};
     const unsigned hf[3] = {hipHostMallocMapped | hipHostMallocCoherent, hipHostMallocDefault, hipHostMallocDefault};
@@ -4208,10 +4183,7 @@ extern "C" void qsp_pose_optimizer_destroy(qsp_pose_optimizer* h) {
 
 extern "C" int qsp_pose_optimizer_create(int device, int32_t max_points, qsp_pose_optimizer** out) {
     if (!out || max_points < 1) return qsp_fail(QSP_ERR_INVALID, "qsp_pose_optimizer_create: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_pose_optimizer_create: device out of range");
-    QSP_HIP(hipSetDevice(device));
+    QSP_TRY(use_device(device, "qsp_pose_optimizer_create"));
     qsp_pose_optimizer* h = new qsp_pose_optimizer();
     h->device = device;
     h->cap = max_points;
@@ -4295,9 +4267,6 @@ extern "C" int qsp_ba_set_deterministic(qsp_ba_problem* p, int on) {
 
 #include "ellipsoid_fit.hpp"
 #include "sim3_opt.hpp"
-#include "sim3_ransac.hpp"
-#include "search_sim3.hpp"
-#include "search_bow.hpp"
 #include "essential_graph.hpp"
 
 #ifdef QSP_CB_STAMPS

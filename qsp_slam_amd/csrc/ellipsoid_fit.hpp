@@ -20,6 +20,8 @@
 #pragma once
 #include <float.h>
 
+#include "staging.hpp"
+
 namespace qsp {
 namespace ell {
 
@@ -451,39 +453,34 @@ extern "C" int qsp_ellipsoid_fit_planes(int device, int32_t n, const double* ell
         if (plane_off[i + 1] < plane_off[i]) return qsp_fail(QSP_ERR_INVALID, "qsp_ellipsoid_fit_planes: offsets must not decrease");
     const size_t np_ = (size_t)plane_off[n];
     if (np_ && !planes) return qsp_fail(QSP_ERR_INVALID, "qsp_ellipsoid_fit_planes: planes missing");
-    QSP_HIP(hipSetDevice(device));
-    struct Pool {
-        std::vector<void*> p;
-        ~Pool() { for (void* q : p) (void)hipFree(q); }
-    } pool;
-    auto dev = [&](size_t bytes, void** out) {
-        hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 8));
-        if (e == hipSuccess) pool.p.push_back(*out);
-        return e;
-    };
-    double *d_ell, *d_pl, *d_out, *d_chi, *d_tr = nullptr;
-    int32_t *d_off, *d_it;
-    QSP_HIP(dev(sizeof(double) * 10 * n, (void**)&d_ell));
-    QSP_HIP(dev(sizeof(double) * 4 * np_, (void**)&d_pl));
-    QSP_HIP(dev(sizeof(double) * 10 * n, (void**)&d_out));
-    QSP_HIP(dev(sizeof(double) * n, (void**)&d_chi));
-    QSP_HIP(dev(sizeof(int32_t) * (n + 1), (void**)&d_off));
-    QSP_HIP(dev(sizeof(int32_t) * n, (void**)&d_it));
-    if (trace) {
-        QSP_HIP(dev(sizeof(double) * 3 * (size_t)n * n_iter, (void**)&d_tr));
-        QSP_HIP(hipMemset(d_tr, 0, sizeof(double) * 3 * (size_t)n * n_iter));
-    }
-    QSP_HIP(hipMemcpy(d_ell, ellipsoid_in, sizeof(double) * 10 * n, hipMemcpyHostToDevice));
-    if (np_) QSP_HIP(hipMemcpy(d_pl, planes, sizeof(double) * 4 * np_, hipMemcpyHostToDevice));
-    QSP_HIP(hipMemcpy(d_off, plane_off, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice));
-    ell::FitIn in{n, n_iter, normal_direction ? 1 : 0, d_ell, d_off, d_pl};
-    hipLaunchKernelGGL(ell::k_ellipsoid_fit, dim3(n), dim3(64), 0, 0, in, d_out, d_chi, d_it, d_tr);
+    QSP_TRY(use_device(device, "qsp_ellipsoid_fit_planes"));
+    // up   [ell | planes | off]
+    // down [out | chi2 | iters | trace]
+    const size_t nn = (size_t)n, n_tr = trace ? 3 * nn * n_iter : 0;
+    StagingLayout L;
+    const size_t a_ell = L.take<double>(10 * nn), a_pl = L.take<double>(4 * np_), a_off = L.take<int32_t>(nn + 1);
+    L.begin_down();
+    const size_t a_out = L.take<double>(10 * nn), a_chi = L.take<double>(nn), a_it = L.take<int32_t>(nn), a_tr = L.take<double>(n_tr);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
+        return qsp_fail(QSP_ERR_INVALID, "qsp_ellipsoid_fit_planes: out of host memory for the staging buffers");
+    put(up, a_ell, ellipsoid_in, 80 * nn); put(up, a_pl, planes, 32 * np_); put(up, a_off, plane_off, 4 * (nn + 1));
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
+    double* d_tr = trace ? ptr<double>(d, a_tr) : nullptr;
+    if (trace) QSP_HIP(hipMemsetAsync(d_tr, 0, sizeof(double) * n_tr, 0));   // the iterations a fit does not reach read as zeros
+    ell::FitIn in{n, n_iter, normal_direction ? 1 : 0, ptr<double>(d, a_ell), ptr<int32_t>(d, a_off), ptr<double>(d, a_pl)};
+    hipLaunchKernelGGL(ell::k_ellipsoid_fit, dim3(n), dim3(64), 0, 0, in, ptr<double>(d, a_out), ptr<double>(d, a_chi), ptr<int32_t>(d, a_it), d_tr);
     QSP_HIP(hipGetLastError());
-    QSP_HIP(hipDeviceSynchronize());
-    QSP_HIP(hipMemcpy(ellipsoid_out, d_out, sizeof(double) * 10 * n, hipMemcpyDeviceToHost));
-    if (chi2_out) QSP_HIP(hipMemcpy(chi2_out, d_chi, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (iters_out) QSP_HIP(hipMemcpy(iters_out, d_it, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (trace) QSP_HIP(hipMemcpy(trace, d_tr, sizeof(double) * 3 * (size_t)n * n_iter, hipMemcpyDeviceToHost));
+    // outputs are written only once everything has succeeded
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
+    const char* h = down.data();
+    memcpy(ellipsoid_out, h + L.in_down(a_out), sizeof(double) * 10 * nn);
+    if (chi2_out) memcpy(chi2_out, h + L.in_down(a_chi), sizeof(double) * nn);
+    if (iters_out) memcpy(iters_out, h + L.in_down(a_it), sizeof(int32_t) * nn);
+    if (trace) memcpy(trace, h + L.in_down(a_tr), sizeof(double) * n_tr);
     return QSP_OK;
 }
 
@@ -503,43 +500,39 @@ extern "C" int qsp_ellipsoid_fit_prior(int device, int32_t n, const double* elli
             return qsp_fail(QSP_ERR_INVALID, "qsp_ellipsoid_fit_prior: offsets must not decrease");
     const size_t n_pn = (size_t)off_normal[n], n_pl = (size_t)off_plane[n];
     if ((n_pn && !planes_normal) || (n_pl && !planes)) return qsp_fail(QSP_ERR_INVALID, "qsp_ellipsoid_fit_prior: planes missing");
-    QSP_HIP(hipSetDevice(device));
-    struct Pool {
-        std::vector<void*> p;
-        ~Pool() { for (void* q : p) (void)hipFree(q); }
-    } pool;
-    auto up = [&](const void* src, size_t bytes, void** out) -> hipError_t {
-        hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 8));
-        if (e != hipSuccess) return e;
-        pool.p.push_back(*out);
-        return (src && bytes) ? hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    std::vector<double> gw(n, -1.0);
-    if (ground_plane_weight) gw.assign(ground_plane_weight, ground_plane_weight + n);
-    double *d_ell, *d_pn, *d_pl, *d_pri, *d_w, *d_gw, *d_out, *d_chi, *d_tr = nullptr;
-    int32_t *d_on, *d_op, *d_it;
-    QSP_HIP(up(ellipsoid_in, sizeof(double) * 10 * n, (void**)&d_ell));
-    QSP_HIP(up(planes_normal, sizeof(double) * 4 * n_pn, (void**)&d_pn));
-    QSP_HIP(up(planes, sizeof(double) * 4 * n_pl, (void**)&d_pl));
-    QSP_HIP(up(off_normal, sizeof(int32_t) * (n + 1), (void**)&d_on));
-    QSP_HIP(up(off_plane, sizeof(int32_t) * (n + 1), (void**)&d_op));
-    QSP_HIP(up(pri, sizeof(double) * 2 * n, (void**)&d_pri));
-    QSP_HIP(up(weight, sizeof(double) * n, (void**)&d_w));
-    QSP_HIP(up(gw.data(), sizeof(double) * n, (void**)&d_gw));
-    QSP_HIP(up(nullptr, sizeof(double) * 10 * n, (void**)&d_out));
-    QSP_HIP(up(nullptr, sizeof(double) * n, (void**)&d_chi));
-    QSP_HIP(up(nullptr, sizeof(int32_t) * n, (void**)&d_it));
-    if (trace) {
-        QSP_HIP(up(nullptr, sizeof(double) * 3 * (size_t)n * n_iter, (void**)&d_tr));
-        QSP_HIP(hipMemset(d_tr, 0, sizeof(double) * 3 * (size_t)n * n_iter));
-    }
-    ell::PriorIn in{n, n_iter, d_ell, d_on, d_pn, d_op, d_pl, d_pri, d_w, d_gw, angle_sigma_deg / 180.0 * 3.14159265358979323846};
-    hipLaunchKernelGGL(ell::k_ellipsoid_prior_fit, dim3(n), dim3(64), 0, 0, in, d_out, d_chi, d_it, d_tr);
+    QSP_TRY(use_device(device, "qsp_ellipsoid_fit_prior"));
+    // up   [ell | planes_normal | planes | off_normal | off_plane | pri | weight | ground weight]
+    // down [out | chi2 | iters | trace]
+    const size_t nn = (size_t)n, n_tr = trace ? 3 * nn * n_iter : 0;
+    StagingLayout L;
+    const size_t a_ell = L.take<double>(10 * nn), a_pn = L.take<double>(4 * n_pn), a_pl = L.take<double>(4 * n_pl), a_on = L.take<int32_t>(nn + 1),
+                 a_op = L.take<int32_t>(nn + 1), a_pri = L.take<double>(2 * nn), a_w = L.take<double>(nn), a_gw = L.take<double>(nn);
+    L.begin_down();
+    const size_t a_out = L.take<double>(10 * nn), a_chi = L.take<double>(nn), a_it = L.take<int32_t>(nn), a_tr = L.take<double>(n_tr);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
+        return qsp_fail(QSP_ERR_INVALID, "qsp_ellipsoid_fit_prior: out of host memory for the staging buffers");
+    put(up, a_ell, ellipsoid_in, 80 * nn); put(up, a_pn, planes_normal, 32 * n_pn); put(up, a_pl, planes, 32 * n_pl);
+    put(up, a_on, off_normal, 4 * (nn + 1)); put(up, a_op, off_plane, 4 * (nn + 1)); put(up, a_pri, pri, 16 * nn); put(up, a_w, weight, 8 * nn);
+    double* gw = ptr<double>(up.data(), a_gw);
+    for (size_t i = 0; i < nn; ++i) gw[i] = ground_plane_weight ? ground_plane_weight[i] : -1.0;
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
+    double* d_tr = trace ? ptr<double>(d, a_tr) : nullptr;
+    if (trace) QSP_HIP(hipMemsetAsync(d_tr, 0, sizeof(double) * n_tr, 0));   // the iterations a fit does not reach read as zeros
+    ell::PriorIn in{n, n_iter, ptr<double>(d, a_ell), ptr<int32_t>(d, a_on), ptr<double>(d, a_pn), ptr<int32_t>(d, a_op), ptr<double>(d, a_pl),
+                    ptr<double>(d, a_pri), ptr<double>(d, a_w), ptr<double>(d, a_gw), angle_sigma_deg / 180.0 * 3.14159265358979323846};
+    hipLaunchKernelGGL(ell::k_ellipsoid_prior_fit, dim3(n), dim3(64), 0, 0, in, ptr<double>(d, a_out), ptr<double>(d, a_chi),
+                       ptr<int32_t>(d, a_it), d_tr);
     QSP_HIP(hipGetLastError());
-    QSP_HIP(hipDeviceSynchronize());
-    QSP_HIP(hipMemcpy(ellipsoid_out, d_out, sizeof(double) * 10 * n, hipMemcpyDeviceToHost));
-    if (chi2_out) QSP_HIP(hipMemcpy(chi2_out, d_chi, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (iters_out) QSP_HIP(hipMemcpy(iters_out, d_it, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (trace) QSP_HIP(hipMemcpy(trace, d_tr, sizeof(double) * 3 * (size_t)n * n_iter, hipMemcpyDeviceToHost));
+    // outputs are written only once everything has succeeded
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
+    const char* h = down.data();
+    memcpy(ellipsoid_out, h + L.in_down(a_out), sizeof(double) * 10 * nn);
+    if (chi2_out) memcpy(chi2_out, h + L.in_down(a_chi), sizeof(double) * nn);
+    if (iters_out) memcpy(iters_out, h + L.in_down(a_it), sizeof(int32_t) * nn);
+    if (trace) memcpy(trace, h + L.in_down(a_tr), sizeof(double) * n_tr);
     return QSP_OK;
 }

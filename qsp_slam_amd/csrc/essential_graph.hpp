@@ -1,5 +1,5 @@
 // essential_graph.hpp -- Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from
-// optimizer.initializeOptimization() to the corrected map points.  Included at the end of ba_solver.hip.
+// optimizer.initializeOptimization() to the corrected map points.  Included at the end of ba_solver.hip (the dense factorisation is the solver's).
 //
 // The problem: n_kf VertexSim3Expmap in hessian order (ascending key-frame id; state tx ty tz qx qy qz qw s), a fixed flag per
 // vertex, n_edge EdgeSim3 in insertion order with error log(Z S_v0 S_v1^-1) (Thirdparty/g2o/g2o/types/types_seven_dof_expmap.h
@@ -32,6 +32,7 @@
 // restates operation for operation.  Sim3::log's W.lu().solve(t) is restated as Eigen's 3x3 partial-pivot LU with its unrolled
 // triangular solves (lu3_solve).
 #pragma once
+#include "staging.hpp"
 
 namespace qsp {
 namespace eg {
@@ -348,24 +349,17 @@ inline int validate(int32_t n_kf, const double* sim3_in, const uint8_t* fixed, i
 // [Sa Sb E chi J b bs y x scal Pout Winv H A Uf]; it goes back to the buffer cache when the call ends.
 struct Run {
     int device = 0, n_kf = 0, n_edge = 0, n_free = 0, n_pt = 0, D = 7, dim = 0, dimp = 0, nb = 0, chol_lds = 0;
-    size_t mat = 0, cache_bytes = 0;
-    char* d = nullptr;
+    size_t mat = 0;
+    DeviceBlock blk;
     Graph g;
     double *S0 = nullptr, *Sa = nullptr, *Sb = nullptr, *P = nullptr, *Po = nullptr, *H = nullptr, *A = nullptr, *Uf = nullptr, *W = nullptr,
            *bv = nullptr, *bs = nullptr, *y = nullptr, *x = nullptr, *scal = nullptr;
     const int32_t* ref = nullptr;
-    Run() = default;
-    Run(const Run&) = delete;
-    Run& operator=(const Run&) = delete;
-    ~Run() { if (d && !buf_cache_put(g_dev_cache, device, d, cache_bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
 
     // a validated graph with n_edge > 0 and n_free > 0: device, layout, host side of the graph, upload; Sa = S0
-    int setup(int device_, int32_t n_kf_, const double* sim3_in, const uint8_t* fixed, int n_free_, int32_t n_edge_, const int32_t* edge_v0,
+    int setup(const char* who, int device_, int32_t n_kf_, const double* sim3_in, const uint8_t* fixed, int n_free_, int32_t n_edge_, const int32_t* edge_v0,
               const int32_t* edge_v1, const double* meas, int32_t fix_scale, int32_t n_pt_, const double* pt_in, const int32_t* pt_ref) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-        if (device_ < 0 || device_ >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_optimize: device out of range");
-        QSP_HIP(hipSetDevice(device_));
+        QSP_TRY(use_device(device_, who));
         device = device_; n_kf = n_kf_; n_edge = n_edge_; n_free = n_free_; n_pt = n_pt_;
         constexpr int NB = ba::NB;
         D = fix_scale ? 6 : 7; dim = D * n_free; dimp = (dim + NB - 1) / NB * NB; nb = dimp / NB;
@@ -373,48 +367,43 @@ struct Run {
         mat = (size_t)dimp * dimp;
         const size_t i_v0 = 0, i_v1 = ne, i_slot = 2 * ne, i_free = i_slot + nk, i_off = i_free + (size_t)n_free, i_inc = i_off + nk + 1,
                      i_ref = i_inc + 2 * ne, n_int = i_ref + np;
-        size_t at = 0;
-        auto take = [&](size_t n) { const size_t o = at; at += (n + 1) & ~(size_t)1; return o; };
-        const size_t oS0 = take(8 * nk), oZ = take(8 * ne), oP = take(3 * np), oI = take((n_int + 1) / 2), n_up = at;
-        const size_t oSa = take(8 * nk), oSb = take(8 * nk), oE = take(7 * ne), oChi = take(ne), oJ = take(98 * ne), oB = take(dimp),
-                     oBs = take(dimp), oY = take(dimp), oX = take(dimp), oScal = take(8), oPo = take(3 * np),
-                     oW = take((size_t)nb * NB * NB), oH = take(mat), oA = take(mat), oUf = take(mat);
-        const size_t bytes = (sizeof(double) * at + 255) & ~(size_t)255;
-        std::vector<double> hd;                                    // (no exception may leave an extern "C" function)
-        try {
-            hd.assign(n_up, 0.0);
-            // host side of the graph: free list, slots, CSR of incident edges in insertion order
-            int32_t* hi = (int32_t*)(hd.data() + oI);
-            memcpy(hi + i_v0, edge_v0, sizeof(int32_t) * ne);
-            memcpy(hi + i_v1, edge_v1, sizeof(int32_t) * ne);
-            for (int v = 0, f = 0; v < n_kf; ++v) {
-                hi[i_slot + v] = fixed[v] ? -1 : f;
-                if (!fixed[v]) hi[i_free + f++] = v;
-            }
-            int32_t* off = hi + i_off;
-            for (size_t k = 0; k < ne; ++k) { off[edge_v0[k] + 1]++; off[edge_v1[k] + 1]++; }
-            for (size_t v = 0; v < nk; ++v) off[v + 1] += off[v];
-            std::vector<int32_t> cur(off, off + nk);
-            for (size_t k = 0; k < ne; ++k) {
-                hi[i_inc + cur[edge_v0[k]]++] = (int32_t)(k << 1);
-                hi[i_inc + cur[edge_v1[k]]++] = (int32_t)(k << 1) | 1;
-            }
-            if (np) memcpy(hi + i_ref, pt_ref, sizeof(int32_t) * np);
-        } catch (const std::exception&) {
-            return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_essential_graph_optimize: out of host memory for a graph of this size");
+        StagingLayout L;
+        const size_t oS0 = L.take<double>(8 * nk), oZ = L.take<double>(8 * ne), oP = L.take<double>(3 * np), oI = L.take<int32_t>(n_int);
+        L.begin_scratch();                                         // (the results come down array by array: S is Sa or Sb)
+        const size_t oSa = L.take<double>(8 * nk), oSb = L.take<double>(8 * nk), oE = L.take<double>(7 * ne), oChi = L.take<double>(ne),
+                     oJ = L.take<double>(98 * ne), oB = L.take<double>(dimp), oBs = L.take<double>(dimp), oY = L.take<double>(dimp),
+                     oX = L.take<double>(dimp), oScal = L.take<double>(8), oPo = L.take<double>(3 * np),
+                     oW = L.take<double>((size_t)nb * NB * NB), oH = L.take<double>(mat), oA = L.take<double>(mat), oUf = L.take<double>(mat);
+        std::vector<char> hd;
+        if (!host_staging(hd, L.up_bytes()))
+            return qsp_fail(QSP_ERR_UNSUPPORTED, (std::string(who) + ": out of host memory for a graph of this size").c_str());
+        // host side of the graph: free list, slots, CSR of incident edges in insertion order
+        int32_t* hi = ptr<int32_t>(hd.data(), oI);
+        memcpy(hi + i_v0, edge_v0, sizeof(int32_t) * ne);
+        memcpy(hi + i_v1, edge_v1, sizeof(int32_t) * ne);
+        for (int v = 0, f = 0; v < n_kf; ++v) {
+            hi[i_slot + v] = fixed[v] ? -1 : f;
+            if (!fixed[v]) hi[i_free + f++] = v;
         }
+        int32_t* off = hi + i_off;                                 // counts at v + 1, starts, then each start walks to its end ...
+        for (size_t k = 0; k < ne; ++k) { off[edge_v0[k] + 1]++; off[edge_v1[k] + 1]++; }
+        for (size_t v = 0; v < nk; ++v) off[v + 1] += off[v];
+        for (size_t k = 0; k < ne; ++k) {
+            hi[i_inc + off[edge_v0[k]]++] = (int32_t)(k << 1);
+            hi[i_inc + off[edge_v1[k]]++] = (int32_t)(k << 1) | 1;
+        }
+        for (size_t v = nk; v > 0; --v) off[v] = off[v - 1];       // ... and is moved back: off[v] is the start of v again
+        off[0] = 0;
+        if (np) memcpy(hi + i_ref, pt_ref, sizeof(int32_t) * np);
         memcpy(&hd[oS0], sim3_in, sizeof(double) * 8 * nk);
         memcpy(&hd[oZ], meas, sizeof(double) * 8 * ne);
         if (np) memcpy(&hd[oP], pt_in, sizeof(double) * 3 * np);
-        size_t got = bytes;
-        char* q = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
-        if (!q) QSP_HIP(hipMalloc((void**)&q, bytes));
-        d = q;
-        cache_bytes = got;
-        double* dd = (double*)d;
-        const int32_t* di = (const int32_t*)(dd + oI);
-        QSP_HIP(hipMemcpy(dd, hd.data(), sizeof(double) * n_up, hipMemcpyHostToDevice));
-        QSP_HIP(hipMemcpy(dd + oSa, dd + oS0, sizeof(double) * 8 * nk, hipMemcpyDeviceToDevice));
+        QSP_TRY(blk.take(device, L.total()));
+        QSP_TRY(blk.upload(hd.data(), L.up_bytes()));
+        char* d = blk.data();
+        const int32_t* di = ptr<int32_t>(d, oI);
+        auto dd = [d](size_t o) { return ptr<double>(d, o); };
+        QSP_HIP(hipMemcpy(dd(oSa), dd(oS0), sizeof(double) * 8 * nk, hipMemcpyDeviceToDevice));
         chol_lds = (int)(sizeof(double) * ba::CHOL_LDS_DOUBLES);
         {   // the factorisation kernels' LDS size: once per device and process
             static std::mutex mu;
@@ -428,9 +417,9 @@ struct Run {
         }
         g.n_kf = n_kf; g.n_edge = n_edge; g.n_free = n_free; g.D = D; g.fix_scale = fix_scale ? 1 : 0; g.ld = dimp;
         g.v0 = di + i_v0; g.v1 = di + i_v1; g.slot = di + i_slot; g.free_v = di + i_free; g.inc_off = di + i_off; g.inc = di + i_inc;
-        g.Z = dd + oZ; g.E = dd + oE; g.chi = dd + oChi; g.J = dd + oJ;
-        S0 = dd + oS0; Sa = dd + oSa; Sb = dd + oSb; P = dd + oP; Po = dd + oPo; H = dd + oH; A = dd + oA; Uf = dd + oUf; W = dd + oW;
-        bv = dd + oB; bs = dd + oBs; y = dd + oY; x = dd + oX; scal = dd + oScal;
+        g.Z = dd(oZ); g.E = dd(oE); g.chi = dd(oChi); g.J = dd(oJ);
+        S0 = dd(oS0); Sa = dd(oSa); Sb = dd(oSb); P = dd(oP); Po = dd(oPo); H = dd(oH); A = dd(oA); Uf = dd(oUf); W = dd(oW);
+        bv = dd(oB); bs = dd(oBs); y = dd(oY); x = dd(oX); scal = dd(oScal);
         ref = di + i_ref;
         return QSP_OK;
     }
@@ -472,12 +461,14 @@ struct Run {
 };
 
 }  // namespace eg
+}  // namespace qsp
 
-int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
-                             const int32_t* edge_v1, const double* meas, int32_t fix_scale, int32_t n_iter, double lambda_init,
-                             int32_t n_pt, const double* pt_in, const int32_t* pt_ref, double* sim3_out, double* pt_out,
-                             qsp_essential_trace* trace) {
-    using namespace eg;
+extern "C" int qsp_essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge,
+                                            const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale,
+                                            int32_t n_iter, double lambda_init, int32_t n_pt, const double* pt_in,
+                                            const int32_t* pt_ref, double* sim3_out, double* pt_out, qsp_essential_trace* trace) {
+    using namespace qsp;
+    using namespace qsp::eg;
     if (n_kf == 0) return QSP_OK;
     int n_free = 0;
     int rc = validate(n_kf, sim3_in, fixed, n_edge, edge_v0, edge_v1, meas, fix_scale, n_iter, n_pt, pt_in, pt_ref, sim3_out, pt_out, &n_free);
@@ -491,14 +482,12 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
         return QSP_OK;
     }
     const size_t nk = (size_t)n_kf, np = (size_t)n_pt;
-    std::vector<double> down;                                  // (no exception may leave an extern "C" function)
-    try {
-        down.resize(8 * nk + 3 * np);
-    } catch (const std::exception&) {
+    std::vector<char> down_bytes;
+    if (!host_staging(down_bytes, sizeof(double) * (8 * nk + 3 * np)))
         return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_essential_graph_optimize: out of host memory for a graph of this size");
-    }
+    double* down = ptr<double>(down_bytes.data(), 0);
     Run r;
-    if ((rc = r.setup(device, n_kf, sim3_in, fixed, n_free, n_edge, edge_v0, edge_v1, meas, fix_scale, n_pt, pt_in, pt_ref))) return rc;
+    if ((rc = r.setup("qsp_essential_graph_optimize", device, n_kf, sim3_in, fixed, n_free, n_edge, edge_v0, edge_v1, meas, fix_scale, n_pt, pt_in, pt_ref))) return rc;
     double *S = r.Sa, *St = r.Sb;
     double h[4], lambda = 0, ni = 2;
     int nbad = 0, done = 0;
@@ -552,19 +541,21 @@ int essential_graph_optimize(int device, int32_t n_kf, const double* sim3_in, co
                                (const double*)S, r.Po);
     QSP_HIP(hipGetLastError());
     // outputs are written only once everything has succeeded
-    QSP_HIP(hipMemcpy(down.data(), S, sizeof(double) * 8 * nk, hipMemcpyDeviceToHost));
-    if (np) QSP_HIP(hipMemcpy(down.data() + 8 * nk, r.Po, sizeof(double) * 3 * np, hipMemcpyDeviceToHost));
-    memcpy(sim3_out, down.data(), sizeof(double) * 8 * nk);
-    if (np) memcpy(pt_out, down.data() + 8 * nk, sizeof(double) * 3 * np);
+    QSP_HIP(hipMemcpy(down, S, sizeof(double) * 8 * nk, hipMemcpyDeviceToHost));
+    if (np) QSP_HIP(hipMemcpy(down + 8 * nk, r.Po, sizeof(double) * 3 * np, hipMemcpyDeviceToHost));
+    memcpy(sim3_out, down, sizeof(double) * 8 * nk);
+    if (np) memcpy(pt_out, down + 8 * nk, sizeof(double) * 3 * np);
     if (trace) *trace = tr;
     return QSP_OK;
 }
 
 // qsp_essential_graph_stages: one Run::linearise and one Run::trial at the input states, every buffer copied down
-int essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge, const int32_t* edge_v0,
-                           const int32_t* edge_v1, const double* meas, int32_t fix_scale, double lambda, double* E, double* chi, double* J,
-                           double* H, double* b, double* x, double* sim3_trial, double* info) {
-    using namespace eg;
+extern "C" int qsp_essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, const uint8_t* fixed, int32_t n_edge,
+                                          const int32_t* edge_v0, const int32_t* edge_v1, const double* meas, int32_t fix_scale,
+                                          double lambda, double* E, double* chi, double* J, double* H, double* b, double* x,
+                                          double* sim3_trial, double* info) {
+    using namespace qsp;
+    using namespace qsp::eg;
     if (!E || !chi || !J || !H || !b || !x || !sim3_trial || !info) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_stages: null output");
     if (!(lambda > 0) || !std::isfinite(lambda)) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_stages: lambda must be positive and finite");
     int n_free = 0;
@@ -573,14 +564,12 @@ int essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, cons
     if (n_edge == 0 || n_free == 0) return qsp_fail(QSP_ERR_INVALID, "qsp_essential_graph_stages: no edge or no free vertex, nothing to show");
     const size_t nk = (size_t)n_kf, ne = (size_t)n_edge, dim = (size_t)(fix_scale ? 6 : 7) * n_free;
     const size_t oE = 0, oChi = oE + 7 * ne, oJ = oChi + ne, oH = oJ + 98 * ne, oB = oH + dim * dim, oX = oB + dim, oS = oX + dim, n_down = oS + 8 * nk;
-    std::vector<double> down;
-    try {
-        down.resize(n_down);
-    } catch (const std::exception&) {
+    std::vector<char> down_bytes;
+    if (!host_staging(down_bytes, sizeof(double) * n_down))
         return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_essential_graph_stages: out of host memory for a graph of this size");
-    }
+    double* down = ptr<double>(down_bytes.data(), 0);
     Run r;
-    if ((rc = r.setup(device, n_kf, sim3_in, fixed, n_free, n_edge, edge_v0, edge_v1, meas, fix_scale, 0, nullptr, nullptr))) return rc;
+    if ((rc = r.setup("qsp_essential_graph_stages", device, n_kf, sim3_in, fixed, n_free, n_edge, edge_v0, edge_v1, meas, fix_scale, 0, nullptr, nullptr))) return rc;
     double hl[4], ht[4];
     if ((rc = r.linearise(r.Sa, hl))) return rc;
     // the trial's k_eg_err overwrites E and chi: what the linearisation wrote comes down first
@@ -605,5 +594,3 @@ int essential_graph_stages(int device, int32_t n_kf, const double* sim3_in, cons
     info[0] = hl[0]; info[1] = hl[2]; info[2] = ht[0]; info[3] = ht[1]; info[4] = ht[3]; info[5] = (double)r.dim; info[6] = (double)r.nb;
     return QSP_OK;
 }
-
-}  // namespace qsp

@@ -23,7 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "staging.hpp"
 
 namespace qsp {
 namespace gate {
@@ -398,7 +398,10 @@ __global__ void __launch_bounds__(kThreads) k_object_gate(GateIn in, GateOut out
 
 }  // namespace gate
 
-inline int object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out) {
+}  // namespace qsp
+
+extern "C" int qsp_object_gates(int device, const qsp_object_gate_in* in, qsp_object_gate_out* out) {
+    using namespace qsp;
     if (!in || !out) return qsp_fail(QSP_ERR_INVALID, "qsp_object_gates: null argument");
     const int32_t n = in->n_obj;
     if (n < 0) return qsp_fail(QSP_ERR_INVALID, "qsp_object_gates: negative object count");
@@ -423,60 +426,41 @@ inline int object_gates(int device, const qsp_object_gate_in* in, qsp_object_gat
     for (int i = 0; i < n; ++i)
         if (in->pts_off[i + 1] - in->pts_off[i] > QSP_GATE_MAX_POINTS)
             return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_object_gates: more than 2^20 points in one object");
-    QSP_HIP(hipSetDevice(device));
-    struct Pool {
-        std::vector<void*> p;
-        ~Pool() { for (void* q : p) (void)hipFree(q); }
-    } pool;
-    auto up = [&](const void* src, size_t bytes, void** dst) -> hipError_t {   // src == nullptr: a zeroed buffer
-        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 8));
-        if (e != hipSuccess) return e;
-        pool.p.push_back(*dst);
-        if (!bytes) return hipSuccess;
-        return src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
-    };
-    gate::GateIn gi{};
-    gate::GateOut go{};
-    QSP_HIP(up(in->mode, sizeof(int32_t) * n, (void**)&gi.mode));
-    QSP_HIP(up(in->pts_off, sizeof(int32_t) * (n + 1), (void**)&gi.pts_off));
-    QSP_HIP(up(in->pts_world, sizeof(float) * 3 * np, (void**)&gi.pts));
-    if (any_model) {
-        QSP_HIP(up(in->T_wo, sizeof(float) * 16 * n, (void**)&gi.T_wo));
-        QSP_HIP(up(in->vert_off, sizeof(int32_t) * (n + 1), (void**)&gi.vert_off));
-        QSP_HIP(up(in->verts, sizeof(float) * 3 * nv, (void**)&gi.verts));
-    }
-    QSP_HIP(up(nullptr, np, (void**)&go.erased));
-    QSP_HIP(up(nullptr, np, (void**)&go.outlier));
-    QSP_HIP(up(nullptr, sizeof(float) * 3 * n, (void**)&go.whl));
-    QSP_HIP(up(nullptr, sizeof(float) * 9 * n, (void**)&go.R));
-    QSP_HIP(up(nullptr, sizeof(float) * 3 * n, (void**)&go.centre_w));
-    QSP_HIP(up(nullptr, sizeof(float) * 16 * n, (void**)&go.T_wo_pca));
-    QSP_HIP(up(nullptr, sizeof(int32_t) * n, (void**)&go.status));
+    QSP_TRY(use_device(device, "qsp_object_gates"));
+    // up   [mode | pts_off | pts | T_wo | vert_off | verts]      (the last three are empty without a MODEL object)
+    // down [erased | outlier | whl | R | centre_w | T_wo_pca | status], zeroed before the launch
+    const size_t no = (size_t)n, nm = any_model ? no : 0;
+    StagingLayout L;
+    const size_t a_mode = L.take<int32_t>(no), a_poff = L.take<int32_t>(no + 1), a_pts = L.take<float>(3 * np), a_Two = L.take<float>(16 * nm),
+                 a_voff = L.take<int32_t>(nm ? nm + 1 : 0), a_verts = L.take<float>(3 * nv);
+    L.begin_down();
+    const size_t a_erased = L.take<uint8_t>(np), a_outlier = L.take<uint8_t>(np), a_whl = L.take<float>(3 * no), a_R = L.take<float>(9 * no),
+                 a_centre = L.take<float>(3 * no), a_Tpca = L.take<float>(16 * no), a_status = L.take<int32_t>(no);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
+        return qsp_fail(QSP_ERR_INVALID, "qsp_object_gates: out of host memory for the staging buffers");
+    put(up, a_mode, in->mode, 4 * no); put(up, a_poff, in->pts_off, 4 * (no + 1)); put(up, a_pts, in->pts_world, 12 * np);
+    if (any_model) { put(up, a_Two, in->T_wo, 64 * no); put(up, a_voff, in->vert_off, 4 * (no + 1)); put(up, a_verts, in->verts, 12 * nv); }
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
+    gate::GateIn gi{ptr<int32_t>(d, a_mode), ptr<int32_t>(d, a_poff), ptr<float>(d, a_pts), nullptr, nullptr, nullptr};
+    if (any_model) { gi.T_wo = ptr<float>(d, a_Two); gi.vert_off = ptr<int32_t>(d, a_voff); gi.verts = ptr<float>(d, a_verts); }
+    gate::GateOut go{ptr<uint8_t>(d, a_erased), ptr<uint8_t>(d, a_outlier), ptr<float>(d, a_whl), ptr<float>(d, a_R),
+                     ptr<float>(d, a_centre), ptr<float>(d, a_Tpca), ptr<int32_t>(d, a_status)};
+    QSP_HIP(hipMemsetAsync(d + L.down_begin(), 0, L.down_bytes(), 0));
     hipLaunchKernelGGL(gate::k_object_gate, dim3(n), dim3(gate::kThreads), 0, 0, gi, go);
     QSP_HIP(hipGetLastError());
-    QSP_HIP(hipDeviceSynchronize());
-    // down into host staging first: no output is written unless every copy succeeded
-    std::vector<uint8_t> h_flags(2 * np);
-    std::vector<float> h_f((size_t)31 * n);
-    std::vector<int32_t> h_status(n);
-    if (np) {
-        QSP_HIP(hipMemcpy(h_flags.data(), go.erased, np, hipMemcpyDeviceToHost));
-        QSP_HIP(hipMemcpy(h_flags.data() + np, go.outlier, np, hipMemcpyDeviceToHost));
-    }
-    float *h_whl = h_f.data(), *h_R = h_whl + 3 * (size_t)n, *h_c = h_R + 9 * (size_t)n, *h_T = h_c + 3 * (size_t)n;
-    QSP_HIP(hipMemcpy(h_whl, go.whl, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
-    QSP_HIP(hipMemcpy(h_R, go.R, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
-    QSP_HIP(hipMemcpy(h_c, go.centre_w, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
-    QSP_HIP(hipMemcpy(h_T, go.T_wo_pca, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
-    QSP_HIP(hipMemcpy(h_status.data(), go.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (out->erased && np) std::memcpy(out->erased, h_flags.data(), np);
-    if (out->outlier && np) std::memcpy(out->outlier, h_flags.data() + np, np);
-    if (out->whl) std::memcpy(out->whl, h_whl, sizeof(float) * 3 * n);
-    if (out->R) std::memcpy(out->R, h_R, sizeof(float) * 9 * n);
-    if (out->centre_w) std::memcpy(out->centre_w, h_c, sizeof(float) * 3 * n);
-    if (out->T_wo_pca) std::memcpy(out->T_wo_pca, h_T, sizeof(float) * 16 * n);
-    if (out->status) std::memcpy(out->status, h_status.data(), sizeof(int32_t) * n);
+    // outputs are written only once everything has succeeded
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
+    const char* h = down.data();
+    if (out->erased && np) std::memcpy(out->erased, h + L.in_down(a_erased), np);
+    if (out->outlier && np) std::memcpy(out->outlier, h + L.in_down(a_outlier), np);
+    if (out->whl) std::memcpy(out->whl, h + L.in_down(a_whl), sizeof(float) * 3 * no);
+    if (out->R) std::memcpy(out->R, h + L.in_down(a_R), sizeof(float) * 9 * no);
+    if (out->centre_w) std::memcpy(out->centre_w, h + L.in_down(a_centre), sizeof(float) * 3 * no);
+    if (out->T_wo_pca) std::memcpy(out->T_wo_pca, h + L.in_down(a_Tpca), sizeof(float) * 16 * no);
+    if (out->status) std::memcpy(out->status, h + L.in_down(a_status), sizeof(int32_t) * no);
     return QSP_OK;
 }
-
-}  // namespace qsp

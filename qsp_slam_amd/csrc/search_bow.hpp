@@ -1,6 +1,6 @@
 // search_bow.hpp -- ORBmatcher::SearchByBoW for ALL candidates in one call: the key-frame overload of LoopClosing::ComputeSim3
 // (reference src/ORBmatcher.cc:522-655, shared_is_source = 1) and the frame overload of Tracking::Relocalization (:159-288,
-// shared_is_source = 0).  Included at the end of ba_solver.hip, beside search_sim3.hpp.
+// shared_is_source = 0).  Compiled in c_abi.cpp; popc128 is search_sim3.hpp's.
 //
 // The reference walks the two DBoW2::FeatureVectors in step and, inside a common vocabulary node, matches every source feature
 // against the node's target features, greedily: a target that an earlier source took is gone (vbMatched2[idx2] /
@@ -17,7 +17,13 @@
 // (:1601-1642) as written, the cull and the count.  Contraction is OFF in both kernels.
 #pragma once
 #include <cmath>
+#include <cstring>
 #include <exception>
+#include <string>
+#include <vector>
+
+#include "search_sim3.hpp"
+#include "staging.hpp"
 
 namespace qsp {
 namespace bow {
@@ -217,7 +223,10 @@ static const char* bow_frame_problem(const qsp_bow_frame& f, std::vector<uint8_t
     return nullptr;
 }
 
-int search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_out* out) {
+}  // namespace qsp
+
+extern "C" int qsp_search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_out* out) {
+    using namespace qsp;
     if (!in) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_bow_batch: null input");
     if (in->n_cand < 0) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_bow_batch: negative candidate count");
     if (in->n_cand == 0) return QSP_OK;
@@ -247,35 +256,25 @@ int search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_
     const int64_t n_work = sis ? (int64_t)nc * in->shared->n_nodes : n_node - in->shared->n_nodes;      // one wave per source node
     if (n_slot > 0x7fffffff || n_grid > 0x7fffffff || n_node + nc + 1 > 0x7fffffff || n_work > 0x7fffffff)
         return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_search_by_bow_batch: more than 2^31 - 1 key-point slots or nodes in one call");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_bow_batch: device out of range");
-    QSP_HIP(hipSetDevice(device));
-    // one staging block up (every array starts on a 16-byte boundary), a scratch part the device fills, one block down:
+    QSP_TRY(use_device(device, "qsp_search_by_bow_batch"));
     // up      [frame | work_off | node_id | node_off | feat | desc | angle | elig]
     // scratch [taken]
     // down    [match | match_raw | dist | n_matches | hist | ind]
     const size_t ns = (size_t)n_slot, no = (size_t)n_out, nf = (size_t)nc + 1;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at = (at + bytes + 15) & ~(size_t)15; return a; };
-    const size_t a_frame = take(nf * sizeof(bow::FrameB)), a_work = take(nf * 8), a_nid = take((size_t)n_node * 4),
-                 a_noff = take(((size_t)n_node + nf) * 4), a_feat = take((size_t)n_feat * 4), a_desc = take(ns * 32),
-                 a_angle = take(ns * 4), a_elig = take(ns);
-    const size_t b_up = at;
-    const size_t a_taken = take((size_t)n_taken);
-    const size_t b_down = at;
-    const size_t a_match = take(no * 4), a_raw = take(no * 4), a_dist = take(no * 4), a_count = take((size_t)nc * 4),
-                 a_hist = take((size_t)nc * bow::HISTO_LENGTH * 4), a_ind = take((size_t)nc * 3 * 4);
-    const size_t b_all = at, bytes = (b_all + 255) & ~(size_t)255;
-    std::vector<char> up, down;                                            // (no exception may leave an extern "C" function)
-    try {
-        up.assign(b_up, 0);
-        down.resize(b_all - b_down);
-    } catch (const std::exception&) {
+    StagingLayout L;
+    const size_t a_frame = L.take<bow::FrameB>(nf), a_work = L.take<int64_t>(nf), a_nid = L.take<int32_t>((size_t)n_node),
+                 a_noff = L.take<int32_t>((size_t)n_node + nf), a_feat = L.take<int32_t>((size_t)n_feat), a_desc = L.take<uint8_t>(ns * 32),
+                 a_angle = L.take<float>(ns), a_elig = L.take<uint8_t>(ns);
+    L.begin_scratch();
+    const size_t a_taken = L.take<uint8_t>((size_t)n_taken);
+    L.begin_down();
+    const size_t a_match = L.take<int32_t>(no), a_raw = L.take<int32_t>(no), a_dist = L.take<int32_t>(no), a_count = L.take<int32_t>((size_t)nc),
+                 a_hist = L.take<int32_t>((size_t)nc * bow::HISTO_LENGTH), a_ind = L.take<int32_t>((size_t)nc * 3);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
         return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_bow_batch: out of host memory for the staging buffers");
-    }
-    bow::FrameB* fp = (bow::FrameB*)(up.data() + a_frame);
-    int64_t* work = (int64_t*)(up.data() + a_work);
+    bow::FrameB* fp = ptr<bow::FrameB>(up.data(), a_frame);
+    int64_t* work = ptr<int64_t>(up.data(), a_work);
     size_t slot = 0, node = 0, feat = 0;
     int64_t wk = 0;
     for (int32_t f = 0; f <= nc; ++f) {
@@ -301,24 +300,19 @@ int search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_
         slot += n; node += nn; feat += nl;
     }
     work[nc] = wk;
-    // the device block comes from (and returns to) the per-device cache the bundle adjustment keeps (qsp_ba_release_caches frees it)
-    size_t got = bytes;
-    char* d = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
-    if (!d) QSP_HIP(hipMalloc((void**)&d, bytes));
-    struct Back {
-        int device; char* d; size_t bytes;
-        ~Back() { if (!buf_cache_put(g_dev_cache, device, d, bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
-    } back{device, d, got};
-    QSP_HIP(hipMemcpy(d, up.data(), b_up, hipMemcpyHostToDevice));
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
     bow::In k;
-    k.frame = (const bow::FrameB*)(d + a_frame); k.work_off = (const int64_t*)(d + a_work);
-    k.node_id = (const int32_t*)(d + a_nid); k.node_off = (const int32_t*)(d + a_noff); k.feat = (const int32_t*)(d + a_feat);
-    k.desc = (const uint8_t*)(d + a_desc); k.angle = (const float*)(d + a_angle); k.elig = (const uint8_t*)(d + a_elig);
+    k.frame = ptr<bow::FrameB>(d, a_frame); k.work_off = ptr<int64_t>(d, a_work);
+    k.node_id = ptr<int32_t>(d, a_nid); k.node_off = ptr<int32_t>(d, a_noff); k.feat = ptr<int32_t>(d, a_feat);
+    k.desc = ptr<uint8_t>(d, a_desc); k.angle = ptr<float>(d, a_angle); k.elig = ptr<uint8_t>(d, a_elig);
     k.n_cand = nc; k.n0 = (int32_t)n0; k.shared_is_source = sis ? 1 : 0; k.th = in->th; k.th_inclusive = in->th_inclusive ? 1 : 0;
     k.check_ori = in->check_orientation ? 1 : 0; k.nn_ratio = in->nn_ratio;
-    uint8_t* d_taken = (uint8_t*)(d + a_taken);
-    int32_t *d_match = (int32_t*)(d + a_match), *d_raw = (int32_t*)(d + a_raw), *d_dist = (int32_t*)(d + a_dist);
-    int32_t *d_count = (int32_t*)(d + a_count), *d_hist = (int32_t*)(d + a_hist), *d_ind = (int32_t*)(d + a_ind);
+    uint8_t* d_taken = ptr<uint8_t>(d, a_taken);
+    int32_t *d_match = ptr<int32_t>(d, a_match), *d_raw = ptr<int32_t>(d, a_raw), *d_dist = ptr<int32_t>(d, a_dist);
+    int32_t *d_count = ptr<int32_t>(d, a_count), *d_hist = ptr<int32_t>(d, a_hist), *d_ind = ptr<int32_t>(d, a_ind);
     // two fills and two launches on one stream, no host round trip in between
     if (n_taken) QSP_HIP(hipMemsetAsync(d_taken, 0, (size_t)n_taken, 0));
     if (no) QSP_HIP(hipMemsetAsync(d_raw, 0xff, (a_count - a_raw), 0));         // match_raw and dist: -1 everywhere
@@ -329,17 +323,15 @@ int search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_
     hipLaunchKernelGGL(bow::k_bow_rot, dim3((unsigned)nc), dim3(256), 0, 0, k, d_raw, d_match, d_count, d_hist, d_ind);
     QSP_HIP(hipGetLastError());
     // outputs are written only once everything has succeeded
-    QSP_HIP(hipMemcpy(down.data(), d + b_down, b_all - b_down, hipMemcpyDeviceToHost));
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
     const char* h = down.data();
     if (no) {
-        memcpy(out->match, h + (a_match - b_down), 4 * no);
-        if (out->match_raw) memcpy(out->match_raw, h + (a_raw - b_down), 4 * no);
-        if (out->dist) memcpy(out->dist, h + (a_dist - b_down), 4 * no);
+        memcpy(out->match, h + L.in_down(a_match), 4 * no);
+        if (out->match_raw) memcpy(out->match_raw, h + L.in_down(a_raw), 4 * no);
+        if (out->dist) memcpy(out->dist, h + L.in_down(a_dist), 4 * no);
     }
-    memcpy(out->n_matches, h + (a_count - b_down), 4 * (size_t)nc);
-    if (out->hist) memcpy(out->hist, h + (a_hist - b_down), 4 * (size_t)nc * bow::HISTO_LENGTH);
-    if (out->ind) memcpy(out->ind, h + (a_ind - b_down), 4 * (size_t)nc * 3);
+    memcpy(out->n_matches, h + L.in_down(a_count), 4 * (size_t)nc);
+    if (out->hist) memcpy(out->hist, h + L.in_down(a_hist), 4 * (size_t)nc * bow::HISTO_LENGTH);
+    if (out->ind) memcpy(out->ind, h + L.in_down(a_ind), 4 * (size_t)nc * 3);
     return QSP_OK;
 }
-
-}  // namespace qsp

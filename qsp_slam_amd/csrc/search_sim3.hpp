@@ -1,5 +1,5 @@
 // search_sim3.hpp -- ORBmatcher::SearchBySim3 (reference src/ORBmatcher.cc:1102-1326) for ALL loop candidates of a key frame in one
-// call.  Included at the end of ba_solver.hip, beside sim3_ransac.hpp.
+// call.  Compiled in c_abi.cpp.
 //
 // The reference runs, per candidate, two serial passes (key frame 1 -> 2 and 2 -> 1): project a map point through the candidate
 // Sim3, walk the target frame's feature grid inside a level-dependent radius (KeyFrame::GetFeaturesInArea, KeyFrame.cc:570-609),
@@ -12,7 +12,11 @@
 //
 // Every function below evaluates with contraction OFF: the float32 operations of the reference in its order.
 #pragma once
-#include <exception>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "staging.hpp"
 
 namespace qsp {
 namespace search {
@@ -196,7 +200,10 @@ static const char* search_frame_problem(const qsp_orb_frame& f) {
     return nullptr;
 }
 
-int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out) {
+}  // namespace qsp
+
+extern "C" int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out) {
+    using namespace qsp;
     if (!in) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null input");
     if (in->n_cand < 0) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: negative candidate count");
     if (in->n_cand == 0) return QSP_OK;
@@ -223,34 +230,24 @@ int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_si
     const int64_t n_slot = (int64_t)n1 + n2_all, n_out1 = (int64_t)nc * n1, n_work = n_out1 + n2_all;
     if (n_slot > 0x7fffffff || n_work > 0x7fffffff)
         return qsp_fail(QSP_ERR_UNSUPPORTED, "qsp_search_by_sim3_batch: more than 2^31 - 1 key-point slots in one call");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: device out of range");
-    QSP_HIP(hipSetDevice(device));
-    // one staging block up (every array starts on a 16-byte boundary), one down:
+    QSP_TRY(use_device(device, "qsp_search_by_sim3_batch"));
     // up   [frame | cand | work_off | off2 | kp | octave | desc | has_point | Xw | dist_min_inv | dist_max_inv | dist_max | mp_desc | pre1 | pre2]
     // down [match12 | best1 | dist1 | best2 | dist2 | n_found]
     const size_t ns = (size_t)n_slot, no1 = (size_t)n_out1, no2 = (size_t)n2_all, nf = (size_t)nc + 1;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at = (at + bytes + 15) & ~(size_t)15; return a; };
-    const size_t a_frame = take(nf * sizeof(search::FrameP)), a_cand = take((size_t)nc * sizeof(search::CandP)), a_work = take(nf * 8),
-                 a_off2 = take(nf * 4), a_kp = take(ns * 8), a_oct = take(ns * 4), a_desc = take(ns * 32), a_has = take(ns),
-                 a_Xw = take(ns * 12), a_dmin = take(ns * 4), a_dmaxi = take(ns * 4), a_dmax = take(ns * 4), a_mpd = take(ns * 32),
-                 a_pre1 = take(no1), a_pre2 = take(no2);
-    const size_t b_up = at;
-    const size_t a_match = take(no1 * 4), a_b1 = take(no1 * 4), a_d1 = take(no1 * 4), a_b2 = take(no2 * 4), a_d2 = take(no2 * 4),
-                 a_found = take((size_t)nc * 4);
-    const size_t b_all = at, bytes = (b_all + 255) & ~(size_t)255;
-    std::vector<char> up, down;                                            // (no exception may leave an extern "C" function)
-    try {
-        up.assign(b_up, 0);
-        down.resize(b_all - b_up);
-    } catch (const std::exception&) {
+    StagingLayout L;
+    const size_t a_frame = L.take<search::FrameP>(nf), a_cand = L.take<search::CandP>((size_t)nc), a_work = L.take<int64_t>(nf),
+                 a_off2 = L.take<int32_t>(nf), a_kp = L.take<float>(ns * 2), a_oct = L.take<int32_t>(ns), a_desc = L.take<uint8_t>(ns * 32),
+                 a_has = L.take<uint8_t>(ns), a_Xw = L.take<float>(ns * 3), a_dmin = L.take<float>(ns), a_dmaxi = L.take<float>(ns),
+                 a_dmax = L.take<float>(ns), a_mpd = L.take<uint8_t>(ns * 32), a_pre1 = L.take<uint8_t>(no1), a_pre2 = L.take<uint8_t>(no2);
+    L.begin_down();
+    const size_t a_match = L.take<int32_t>(no1), a_b1 = L.take<int32_t>(no1), a_d1 = L.take<int32_t>(no1), a_b2 = L.take<int32_t>(no2),
+                 a_d2 = L.take<int32_t>(no2), a_found = L.take<int32_t>((size_t)nc);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
         return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: out of host memory for the staging buffers");
-    }
-    search::FrameP* fp = (search::FrameP*)(up.data() + a_frame);
-    search::CandP* cp = (search::CandP*)(up.data() + a_cand);
-    int64_t* work = (int64_t*)(up.data() + a_work);
+    search::FrameP* fp = ptr<search::FrameP>(up.data(), a_frame);
+    search::CandP* cp = ptr<search::CandP>(up.data(), a_cand);
+    int64_t* work = ptr<int64_t>(up.data(), a_work);
     size_t slot = 0;
     for (int32_t f = 0; f <= nc; ++f) {
         const qsp_orb_frame& F = f ? in->kf2[f - 1] : *in->kf1;
@@ -286,29 +283,22 @@ int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_si
         work[c] = (int64_t)c * n1 + in->off2[c];
     }
     work[nc] = n_work;
-    memcpy(up.data() + a_off2, in->off2, nf * 4);
-    if (no1) memcpy(up.data() + a_pre1, in->pre1, no1);
-    if (no2) memcpy(up.data() + a_pre2, in->pre2, no2);
-    // the device block comes from (and returns to) the per-device cache the bundle adjustment keeps (qsp_ba_release_caches frees it)
-    size_t got = bytes;
-    char* d = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
-    if (!d) QSP_HIP(hipMalloc((void**)&d, bytes));
-    struct Back {
-        int device; char* d; size_t bytes;
-        ~Back() { if (!buf_cache_put(g_dev_cache, device, d, bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
-    } back{device, d, got};
-    QSP_HIP(hipMemcpy(d, up.data(), b_up, hipMemcpyHostToDevice));
+    put(up, a_off2, in->off2, nf * 4); put(up, a_pre1, in->pre1, no1); put(up, a_pre2, in->pre2, no2);
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
     search::In k;
-    k.frame = (const search::FrameP*)(d + a_frame); k.cand = (const search::CandP*)(d + a_cand);
-    k.work_off = (const int64_t*)(d + a_work); k.off2 = (const int32_t*)(d + a_off2);
-    k.kp = (const float*)(d + a_kp); k.octave = (const int32_t*)(d + a_oct); k.desc = (const uint8_t*)(d + a_desc);
-    k.has_point = (const uint8_t*)(d + a_has); k.Xw = (const float*)(d + a_Xw);
-    k.dist_min_inv = (const float*)(d + a_dmin); k.dist_max_inv = (const float*)(d + a_dmaxi); k.dist_max = (const float*)(d + a_dmax);
-    k.mp_desc = (const uint8_t*)(d + a_mpd); k.pre1 = (const uint8_t*)(d + a_pre1); k.pre2 = (const uint8_t*)(d + a_pre2);
+    k.frame = ptr<search::FrameP>(d, a_frame); k.cand = ptr<search::CandP>(d, a_cand);
+    k.work_off = ptr<int64_t>(d, a_work); k.off2 = ptr<int32_t>(d, a_off2);
+    k.kp = ptr<float>(d, a_kp); k.octave = ptr<int32_t>(d, a_oct); k.desc = ptr<uint8_t>(d, a_desc);
+    k.has_point = ptr<uint8_t>(d, a_has); k.Xw = ptr<float>(d, a_Xw);
+    k.dist_min_inv = ptr<float>(d, a_dmin); k.dist_max_inv = ptr<float>(d, a_dmaxi); k.dist_max = ptr<float>(d, a_dmax);
+    k.mp_desc = ptr<uint8_t>(d, a_mpd); k.pre1 = ptr<uint8_t>(d, a_pre1); k.pre2 = ptr<uint8_t>(d, a_pre2);
     k.n_cand = nc; k.n1 = n1;
-    int32_t* d_match = (int32_t*)(d + a_match);
-    int32_t *d_b1 = (int32_t*)(d + a_b1), *d_d1 = (int32_t*)(d + a_d1), *d_b2 = (int32_t*)(d + a_b2), *d_d2 = (int32_t*)(d + a_d2);
-    int32_t* d_found = (int32_t*)(d + a_found);
+    int32_t* d_match = ptr<int32_t>(d, a_match);
+    int32_t *d_b1 = ptr<int32_t>(d, a_b1), *d_d1 = ptr<int32_t>(d, a_d1), *d_b2 = ptr<int32_t>(d, a_b2), *d_d2 = ptr<int32_t>(d, a_d2);
+    int32_t* d_found = ptr<int32_t>(d, a_found);
     // two launches and one fill on one stream, no host round trip in between
     QSP_HIP(hipMemsetAsync(d_found, 0, 4 * (size_t)nc, 0));
     if (n_work) {
@@ -320,15 +310,13 @@ int search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_si
         QSP_HIP(hipGetLastError());
     }
     // outputs are written only once everything has succeeded
-    QSP_HIP(hipMemcpy(down.data(), d + b_up, b_all - b_up, hipMemcpyDeviceToHost));
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
     const char* h = down.data();
-    if (no1) memcpy(out->match12, h + (a_match - b_up), 4 * no1);
-    memcpy(out->n_found, h + (a_found - b_up), 4 * (size_t)nc);
+    if (no1) memcpy(out->match12, h + L.in_down(a_match), 4 * no1);
+    memcpy(out->n_found, h + L.in_down(a_found), 4 * (size_t)nc);
     if (out->best1) {
-        if (no1) { memcpy(out->best1, h + (a_b1 - b_up), 4 * no1); memcpy(out->dist1, h + (a_d1 - b_up), 4 * no1); }
-        if (no2) { memcpy(out->best2, h + (a_b2 - b_up), 4 * no2); memcpy(out->dist2, h + (a_d2 - b_up), 4 * no2); }
+        if (no1) { memcpy(out->best1, h + L.in_down(a_b1), 4 * no1); memcpy(out->dist1, h + L.in_down(a_d1), 4 * no1); }
+        if (no2) { memcpy(out->best2, h + L.in_down(a_b2), 4 * no2); memcpy(out->dist2, h + L.in_down(a_d2), 4 * no2); }
     }
     return QSP_OK;
 }
-
-}  // namespace qsp

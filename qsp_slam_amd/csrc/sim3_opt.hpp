@@ -1,5 +1,5 @@
 // sim3_opt.hpp -- Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1050-1245) for ALL loop candidates of a key frame in one
-// launch.  Included at the end of ba_solver.hip.
+// launch.  Included at the end of ba_solver.hip (ba::skew3 is the solver's).
 //
 // The reference's caller (LoopClosing::ComputeSim3, src/LoopClosing.cc) walks its candidate key frames one after another and
 // builds, solves and tears down one g2o graph each: one free VertexSim3Expmap (7 unknowns: rotation, translation, log scale),
@@ -22,7 +22,7 @@
 #pragma once
 #include <float.h>
 
-#include <exception>
+#include "staging.hpp"
 
 namespace qsp {
 namespace sim3 {
@@ -430,51 +430,42 @@ extern "C" int qsp_sim3_optimize_batch(int device, int32_t n_cand, const int32_t
     if (nm && (!P1c || !P2c || !obs1 || !obs2 || !info1 || !info2 || !inlier))
         return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_optimize_batch: null match array");
     if (!(th2 >= 0)) return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_optimize_batch: th2 must not be negative");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_optimize_batch: device out of range");
-    QSP_HIP(hipSetDevice(device));
-    // one staging block up, one down: [doubles: K1 K2 S0 P1 P2 o1 o2 i1 i2 | chi (device only)] [Out x n_cand] [off] [inlier]
-    const size_t nd_in = 16 * nc + 12 * nm, nd = nd_in + 2 * nm;
-    const size_t o_out = sizeof(double) * nd, o_off = o_out + sizeof(sim3::Out) * nc, o_inl = o_off + sizeof(int32_t) * (nc + 1);
-    const size_t bytes = (o_inl + nm + 255) & ~(size_t)255;
-    std::vector<double> up;
-    std::vector<char> down;                                                // (no exception may leave an extern "C" function)
-    try {
-        up.resize(nd_in + (sizeof(int32_t) * (nc + 1) + 7) / 8);
-        down.resize(bytes - o_out);
-    } catch (const std::exception&) {
+    QSP_TRY(use_device(device, "qsp_sim3_optimize_batch"));
+    // up      [K1 | K2 | S0 | P1 | P2 | o1 | o2 | i1 | i2 | off]
+    // scratch [chi]
+    // down    [Out x n_cand | inlier]
+    StagingLayout L;
+    const size_t aK1 = L.take<double>(4 * nc), aK2 = L.take<double>(4 * nc), aS0 = L.take<double>(8 * nc), aP1 = L.take<double>(3 * nm),
+                 aP2 = L.take<double>(3 * nm), ao1 = L.take<double>(2 * nm), ao2 = L.take<double>(2 * nm), ai1 = L.take<double>(nm),
+                 ai2 = L.take<double>(nm), a_off = L.take<int32_t>(nc + 1);
+    L.begin_scratch();
+    const size_t a_chi = L.take<double>(2 * nm);
+    L.begin_down();
+    const size_t a_out = L.take<sim3::Out>(nc), a_inl = L.take<uint8_t>(nm);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
         return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_optimize_batch: out of host memory for the staging buffers");
-    }
-    double* h = up.data();
-    size_t at = 0;
-    auto put = [&](const double* src, size_t n) { if (n) memcpy(h + at, src, sizeof(double) * n); at += n; return at - n; };
-    const size_t aK1 = put(K1, 4 * nc), aK2 = put(K2, 4 * nc), aS0 = put(sim3_in, 8 * nc), aP1 = put(P1c, 3 * nm), aP2 = put(P2c, 3 * nm),
-                 ao1 = put(obs1, 2 * nm), ao2 = put(obs2, 2 * nm), ai1 = put(info1, nm), ai2 = put(info2, nm);
-    memcpy(h + nd_in, match_off, sizeof(int32_t) * (nc + 1));
-    // the device block comes from (and returns to) the per-device cache the bundle adjustment keeps (qsp_ba_release_caches frees it)
-    size_t got = bytes;
-    char* d = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
-    if (!d) QSP_HIP(hipMalloc((void**)&d, bytes));
-    struct Back {
-        int device; char* d; size_t bytes;
-        ~Back() { if (!buf_cache_put(g_dev_cache, device, d, bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
-    } back{device, d, got};
-    double* dd = (double*)d;
-    QSP_HIP(hipMemcpy(dd, h, sizeof(double) * nd_in, hipMemcpyHostToDevice));
-    QSP_HIP(hipMemcpy(d + o_off, h + nd_in, sizeof(int32_t) * (nc + 1), hipMemcpyHostToDevice));
+    put(up, aK1, K1, 32 * nc); put(up, aK2, K2, 32 * nc); put(up, aS0, sim3_in, 64 * nc); put(up, aP1, P1c, 24 * nm); put(up, aP2, P2c, 24 * nm);
+    put(up, ao1, obs1, 16 * nm); put(up, ao2, obs2, 16 * nm); put(up, ai1, info1, 8 * nm); put(up, ai2, info2, 8 * nm);
+    put(up, a_off, match_off, 4 * (nc + 1));
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
     sim3::In in;
     in.n_cand = n_cand; in.fix_scale = fix_scale ? 1 : 0;
-    in.off = (const int32_t*)(d + o_off);
-    in.K1 = dd + aK1; in.K2 = dd + aK2; in.S0 = dd + aS0; in.P1 = dd + aP1; in.P2 = dd + aP2;
-    in.o1 = dd + ao1; in.o2 = dd + ao2; in.i1 = dd + ai1; in.i2 = dd + ai2;
+    in.off = ptr<int32_t>(d, a_off);
+    in.K1 = ptr<double>(d, aK1); in.K2 = ptr<double>(d, aK2); in.S0 = ptr<double>(d, aS0); in.P1 = ptr<double>(d, aP1);
+    in.P2 = ptr<double>(d, aP2); in.o1 = ptr<double>(d, ao1); in.o2 = ptr<double>(d, ao2); in.i1 = ptr<double>(d, ai1);
+    in.i2 = ptr<double>(d, ai2);
     in.th2 = th2;
     in.delta = (double)sqrtf((float)th2);                                  // const float deltaHuber = sqrt(th2), :1099
-    hipLaunchKernelGGL(sim3::k_sim3_opt, dim3(n_cand), dim3(64), 0, 0, in, (uint8_t*)(d + o_inl), dd + nd_in, (sim3::Out*)(d + o_out));
+    hipLaunchKernelGGL(sim3::k_sim3_opt, dim3(n_cand), dim3(64), 0, 0, in, ptr<uint8_t>(d, a_inl), ptr<double>(d, a_chi),
+                       ptr<sim3::Out>(d, a_out));
     QSP_HIP(hipGetLastError());
     // outputs are written only once everything has succeeded
-    QSP_HIP(hipMemcpy(down.data(), d + o_out, o_inl + nm - o_out, hipMemcpyDeviceToHost));
-    const sim3::Out* O = (const sim3::Out*)down.data();
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
+    const sim3::Out* O = ptr<sim3::Out>(down.data(), L.in_down(a_out));
     for (size_t c = 0; c < nc; ++c) {
         memcpy(sim3_out + 8 * c, O[c].S, sizeof(double) * 8);
         n_inliers[c] = O[c].n_inliers;
@@ -484,6 +475,6 @@ extern "C" int qsp_sim3_optimize_batch(int device, int32_t n_cand, const int32_t
             memcpy(trace[c].trace, O[c].trace, sizeof(O[c].trace));
         }
     }
-    if (nm) memcpy(inlier, down.data() + (o_inl - o_out), nm);
+    if (nm) memcpy(inlier, down.data() + L.in_down(a_inl), nm);
     return QSP_OK;
 }

@@ -1,5 +1,5 @@
-// sim3_ransac.hpp -- Sim3Solver (reference src/Sim3Solver.cc) for ALL loop candidates of a key frame in one call.  Included at the
-// end of ba_solver.hip.
+// sim3_ransac.hpp -- Sim3Solver (reference src/Sim3Solver.cc) for ALL loop candidates of a key frame in one call.  Compiled in
+// c_abi.cpp.
 //
 // The reference's caller (LoopClosing::ComputeSim3, src/LoopClosing.cc:292-352) drives one Sim3Solver per candidate five RANSAC
 // iterations at a time, round-robin.  Per candidate that is up to 300 hypotheses, each Horn's closed form on three point pairs
@@ -16,7 +16,10 @@
 #pragma once
 #include <float.h>
 
-#include <exception>
+#include <cstring>
+#include <vector>
+
+#include "staging.hpp"
 
 namespace qsp {
 namespace ransac {
@@ -310,10 +313,14 @@ __global__ __launch_bounds__(64) void k_sim3_ransac_select(In in, const unsigned
 
 }  // namespace ransac
 
-int sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, const int32_t* n_its, const int32_t* trip_off,
-                      const int32_t* triples, const float* K1, const float* K2, const float* X1c, const float* X2c, const float* sigma2_1,
-                      const float* sigma2_2, int32_t min_inliers, int32_t fix_scale, int32_t* first_it, float* R12, float* t12, float* s12,
-                      uint8_t* inlier, int32_t* n_inliers, int32_t* hyp_inliers) {
+}  // namespace qsp
+
+extern "C" int qsp_sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, const int32_t* n_its, const int32_t* trip_off,
+                                     const int32_t* triples, const float* K1, const float* K2, const float* X1c, const float* X2c,
+                                     const float* sigma2_1, const float* sigma2_2, int32_t min_inliers, int32_t fix_scale,
+                                     int32_t* first_it, float* R12, float* t12, float* s12, uint8_t* inlier, int32_t* n_inliers,
+                                     int32_t* hyp_inliers) {
+    using namespace qsp;
     if (n_cand < 0) return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_ransac_batch: negative candidate count");
     if (n_cand == 0) return QSP_OK;
     if (!match_off || !n_its || !trip_off || !K1 || !K2 || !first_it || !R12 || !t12 || !s12 || !n_inliers)
@@ -339,53 +346,38 @@ int sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, cons
             if (a == b || a == d || b == d) return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_ransac_batch: a triple repeats an index");
         }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return qsp_fail(QSP_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_ransac_batch: device out of range");
-    QSP_HIP(hipSetDevice(device));
-    // one staging block up, one down, in 4-byte words:
-    // up   [off | n_its | trip_off | triples | K1 | K2 | X1 | X2 | sig1 | sig2]
-    // down [first_it | n_inliers | R | t | s | hyp_count] [inlier bytes]; device only: [first]
-    const size_t w_up = (nc + 1) + nc + (nc + 1) + 3 * nt + 8 * nc + 8 * nm;
-    const size_t w_down = 2 * nc + 13 * nc + nt;
-    const size_t o_down = 4 * w_up, o_inl = o_down + 4 * w_down, o_first = (o_inl + nm + 3) & ~(size_t)3;
-    const size_t bytes = (o_first + 4 * nc + 255) & ~(size_t)255;
-    std::vector<int32_t> up;
-    std::vector<char> down;                                                // (no exception may leave an extern "C" function)
-    try {
-        up.resize(w_up);
-        down.resize(o_first - o_down);
-    } catch (const std::exception&) {
+    QSP_TRY(use_device(device, "qsp_sim3_ransac_batch"));
+    // up      [off | n_its | trip_off | triples | K1 | K2 | X1 | X2 | sig1 | sig2]
+    // scratch [first]
+    // down    [first_it | n_inliers | R | t | s | hyp_count | inlier]
+    StagingLayout L;
+    const size_t a_off = L.take<int32_t>(nc + 1), a_its = L.take<int32_t>(nc), a_toff = L.take<int32_t>(nc + 1), a_tri = L.take<int32_t>(3 * nt),
+                 a_K1 = L.take<float>(4 * nc), a_K2 = L.take<float>(4 * nc), a_X1 = L.take<float>(3 * nm), a_X2 = L.take<float>(3 * nm),
+                 a_s1 = L.take<float>(nm), a_s2 = L.take<float>(nm);
+    L.begin_scratch();
+    const size_t a_first = L.take<unsigned>(nc);
+    L.begin_down();
+    const size_t a_first_it = L.take<int32_t>(nc), a_ninl = L.take<int32_t>(nc), a_R = L.take<float>(9 * nc), a_t = L.take<float>(3 * nc),
+                 a_s = L.take<float>(nc), a_hyp = L.take<int32_t>(nt), a_inl = L.take<uint8_t>(nm);
+    std::vector<char> up, down;
+    if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
         return qsp_fail(QSP_ERR_INVALID, "qsp_sim3_ransac_batch: out of host memory for the staging buffers");
-    }
-    size_t at = 0;
-    auto put = [&](const void* src, size_t words) { if (words) memcpy(up.data() + at, src, 4 * words); at += words; return at - words; };
-    const size_t a_off = put(match_off, nc + 1), a_its = put(n_its, nc), a_toff = put(trip_off, nc + 1), a_tri = put(triples, 3 * nt),
-                 a_K1 = put(K1, 4 * nc), a_K2 = put(K2, 4 * nc), a_X1 = put(X1c, 3 * nm), a_X2 = put(X2c, 3 * nm), a_s1 = put(sigma2_1, nm),
-                 a_s2 = put(sigma2_2, nm);
-    // the device block comes from (and returns to) the per-device cache the bundle adjustment keeps (qsp_ba_release_caches frees it)
-    size_t got = bytes;
-    char* d = (char*)buf_cache_take(g_dev_cache, device, bytes, 0, &got);
-    if (!d) QSP_HIP(hipMalloc((void**)&d, bytes));
-    struct Back {
-        int device; char* d; size_t bytes;
-        ~Back() { if (!buf_cache_put(g_dev_cache, device, d, bytes, 0, (size_t)512 << 20)) (void)hipFree(d); }
-    } back{device, d, got};
-    QSP_HIP(hipMemcpy(d, up.data(), 4 * w_up, hipMemcpyHostToDevice));
-    const int32_t* di = (const int32_t*)d;
-    const float* df = (const float*)d;
+    put(up, a_off, match_off, 4 * (nc + 1)); put(up, a_its, n_its, 4 * nc); put(up, a_toff, trip_off, 4 * (nc + 1)); put(up, a_tri, triples, 12 * nt);
+    put(up, a_K1, K1, 16 * nc); put(up, a_K2, K2, 16 * nc); put(up, a_X1, X1c, 12 * nm); put(up, a_X2, X2c, 12 * nm);
+    put(up, a_s1, sigma2_1, 4 * nm); put(up, a_s2, sigma2_2, 4 * nm);
+    DeviceBlock blk;
+    QSP_TRY(blk.take(device, L.total()));
+    QSP_TRY(blk.upload(up.data(), L.up_bytes()));
+    char* d = blk.data();
     ransac::In in;
-    in.off = di + a_off; in.n_its = di + a_its; in.trip_off = di + a_toff; in.triples = di + a_tri;
-    in.K1 = df + a_K1; in.K2 = df + a_K2; in.X1 = df + a_X1; in.X2 = df + a_X2; in.sig1 = df + a_s1; in.sig2 = df + a_s2;
+    in.off = ptr<int32_t>(d, a_off); in.n_its = ptr<int32_t>(d, a_its); in.trip_off = ptr<int32_t>(d, a_toff);
+    in.triples = ptr<int32_t>(d, a_tri); in.K1 = ptr<float>(d, a_K1); in.K2 = ptr<float>(d, a_K2); in.X1 = ptr<float>(d, a_X1);
+    in.X2 = ptr<float>(d, a_X2); in.sig1 = ptr<float>(d, a_s1); in.sig2 = ptr<float>(d, a_s2);
     in.min_inliers = min_inliers; in.fix_scale = fix_scale ? 1 : 0;
-    int32_t* d_first_it = (int32_t*)(d + o_down);
-    int32_t* d_ninl = d_first_it + nc;
-    float* d_R = (float*)(d_ninl + nc);
-    float* d_t = d_R + 9 * nc;
-    float* d_s = d_t + 3 * nc;
-    int32_t* d_hyp = (int32_t*)(d_s + nc);
-    uint8_t* d_inl = (uint8_t*)(d + o_inl);
-    unsigned* d_first = (unsigned*)(d + o_first);
+    int32_t *d_first_it = ptr<int32_t>(d, a_first_it), *d_ninl = ptr<int32_t>(d, a_ninl), *d_hyp = ptr<int32_t>(d, a_hyp);
+    float *d_R = ptr<float>(d, a_R), *d_t = ptr<float>(d, a_t), *d_s = ptr<float>(d, a_s);
+    uint8_t* d_inl = ptr<uint8_t>(d, a_inl);
+    unsigned* d_first = ptr<unsigned>(d, a_first);
     // both kernels and the two fills on one stream, no host round trip in between
     if (nt) QSP_HIP(hipMemsetAsync(d_hyp, 0, 4 * nt, 0));                 // the triples beyond n_its count 0
     QSP_HIP(hipMemsetAsync(d_first, 0xff, 4 * nc, 0));                     // ransac::NONE
@@ -396,16 +388,14 @@ int sim3_ransac_batch(int device, int32_t n_cand, const int32_t* match_off, cons
     hipLaunchKernelGGL(ransac::k_sim3_ransac_select, dim3(n_cand), dim3(64), 0, 0, in, d_first, d_first_it, d_ninl, d_R, d_t, d_s, d_inl);
     QSP_HIP(hipGetLastError());
     // outputs are written only once everything has succeeded
-    QSP_HIP(hipMemcpy(down.data(), d + o_down, o_inl + nm - o_down, hipMemcpyDeviceToHost));
+    QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
     const char* h = down.data();
-    memcpy(first_it, h, 4 * nc);
-    memcpy(n_inliers, h + 4 * nc, 4 * nc);
-    memcpy(R12, h + 8 * nc, 36 * nc);
-    memcpy(t12, h + 44 * nc, 12 * nc);
-    memcpy(s12, h + 56 * nc, 4 * nc);
-    if (hyp_inliers && nt) memcpy(hyp_inliers, h + 60 * nc, 4 * nt);
-    if (nm) memcpy(inlier, h + (o_inl - o_down), nm);
+    memcpy(first_it, h + L.in_down(a_first_it), 4 * nc);
+    memcpy(n_inliers, h + L.in_down(a_ninl), 4 * nc);
+    memcpy(R12, h + L.in_down(a_R), 36 * nc);
+    memcpy(t12, h + L.in_down(a_t), 12 * nc);
+    memcpy(s12, h + L.in_down(a_s), 4 * nc);
+    if (hyp_inliers && nt) memcpy(hyp_inliers, h + L.in_down(a_hyp), 4 * nt);
+    if (nm) memcpy(inlier, h + L.in_down(a_inl), nm);
     return QSP_OK;
 }
-
-}  // namespace qsp

@@ -2,9 +2,10 @@
 """Times the object map-point gate (qsp_object_gates): one batched call over 1 / 16 / 64 objects of 2 000 points -- half PCA,
 half MODEL with 600-vertex meshes -- against a loop of single-object calls over the same objects.  Wall clock around the
 C-ABI call, which uploads, launches, synchronises and downloads, so a time is what a caller waits.  Median (min - max) ms per
-call over `reps` repetitions after a warm-up; writes profiles/object_gate.txt.  The file is a record, not a bar.
+call over `reps` repetitions after a warm-up; writes profiles/object_gate.txt.  The file is a record, not a bar.  The same clock
+is then put around one ellipsoid plane fit (qsp_ellipsoid_fit_planes through its Python wrapper) of 1 / 16 / 64 ellipsoids.
 
-usage: python tools/time_object_gate.py [reps]"""
+usage: python tools/time_object_gate.py [reps] [--out FILE]"""
 import os
 import sys
 import time
@@ -15,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from qsp_slam_amd import _lib, object_gate  # noqa: E402
+from qsp_slam_amd.ellipsoid import optimize_ellipsoids_using_planes  # noqa: E402
 from tests import object_gate_cases as GC  # noqa: E402
 
 
@@ -46,7 +48,12 @@ def timed(fn, reps):
 
 
 def main():
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    argv = sys.argv[1:]
+    out = os.path.join(ROOT, "profiles", "object_gate.txt")
+    if "--out" in argv:
+        out = argv[argv.index("--out") + 1]
+        del argv[argv.index("--out"):argv.index("--out") + 2]
+    reps = int(argv[0]) if argv else 50
     if _lib.lib().qsp_device_count() < 1:
         raise SystemExit("no GPU visible: nothing is measured without one")
     mesh = GC.mesh600()
@@ -67,9 +74,18 @@ def main():
         s = timed(lambda: [object_gate.object_gates(*a) for a in singles], reps)
         lines.append("%3d objects   one batched call %7.3f (%.3f - %.3f)   loop of %d single calls %7.3f (%.3f - %.3f)   ratio %.1fx"
                      % ((n,) + b + (n,) + s + (s[0] / b[0],)))
+    lines += ["", "ellipsoid plane fit, qsp_ellipsoid_fit_planes: 12 noisy tangent planes per ellipsoid, 10 iterations, the same clock"]
+    rng = np.random.default_rng(0)
+    ells = np.concatenate([rng.normal(size=(64, 3)) + [0, 0, 3], np.tile([0.0, 0.0, 0.0, 1.0], (64, 1)), rng.uniform(0.2, 1.2, (64, 3))], axis=1)
+    planes = []
+    for e in ells:                                               # tangent planes of the axis-aligned ellipsoid, offsets jittered
+        nrm = rng.normal(size=(12, 3))
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        planes.append(np.concatenate([nrm, (-nrm @ e[:3] - np.linalg.norm(nrm * e[7:], axis=1) + rng.normal(scale=0.01, size=12))[:, None]], axis=1))
+    for n in (1, 16, 64):
+        lines.append("%3d ellipsoids   one batched call %7.3f (%.3f - %.3f)" % ((n,) + timed(lambda: optimize_ellipsoids_using_planes(ells[:n], planes[:n]), reps)))
     txt = "\n".join(lines) + "\n"
     print(txt, end="")
-    out = os.path.join(ROOT, "profiles", "object_gate.txt")
     with open(out, "w") as f:
         f.write(txt)
 
