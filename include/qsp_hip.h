@@ -402,6 +402,9 @@ typedef struct {
                                 the second stage's first system) ran on the device behind the first stage's last trial ...  */
     int32_t boundary_host;   /* ... and those that took the host path: the last trial was rejected, a key-frame or object
                                 vertex lost its last active edge (the reduced system changes shape), or several ranks       */
+    int32_t schur_form;      /* how the last Levenberg-Marquardt trial of the last solve built the reduced camera system: 0 key-frame
+                                pair lists (no atomics), 1 per landmark (FP64 atomics), 2 block rows (LDS atomics), -1 none was
+                                built (no trial ran, or no free key-frame).  Filled with profiling on or off                 */
 } qsp_ba_stats;
 
 typedef struct qsp_ba_problem qsp_ba_problem;

@@ -104,6 +104,14 @@ class BaProblem(object):
         _lib.check(L.qsp_ba_profile(self.handle, 1 if getattr(self, "_profiling", False) else 0, C.byref(prof)))
         return bool(prof.cholesky_chain)
 
+    @property
+    def schur_form(self):
+        """how the last trial of the last solve built the reduced camera system: 0 key-frame pair lists, 1 per landmark (FP64
+        atomics), 2 block rows (LDS atomics), -1 none was built (qsp_ba_stats.schur_form)"""
+        prof = _lib.BaProfile()
+        _lib.check(_lib.lib().qsp_ba_profile(self.handle, 1 if getattr(self, "_profiling", False) else 0, C.byref(prof)))
+        return int(prof.schur_form)
+
     def set_deterministic(self, on=True):
         """no atomics in the Schur complement: repeated runs give the same bits (qsp_ba_set_deterministic)"""
         _lib.check(_lib.lib().qsp_ba_set_deterministic(self.handle, 1 if on else 0))

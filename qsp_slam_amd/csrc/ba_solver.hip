@@ -2843,6 +2843,7 @@ struct qsp_ba_problem {
     int chol_grid_max = 1;                 // tile workgroups launched at most: one per compute unit beside the chain's
     int chain_timeouts = 0;                // solves in which a flag wait expired: repeated on the one-launch-per-step form
     int n_boundary_device = 0, n_boundary_host = 0;      // local joint BAs by the path their stage boundary took (qsp_ba_stats)
+    int schur_form = -1;                   // how the last trial built the reduced system (qsp_ba_stats.schur_form)
     double* scal_host = nullptr; // pinned, device-visible copy of scal[0..3] (k_publish_scal): read back without a copy engine hop
     double* scal_host_dev = nullptr;
     double scal_seq = 0.0;       // sequence number of the last read-back enqueued
@@ -3709,6 +3710,7 @@ static int ba_optimize(qsp_ba_problem* p, int32_t n_iter, double delta_mono, dou
         (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
         (void)hipEventRecord(ev0, s);
     }
+    p->schur_form = -1;
     const int gp = std::max(1, std::min(p->n_partial, (d.n_pt + 255) / 256));
     d.bs = d.Hs + (size_t)p->dimp * p->dimp;      // right behind the reduced matrix: one all-reduce covers both
     double lambda = 0, ni = 2, currentChi = 0;
@@ -3812,10 +3814,12 @@ static int ba_optimize(qsp_ba_problem* p, int32_t n_iter, double delta_mono, dou
                 if (d.n_pt) QSP_HIP(hipMemcpyAsync(d.pt_bk, d.pt_xyz, sizeof(double) * 3 * d.n_pt, hipMemcpyDeviceToDevice, s));
             }
             // solve
+            p->schur_form = -1;
             if (p->dimp > 0) {
                 const int nprep = p->n_dense * 36 + d.n_oe * 36 + (p->dimp - p->dim);
                 const size_t row_lds = sizeof(double) * ((size_t)6 * p->dimp + 6);
                 if (fused) {
+                    p->schur_form = 0;
                     // atomic-free path, two launches: everything that is independent, then one workgroup per key-frame pair
                     Stage1 g;
                     g.nb_hs = (int)(((size_t)p->dimp * p->dimp + p->dimp + 255) / 256);
@@ -3835,8 +3839,10 @@ static int ba_optimize(qsp_ba_problem* p, int32_t n_iter, double delta_mono, dou
                     if (d.n_pt && row_lds <= SCHUR_ROW_LDS_MAX && d.n_ksplit && d.n_edge >= SCHUR_ROWS_MIN_EDGES) {
                         hipLaunchKernelGGL(k_schur_dinv, dim3((d.n_pt + 255) / 256), dim3(256), 0, s, d, par);
                         hipLaunchKernelGGL(k_schur_rows, dim3(d.n_ksplit), dim3(256), row_lds, s, d, par);
-                    } else if (d.n_pt) {
-                        hipLaunchKernelGGL(k_schur_points, dim3((d.n_pt + 3) / 4), dim3(256), 0, s, d, par);
+                        p->schur_form = 2;
+                    } else {
+                        if (d.n_pt) hipLaunchKernelGGL(k_schur_points, dim3((d.n_pt + 3) / 4), dim3(256), 0, s, d, par);
+                        p->schur_form = 1;
                     }
                     if (p->elim) {
                         hipLaunchKernelGGL(k_obj_prepare, dim3(d.n_obj), dim3(64), 0, s, d, par);
@@ -4075,6 +4081,7 @@ extern "C" int qsp_ba_profile(qsp_ba_problem* p, int enable, qsp_ba_stats* out) 
     p->prof.chain_timeouts = p->chain_timeouts;
     p->prof.boundary_device = p->n_boundary_device;
     p->prof.boundary_host = p->n_boundary_host;
+    p->prof.schur_form = p->schur_form;
     if (out) *out = p->prof;
     return QSP_OK;
 }

@@ -313,16 +313,22 @@ def test_library_rccl_communicator_world_of_one():
     c.close()
 
 
-def test_block_row_schur_path_on_a_large_graph():
-    """>= 65536 edges switches the Schur complement to k_schur_rows (LDS row blocks per key-frame split); same bars as
-    the small scenes, against the C oracle on the same graph (12 key-frames, 10 000 landmarks x 8 observations, 2 objects)."""
+@pytest.mark.parametrize("mode", ["deterministic", "atomic"])
+def test_block_row_schur_path_on_a_large_graph(mode):
+    """80 000 edges (12 key-frames, 10 000 landmarks x 8 observations, 2 objects), against the C oracle on the same graph with the
+    bars of the small scenes.  The graph holds 360 000 pair entries, far under the cap, so its default mode is the pair lists
+    (`deterministic`: k_schur_pairs, form 0); only in the atomic mode do >= 65536 edges switch the Schur complement to
+    k_schur_rows (LDS row blocks per key-frame split, form 2).  qsp_ba_stats.schur_form is the witness of which one ran."""
     from qsp_slam_amd.ba import BaProblem
     sc = synth.make_ba_scene_large(11, 12, 10000, obs_per_pt=8, n_obj=2)
     assert len(sc["mono_pt"]) >= 65536
     ref = bo.BaProblem(sc)
     tr = ref.optimize(4, DM, DS, DO)
     gpu = BaProblem(sc)
+    if mode == "atomic":
+        gpu.set_deterministic(False)
     tg = gpu.optimize(4, DM, DS, DO)
+    assert gpu.schur_form == (0 if mode == "deterministic" else 2)
     assert np.array_equal(tg["kf_hidx"], tr["kf_hidx"]) and np.array_equal(tg["pt_hidx"], tr["pt_hidx"])
     assert list(tg["trials"]) == list(tr["trials"]) and list(tg["accepted"]) == list(tr["accepted"])
     assert close(tg["chi2"], tr["chi2"]) and close(tg["lam"], tr["lam"])
