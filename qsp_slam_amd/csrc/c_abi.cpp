@@ -1,12 +1,16 @@
-// c_abi.cpp -- library-wide C-ABI entry points (version, error text, device count), the buffer cache, and the one-shot batch calls
-// that need nothing from the bundle-adjustment solver: the object map-point gate, Sim3 RANSAC, SearchBySim3 and SearchByBoW.
+// c_abi.cpp -- library-wide C-ABI entry points (version, error text, device count), the buffer cache, and the one-shot batch calls:
+// the object map-point gate, Sim3 RANSAC, SearchBySim3, SearchByBoW, the ellipsoid fits, OptimizeSim3 and the essential graph.  The
+// last launches the dense factorisation that ba_solver.hip defines, through dense_chol.hpp; nothing else here is the solver's.
 #include <hip/hip_runtime.h>
 
 #include "buf_cache.hpp"
 #include "common.hpp"
+#include "ellipsoid_fit.hpp"
+#include "essential_graph.hpp"
 #include "object_gate.hpp"
 #include "search_bow.hpp"
 #include "search_sim3.hpp"
+#include "sim3_opt.hpp"
 #include "sim3_ransac.hpp"
 
 namespace qsp {

@@ -5,7 +5,7 @@
 // EdgeEllipsoidPlane per plane whose 1-D error is the distance from the plane to the nearest tangent point of the
 // ellipsoid (src/pca/EllipsoidExtractorEdges.cpp:35-175), information 1, no robust kernel, g2o's NUMERIC Jacobian
 // (Thirdparty/g2o/g2o/core/base_unary_edge.hpp:82-123: central differences, delta 1e-9), BlockSolverX + dense LDLT,
-// OptimizationAlgorithmLevenberg, optimize(10).  Included at the end of ba_solver.hip.
+// OptimizationAlgorithmLevenberg, optimize(10).  Compiled in c_abi.cpp.
 //
 // The quadric BA these problems once fed is dead code in the reference, and in this revision the function itself
 // is compiled but has no live caller (its call sites, src/pca/EllipsoidExtractorMultiPlanes.cpp:692-693, are commented out).
@@ -21,6 +21,7 @@
 #include <float.h>
 
 #include "staging.hpp"
+#include "wave.hpp"
 
 namespace qsp {
 namespace ell {
@@ -31,12 +32,6 @@ struct FitIn {
     const int32_t* off;       // [n+1]
     const double* planes;     // [off[n]][4]
 };
-
-__device__ inline double wave_sum(double a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    return a;
-}
 
 // EdgeEllipsoidPlane::computeError (direction == 0) / EdgeSE3EllipsoidPlane::computeError with an identity camera
 // (direction != 0: GetDistanceWithDirection + the NaN check, EllipsoidExtractorEdges.cpp:151-226)

@@ -1,5 +1,5 @@
 // essential_graph.hpp -- Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from
-// optimizer.initializeOptimization() to the corrected map points.  Included at the end of ba_solver.hip (the dense factorisation is the solver's).
+// optimizer.initializeOptimization() to the corrected map points.  Compiled in c_abi.cpp; the dense factorisation is dense_chol.hpp's.
 //
 // The problem: n_kf VertexSim3Expmap in hessian order (ascending key-frame id; state tx ty tz qx qy qz qw s), a fixed flag per
 // vertex, n_edge EdgeSim3 in insertion order with error log(Z S_v0 S_v1^-1) (Thirdparty/g2o/g2o/types/types_seven_dof_expmap.h
@@ -32,7 +32,14 @@
 // restates operation for operation.  Sim3::log's W.lu().solve(t) is restated as Eigen's 3x3 partial-pivot LU with its unrolled
 // triangular solves (lu3_solve).
 #pragma once
+#include <algorithm>
+#include <mutex>
+
+#include "dense_chol.hpp"
+#include "se3.hpp"
+#include "sim3_opt.hpp"
 #include "staging.hpp"
+#include "wave.hpp"
 
 namespace qsp {
 namespace eg {
@@ -282,7 +289,7 @@ __global__ __launch_bounds__(64) void k_eg_reduce(Graph g, const double* __restr
     const int lane = threadIdx.x;
     double c = 0;
     for (int k = lane; k < g.n_edge; k += 64) c = c + g.chi[k];
-    c = sim3::wave_sum(c);
+    c = wave_sum(c);
     if (lane == 0) scal[0] = c;
     if (x) {
         double a = 0;
@@ -292,7 +299,7 @@ __global__ __launch_bounds__(64) void k_eg_reduce(Graph g, const double* __restr
             const int j = fi * g.D + q;
             a = a + x[j] * (lambda * x[j] + bvec[j]);
         }
-        a = sim3::wave_sum(a);
+        a = wave_sum(a);
         if (lane == 0) scal[1] = a;
     }
     if (H) {

@@ -1,5 +1,5 @@
 // sim3_opt.hpp -- Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1050-1245) for ALL loop candidates of a key frame in one
-// launch.  Included at the end of ba_solver.hip (ba::skew3 is the solver's).
+// launch.  Compiled in c_abi.cpp.
 //
 // The reference's caller (LoopClosing::ComputeSim3, src/LoopClosing.cc) walks its candidate key frames one after another and
 // builds, solves and tears down one g2o graph each: one free VertexSim3Expmap (7 unknowns: rotation, translation, log scale),
@@ -22,7 +22,9 @@
 #pragma once
 #include <float.h>
 
+#include "se3.hpp"
 #include "staging.hpp"
+#include "wave.hpp"
 
 namespace qsp {
 namespace sim3 {
@@ -40,12 +42,6 @@ struct Out {                                       // per candidate
     int32_t iters[2];
     int32_t n_inliers, pad;
 };
-
-__device__ inline double wave_sum(double a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    return a;
-}
 
 // Eigen's quaternion * vector and quaternion * quaternion; q = x y z w, not normalised anywhere (g2o::Sim3 does not either)
 __device__ inline void rot(const double* q, const double* v, double* o) {

@@ -1,6 +1,6 @@
-"""The block-row regimes of the dense solve of the bundle adjustment's reduced system (csrc/ba_solver.hip: k_chol_first / k_chol_step,
-k_chol_solve, k_chol_back), one scene per regime, each the smallest that reaches it.  Shared by tests/test_oracle_ba_blocks.py (the
-C oracle on the CPU: is every scene what the table says, and how sharp is the reference there?) and tests/test_gpu_ba_blocks.py
+"""The block-row regimes of the dense solve of the bundle adjustment's reduced system (csrc/dense_chol.hpp: k_chol_first / k_chol_step,
+k_chol_solve; csrc/ba_solver.hip: k_chol_back), one scene per regime, each the smallest that reaches it.  Shared by
+tests/test_oracle_ba_blocks.py (the C oracle on the CPU: is every scene what the table says, and how sharp is the reference there?) and tests/test_gpu_ba_blocks.py
 (the device solve against that oracle).  Nothing here touches a GPU.
 
 The solver works on 64-wide block rows, nb = dimp / 64, dimp = the dense dimension padded to a multiple of 64.  The dense dimension

@@ -1,9 +1,13 @@
-r"""Compare the kernels of two gfx950 assembly listings of csrc/sdf_refine.hip, kernel by kernel.
+r"""Compare the kernels of two sets of gfx950 assembly listings, kernel by kernel.
 
-Make each listing with tools/check_mfma_hazards.compile_isa (the command tests/conftest.py uses), in the two trees to compare:
-    python -c "import sys; sys.path.insert(0, 'tools'); import check_mfma_hazards as c; c.compile_isa('/tmp/a.s')"
-then  python tools/isa_kernel_diff.py /tmp/a.s /tmp/b.s  [-v NAME] [--alias REGEX=REPL ...]
-Every function body is cut out by its mangled symbol (label to .Lfunc_end, its .size or the next function) and paired by its
+Make a device-only listing of any translation unit of csrc/ with csrc/build.sh's flags plus -S --cuda-device-only, in the two
+trees to compare:
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -S --cuda-device-only -o /tmp/a_ba.s ba_solver.hip
+(for sdf_refine.hip, tools/check_mfma_hazards.compile_isa is that command, the one tests/conftest.py uses)
+then  python tools/isa_kernel_diff.py A1.s[,A2.s ...] B1.s[,B2.s ...]  [-v NAME] [--alias REGEX=REPL ...]
+Each side is one listing or several joined by commas -- code that moved from one translation unit to another is then compared
+where it is now.  A function that two listings of a side hold with the same body (an inline helper both units emit) is one
+function; different bodies under one name are an error.  Every function body is cut out by its mangled symbol (label to .Lfunc_end, its .size or the next function) and paired by its
 demangled name; assembler comments, the numbers of local labels, section directives and the function's own symbol are dropped
 (source positions, counters over the function or the file, and where the code is placed: not code).  Prints the kernels that are
 identical, differ, are missing, and are new; -v NAME shows the first lines of the difference of a kernel whose demangled name
@@ -38,16 +42,21 @@ def bodies(path):
     return out
 
 
-def named(path, alias=()):
-    """bodies() keyed by demangled name without the argument list, the aliases applied in the order given"""
-    raw, out = bodies(path), {}
-    dm = subprocess.run(["c++filt"], input="\n".join(raw), capture_output=True, text=True).stdout.split("\n")
-    for sym, name in zip(raw, dm):
-        name = name.replace("void ", "", 1).split("(")[0]
-        for pat, repl in alias:
-            name = re.sub(pat, repl, name)
-        assert name not in out, "two functions named " + name
-        out[name] = raw[sym]
+def named(paths, alias=()):
+    """bodies() of the comma-separated listings keyed by demangled name without the argument list, the aliases applied in the
+    order given"""
+    out = {}
+    for path in paths.split(","):
+        raw = bodies(path)
+        dm = subprocess.run(["c++filt"], input="\n".join(raw), capture_output=True, text=True).stdout.split("\n")
+        seen = set()
+        for sym, name in zip(raw, dm):
+            name = name.replace("void ", "", 1).split("(")[0]
+            for pat, repl in alias:
+                name = re.sub(pat, repl, name)
+            assert name not in seen and out.get(name, raw[sym]) == raw[sym], "two functions named " + name
+            seen.add(name)
+            out[name] = raw[sym]
     return out
 
 

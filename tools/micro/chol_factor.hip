@@ -1,4 +1,4 @@
-// Micro-benchmark of the 64x64 diagonal-block factorisation of the BA's blocked Cholesky (csrc/ba_solver.hip:factor_tile64): the
+// Micro-benchmark of the 64x64 diagonal-block factorisation of the BA's blocked Cholesky (csrc/dense_chol_kernels.hpp:factor_tile64): the
 // serial chain of every block step.  One workgroup of 256 threads factorises a 64x64 SPD matrix held as 4x4 register tiles and
 // produces W = L^-1; wave 3's last thread stamps the shader clock at the phase boundaries of every 4-row round.
 //   hipcc --offload-arch=gfx950 -O3 -o chol_factor tools/micro/chol_factor.hip && ./chol_factor [variant]

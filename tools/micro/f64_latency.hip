@@ -1,5 +1,5 @@
 // Dependent-issue latency of the FP64 instructions on the serial chain of the BA's diagonal-block factorisation
-// (csrc/ba_solver.hip:factor_tile64): one wave, N dependent instructions of a kind, shader-clock stamps around them.
+// (csrc/dense_chol_kernels.hpp:factor_tile64): one wave, N dependent instructions of a kind, shader-clock stamps around them.
 //   hipcc --offload-arch=gfx950 -O3 -o f64_latency tools/micro/f64_latency.hip && ./f64_latency
 #include <hip/hip_runtime.h>
 #include <cstdio>
