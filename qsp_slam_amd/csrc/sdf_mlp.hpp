@@ -66,6 +66,9 @@ constexpr int KG4 = K4 / 8;           // into the per-hypothesis bias c4 (mlp_pr
 constexpr int K0_PAD = 96;      // layer-0 K (67) padded to a multiple of 8*PF
 constexpr int LDA = HID + 4;    // activation row stride (floats)
 constexpr int LDST = 68;        // stash row stride
+constexpr int STASH_SHIFT = 1;  // split-fp16 tile: skip-gradient input ci at word ci + 1 of its stash row, so that the unit quads of
+                                // layer 4's backward write-out (unit 445 + ci, quads at multiples of 4) are aligned 16-byte stores
+static_assert((SKIP_COL - STASH_SHIFT) % 4 == 0 && STASH_SHIFT + NIN <= LDST, "stash row: aligned quads of units 444.., 67 inputs");
 constexpr int LDJ = 96;         // augmented-Jacobian row stride (72 used)
 constexpr int NJ = 72;          // 7 pose + 64 code + 1 residual column
 constexpr int MLP_THREADS = 512;
@@ -84,7 +87,8 @@ struct MlpParams {
     const float4* wb3[8];   // split-bf16 backward weights of layers 0..7 (column blocks over the layer's inputs, slabs over outputs)
     const float4* wfh[8];   // split-fp16 forward weights: [col block 16][slab K/16][plane hi|lo'][lane 64][8 fp16]; layer 0: its xyz columns, one slab
     const float4* wbh[8];   // split-fp16 backward weights of layers 0..7 (column blocks over the layer's inputs, slabs over outputs)
-    const float4* wbh4s;    // split-fp16 backward weights of layer 4's skip columns (inputs 445..511 = [code | xyz]), packed like wbh[0]
+    const float4* wbh4s;    // split-fp16 backward weights of layer 4's skip columns (inputs 445..511 = [code | xyz]), packed like wbh[0]:
+                            // read by the NARROW tile only (the full-width tile takes these columns from wbh[4] itself)
     int* range_flag;        // set by the split-fp16 kernels when a value they had to split was outside fp16's range
     int use_tanh;           // NetworkSpecs.use_tanh: tanh on the output layer in front of the final tanh (deep_sdf_decoder.py:92-94)
     // Narrow decoders (a member of the family embedded into the 8 x 512 shape, e.g. 4 x 256 / code 32): what the NARROW form of the
@@ -1616,6 +1620,8 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
 #define QSP_BWDH(L, KS_, NWB)                                                                                            \
   if (!(NARROW && P.skip[L])) {        /* (an identity slot passes the gradient on: its mask is applied by the layer below) */ \
     const bool act_ = !NARROW || cb0 < (int)P.ncb_in[L];                                                                  \
+    const int cu0_ = 32 * NCB * wave;                                                                                    \
+    (void)cu0_;                                                                                                          \
     _Pragma("unroll") for (int r_ = 0; r_ < NR; ++r_) _Pragma("unroll") for (int c_ = 0; c_ < NCB; ++c_)                 \
         _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) { acc[r_][c_][i_] = 0.f; acc2[r_][c_][i_] = 0.f; }             \
     if constexpr (NARROW)                                                                                                \
@@ -1631,12 +1637,19 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
         const int u0_ = 32 * NCB * wave + 32 * c_ + 8 * g_ + 4 * h;                                                      \
         _Pragma("unroll") for (int r_ = 0; r_ < NR; ++r_) {                                                              \
             const int p_ = 32 * r_ + (lane & 31);                                                                      \
-            f32x4 v_;                                                                                                    \
+            f32x4 v_, raw_;                                                                                              \
             _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                                           \
                 float x_ = fmaf(acc2[r_][c_][4 * g_ + q_], 0.00048828125f, acc[r_][c_][4 * g_ + q_]);                   \
                 if ((L) == 7) x_ *= dyr_[r_];                                                                            \
+                raw_[q_] = x_;                                                                                           \
                 const float m_ = h2_mask_sel(x_, mk[(L) - 1][r_][c_ >> 1], (c_ & 1) * 16 + 4 * g_ + q_);                       \
                 v_[q_] = m_;                                                                                             \
+            }                                                                                                            \
+            /* layer 4's columns 445..511 are the skip connection's gradient d y / d [code | xyz]: the quad goes to the */ \
+            /* stash unmasked (STASH_SHIFT: column 444, a hidden unit, lands in the row's padding word); the image gets */ \
+            /* the zeros of mk[3] there like any dead unit (layer 3's backward contracts over 445..447)                 */ \
+            if (!NARROW && (L) == 4 && cu0_ + 32 * c_ + 32 > SKIP_COL) {          /* (uniform: this column block) */       \
+                if (u0_ + 3 >= SKIP_COL) *reinterpret_cast<f32x4*>(s.stash + p_ * LDST + (u0_ - (SKIP_COL - STASH_SHIFT))) = raw_; \
             }                                                                                                            \
             h2_store4(img, p_, u0_, v_, amax);                                                                           \
         }                                                                                                                \
@@ -1648,8 +1661,11 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
         QSP_BWDH(7, KSH, QSP_WBH(6))
         QSP_BWDH(6, KSH, QSP_WBH(5))
         QSP_BWDH(5, KSH, QSP_WBH(4))
-        {   // the skip connection's gradient d y / d [code | xyz] = g_a4 . W4[:, 445:512]: its own 64 x 96 product, to the stash
-            // in f32 (layer 4's write-out below masks those columns to zero like any dead unit: mk[3] has no bit set there)
+        // The skip connection's gradient d y / d [code | xyz] = g_a4 . W4[:, 445:512] is columns 445..511 of layer 4's own
+        // backward product: the full-width form takes it from that write-out (QSP_BWDH above), to the stash in f32, input ci
+        // at word ci + STASH_SHIFT of the point's row.  The narrow form keeps it as a product of its own (64 x 96,
+        // gemm_side_h2 over wbh4s): its layer 4 may be an identity slot or stop short of those column blocks.
+        if constexpr (NARROW) {
             f32x4 sk[NR][4];
             gemm_side_h2<PF, NR, NW, NARROW>(img, P.wbh4s, wave, lane, sk, NARROW ? (int)P.ks_out[4] : KSH);
             const int c0 = side_c0<NR, NW>(wave);
@@ -1660,7 +1676,9 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int k0 = 32 * c0 + 8 * g + 4 * h;
-                    if (k0 < NIN) *reinterpret_cast<f32x4*>(s.stash + p * LDST + k0) = sk[r][g];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (k0 + q < NIN) s.stash[p * LDST + STASH_SHIFT + k0 + q] = sk[r][g][q];
                 }
             }
         }
@@ -1695,10 +1713,12 @@ __device__ __forceinline__ void mlp_tile_h2(MlpSmem& s, const MlpParams* __restr
                 for (int g = 0; g < 4; ++g) {
                     const int k0 = 32 * c0 + 8 * g + 4 * h;
                     if (k0 < NIN) {     // 64..67 is the last useful quad (67 itself is padding inside both row strides)
-                        const f32x4 st = lds4(s.stash + p * LDST + k0);
+                        // (the stash row is shifted by STASH_SHIFT: four scalar reads; input 67 of the last quad is padding in
+                        // both row strides and the word behind the last row belongs to the next array: not read)
+                        const float* st = s.stash + p * LDST + STASH_SHIFT + k0;
                         f32x4 v;
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = gl[r][g][q] + st[q];
+                        for (int q = 0; q < 4; ++q) v[q] = gl[r][g][q] + (k0 + q < NIN ? st[q] : 0.f);
                         *reinterpret_cast<f32x4*>(s.act + p * LDG + k0) = v;
                     }
                 }
