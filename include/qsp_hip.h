@@ -253,7 +253,11 @@ int qsp_reconstruct_objects(qsp_decoder* dec, const qsp_joint_cfg* cfg, int32_t 
 
 /* Optimizer.estimate_pose_cam_obj, reconstruct/optimizer.py:47-93, batched: per item an SE3 t_co (4,4), a scale, surface
  * points and a code; n_iter SDF-only Gauss-Newton iterations on the 6 pose dimensions (1e-2 damping, raw residual,
- * inlier filter |res| <= 0.05 after iteration index 4).  t_co_out (n,4,4) SE3.  Host pointers. */
+ * inlier filter |res| <= 0.05 after iteration index 4).  t_co_out (n,4,4) SE3.  Host pointers.
+ * An item that has no point to iterate on -- n_pts[i] = 0 (pts[i] is then not read), or every point removed by the inlier filter --
+ * is no error: like the reference, which divides by the point count, the call returns QSP_OK with all 16 entries of that item's
+ * matrix NaN; the other items of the call are not affected (a call whose items all have n_pts[i] = 0 launches nothing).  n <= 0, a null argument, a negative n_pts[i] or a null pts[i] with
+ * n_pts[i] > 0: QSP_ERR_INVALID, t_co_out untouched. */
 int qsp_estimate_pose(qsp_decoder* dec, int32_t n, const float* t_co_se3, const float* scale,
                       const float* const* pts, const int32_t* n_pts, const float* code, int32_t n_iter,
                       float* t_co_out);

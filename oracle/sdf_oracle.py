@@ -405,26 +405,51 @@ def reconstruct_object(dec, cfg, t_cam_obj, pts, rays, depth, code=None, trace=N
     return dict(t_cam_obj=np.linalg.inv(T_oc).astype(F32), code=z, is_good=True, loss=loss)
 
 
-def estimate_pose_cam_obj(dec, cfg, t_co_se3, scale, pts, code, trace=None):
+POSE_ONLY_INLIER = 0.05      # optimizer.py:80-82
+
+
+def pose_only_iteration(dec, T_oc, z, pts, divisor=None, f64=False):
+    """One iteration of estimate_pose_cam_obj from the state T_oc on the points `pts` (optimizer.py:62-78): decoder, Jacobian, H, b,
+    solve and exponential.  Returns dict(T_oc, H, b, dx, n, res, T_oc_new).
+    f64=True: the same iteration evaluated in float64 on the same (float32-valued) weights and inputs -- the yardstick flavour, as
+    gn_iteration_f64 is for the joint iteration.  divisor: what H and b are divided by in place of the number of points (the tests'
+    vacuity guards restate a kernel's possible defects with it)."""
+    if f64:
+        with working_precision(np.float64):
+            d64 = DecoderWeights(dec.layers, dec.latent_in, dec.code_len, getattr(dec, "use_tanh", False))
+            return pose_only_iteration(d64, np.asarray(T_oc, np.float64), np.asarray(z, np.float64), np.asarray(pts, np.float64),
+                                       divisor=divisor)
+    Jp, _, res, _ = sdf_term(dec, pts, T_oc, z)
+    J = Jp[:, :6]
+    n = F32(J.shape[0] if divisor is None else divisor)
+    H = (J.T @ J).astype(F32) / n + F32(1e-2) * np.eye(6, dtype=F32)
+    b = -(J.T @ res).astype(F32) / n
+    dx = (np.linalg.inv(H).astype(F32) @ b).astype(F32)
+    return dict(T_oc=np.array(T_oc, F32), H=H, b=b, dx=dx, n=int(J.shape[0]), res=res, T_oc_new=(exp_se3(dx) @ T_oc).astype(F32))
+
+
+def estimate_pose_cam_obj(dec, cfg, t_co_se3, scale, pts, code, trace=None, trace_f64=False):
     """Optimizer.estimate_pose_cam_obj, optimizer.py:47-93: SDF-only GN on the 6 pose dims, 1e-2 damping, raw
-    residual in b, inlier filter |res|<=0.05 after iteration index 4.  Returns (4,4) f32 SE3."""
+    residual in b, inlier filter |res|<=0.05 after iteration index 4.  Returns (4,4) f32 SE3.
+    trace: a list that receives one record per iteration, pose_only_iteration's dict; the record of iteration index 4 also holds
+    `kept`, the mask |res| <= 0.05 over the points of that iteration.  trace_f64: every record also holds `f64`, the same iteration
+    evaluated in float64 from the record's own float32 state and points (the result itself stays the float32 one)."""
     T_co = np.asarray(t_co_se3, F32).copy()
     T_co[:3, :3] *= F32(scale)
     T_oc = np.linalg.inv(T_co).astype(F32)
     z = np.asarray(code, F32)[: cfg.code_len]
     pts = np.asarray(pts, F32)
     for e in range(cfg.n_iter_pose):
-        Jp, _, res, _ = sdf_term(dec, pts, T_oc, z)
-        J = Jp[:, :6]
-        n = F32(J.shape[0])
-        H = (J.T @ J).astype(F32) / n + F32(1e-2) * np.eye(6, dtype=F32)
-        b = -(J.T @ res).astype(F32) / n
-        dx = (np.linalg.inv(H).astype(F32) @ b).astype(F32)
-        if trace is not None:
-            trace.append(dict(T_oc=T_oc.copy(), H=H, b=b, dx=dx, n=int(J.shape[0])))
-        T_oc = (exp_se3(dx) @ T_oc).astype(F32)
+        it = pose_only_iteration(dec, T_oc, z, pts)
         if e == 4:
-            pts = pts[np.abs(res) <= 0.05]
+            it["kept"] = np.abs(it["res"]) <= POSE_ONLY_INLIER
+        if trace is not None:
+            if trace_f64:
+                it["f64"] = pose_only_iteration(dec, T_oc, z, pts, f64=True)
+            trace.append(it)
+        T_oc = it["T_oc_new"]
+        if e == 4:
+            pts = pts[it["kept"]]
     T_co = np.linalg.inv(T_oc).astype(F32)
     T_co[:3, :3] /= F32(scale)
     return T_co

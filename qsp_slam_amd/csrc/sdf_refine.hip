@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <limits>
 #include <string>
 #include <mutex>
 #include <vector>
@@ -1441,7 +1442,7 @@ static int run_once(qsp_refine_batch* b, int32_t n_iter, bool* hit, bool* screen
         hipLaunchKernelGGL(k_solve, dim3(nH), dim3(SOLVE_THREADS), 0, s, b->st, b->objs, cfg, b->partials, b->nw_sdf, nw_total,
                            b->pt_active, b->act_stride, b->trH, b->trb, b->trdx, b->counters, b->trrot);
         pm.end(2);
-        if (cfg.pose_only && it == 4)   // optimizer.py:80-82
+        if (cfg.pose_only && it == 4 && b->max_pts > 0)   // optimizer.py:80-82
             hipLaunchKernelGGL(k_inlier_filter, dim3((b->max_pts + 255) / 256, nH), dim3(256), 0, s, b->st, b->objs,
                                b->res_buf, b->act_stride, b->pt_active);
     }
@@ -1751,6 +1752,12 @@ static int estimate_pose(qsp_decoder* dec, qsp_decoder_group* grp, const int32_t
                          float* t_co_out) {
     if (!dec || n <= 0 || !t_co_se3 || !scale || !pts || !n_pts || !code || !t_co_out)
         return qsp_fail(QSP_ERR_INVALID, "qsp_estimate_pose: bad argument");
+    for (int i = 0; i < n; ++i)
+        if (n_pts[i] < 0 || (n_pts[i] > 0 && !pts[i])) return qsp_fail(QSP_ERR_INVALID, "qsp_estimate_pose: bad points of an item");
+    if (std::all_of(n_pts, n_pts + n, [](int32_t m) { return m == 0; })) {      // no item has a point: nothing to launch (see below)
+        std::fill(t_co_out, t_co_out + (size_t)n * 16, std::numeric_limits<float>::quiet_NaN());
+        return QSP_OK;
+    }
     if (n_iter <= 0) n_iter = 5;
     RefineCfg c{};
     c.n_depth = 2;
@@ -1771,12 +1778,17 @@ static int estimate_pose(qsp_decoder* dec, qsp_decoder_group* grp, const int32_t
     rc = qsp_refine_batch_set_state(b, T.data(), code);
     if (!rc) rc = qsp_refine_batch_run(b, n_iter);
     std::vector<float> To((size_t)n * 16);
-    if (!rc) rc = qsp_refine_batch_get(b, To.data(), nullptr, nullptr, nullptr);
+    std::vector<uint8_t> good(n);
+    if (!rc) rc = qsp_refine_batch_get(b, To.data(), nullptr, nullptr, good.data());
     if (!rc)
         for (int i = 0; i < n; ++i) {
             memcpy(t_co_out + 16 * i, &To[16 * i], 16 * sizeof(float));
             for (int r = 0; r < 3; ++r)
                 for (int q = 0; q < 3; ++q) t_co_out[16 * i + 4 * r + q] /= scale[i];   // optimizer.py:88
+            // An item without a point left (none given, or all removed by the inlier filter): the reference divides H and b by
+            // zero and hands back a matrix of NaNs.  k_solve stops such a hypothesis at the pose it had; that pose is not a result.
+            if (!good[i])
+                for (int e = 0; e < 16; ++e) t_co_out[16 * i + e] = std::numeric_limits<float>::quiet_NaN();
         }
     qsp_refine_batch_destroy(b);
     return rc;

@@ -244,22 +244,16 @@ def test_jacobian_rows_of_fused_kernel_vs_reference(gpu_decoder, golden_dir, nam
 def test_pose_only_more_iterations_exercises_the_inlier_filter(gpu_decoder, oracle_decoder):
     """With 5 iterations the |res| <= 0.05 filter after iteration index 4 (optimizer.py:80-82) never influences the
     result; with 8 it does (iterations 5..7 run on the filtered set and a smaller N).  Outliers are planted."""
-    from qsp_slam_amd import synth
     from qsp_slam_amd.reconstruct.optimizer import Optimizer
-    o = synth.make_object_views(77, 1, 300, n_fg=8, n_bg=4)[0]
-    T = o["t_cam_obj"].astype(np.float64)
-    s = np.linalg.det(T[:3, :3]) ** (1 / 3)
-    T_se3 = T.copy()
-    T_se3[:3, :3] /= s
-    pts = o["pts"].copy()
-    pts[::7] += np.float32(0.25)                      # gross outliers: SDF residual > 0.05
+    from tests import pose_only_cases as pc
+    c = pc.case("filter_m300")                        # 300 points, every 7th a gross outlier (SDF residual > 0.05), a non-zero code
     cfg = so.JointConfig(n_iter_pose=8)
-    ref = so.estimate_pose_cam_obj(oracle_decoder, cfg, T_se3.astype(np.float32), float(s), pts, np.zeros(64, np.float32))
+    ref = so.estimate_pose_cam_obj(oracle_decoder, cfg, c["t_co_se3"], c["scale"], c["pts"], c["code"])
+    assert np.array_equal(ref, pc.oracle_pose("filter_m300", 8))
     opt = Optimizer(gpu_decoder, make_cfg(cfg))
-    out = opt.estimate_pose_cam_obj(T_se3.astype(np.float32), float(s), pts, np.zeros(64, np.float32))
+    out = opt.estimate_pose_cam_obj(c["t_co_se3"], c["scale"], c["pts"], c["code"])
     assert within("pose_only_8_iterations_vs_oracle/t_co", relerr(out, ref), 2e-4)
-    ref5 = so.estimate_pose_cam_obj(oracle_decoder, so.JointConfig(n_iter_pose=5), T_se3.astype(np.float32), float(s), pts,
-                                    np.zeros(64, np.float32))
+    ref5 = so.estimate_pose_cam_obj(oracle_decoder, so.JointConfig(n_iter_pose=5), c["t_co_se3"], c["scale"], c["pts"], c["code"])
     assert relerr(ref, ref5) > 1e-3                   # the filter really changed the trajectory
 
 
