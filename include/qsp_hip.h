@@ -970,6 +970,58 @@ typedef struct {
 } qsp_search_bow_out;
 int qsp_search_by_bow_batch(int device, const qsp_search_bow_in* in, qsp_search_bow_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:657-823, CheckDistEpipolarLine :140-157) for every covisible neighbour of
+ * LocalMapping::CreateNewMapPoints in ONE call.  Key frame 1 (the current one, the SOURCE) is given once, key frame 2 (the
+ * target) per neighbour.  One wave per (neighbour, position in key frame 1's feature list), then one workgroup per neighbour for
+ * the orientation check: two launches.
+ * A frame is a qsp_bow_frame -- descriptors, mvKeysUn[i].angle, the FeatureVector in CSR form with the reference's list order, and
+ * eligible[i] = (GetMapPoint(i) == NULL): the reference tests for null only here, not isBad() (NULL = every slot) -- and beside it
+ * mvKeysUn[i].pt, the stereo flag mvuRight[i] >= 0 and, read of the targets only, mvLevelSigma2 and mvScaleFactors gathered
+ * through the key point's octave.  Per neighbour: F12 (the caller's ComputeF12) and the epipole of key frame 1 in its image.
+ * Per node id both frames hold, for every source of the node that is eligible (and stereo, with only_stereo): bestDist = th,
+ * bestIdx2 = -1; the node's targets are walked in list order; a target that is not eligible (or not stereo, with only_stereo) is
+ * skipped; dist = Hamming distance over the 256 bits; skipped when dist > th || dist > bestDist (INCLUSIVE: th itself is
+ * accepted, and an EQUAL distance later in the list replaces the earlier best); when neither side is stereo, skipped when
+ * (ex - x2)^2 + (ey - y2)^2 < 100.0f * scale2 in float32; then a = x1 F00 + y1 F10 + F20 (b, c alike), num = a x2 + b y2 + c,
+ * den = a a + b b, all float32 and left to right; den == 0 refuses; dsqr = num * num / den; accepted when
+ * (double)dsqr < 3.84 * (double)sigma2.  A target that fails a geometric test changes nothing, so the result is the passing target
+ * of smallest distance, the LAST in list order among equals.  The reference never sets its vbMatched2: two sources may take the
+ * same target (kept); mfNNratio is not read.  With check_orientation the tail is qsp_search_by_bow_batch's.
+ * Non-finite F12, epipole or key-point values are not refused: the IEEE compares decide as in the reference (a NaN never matches
+ * and never skips).  A neighbour's outputs have the same bits alone, in any batch and at any position.
+ * Host pointers.  n_cand == 0 is QSP_OK and touches nothing.  QSP_ERR_INVALID: null required pointers (arrays of a frame with
+ * n == 0 or no nodes may be NULL, node_off never; sigma2 and scale of kf1 are not read), negative sizes, what qsp_search_by_bow_batch
+ * refuses of a feature vector, th outside [0, 256].  More than 2^31 - 1 slots (or n_cand * kf1->bow.n, or nodes, or n_cand * the
+ * length of kf1's feature list) in one call: QSP_ERR_UNSUPPORTED.  No output is written unless the call returns QSP_OK. */
+typedef struct {
+    qsp_bow_frame bow;            /* desc, angle, eligible = no map point in the slot, the FeatureVector */
+    const float* xy;              /* (n,2) mvKeysUn[i].pt */
+    const uint8_t* stereo;        /* (n) mvuRight[i] >= 0 */
+    const float* sigma2;          /* (n) mvLevelSigma2[mvKeysUn[i].octave]; targets only */
+    const float* scale;           /* (n) mvScaleFactors[mvKeysUn[i].octave]; targets only */
+} qsp_tri_frame;
+typedef struct {
+    int32_t n_cand;
+    const qsp_tri_frame* kf1;     /* one: the source of every neighbour */
+    const qsp_tri_frame* kf2;     /* (n_cand) */
+    const float* F12;             /* (n_cand,9) row-major */
+    const float* exy;             /* (n_cand,2) the epipole ex ey (:664-670) */
+    int32_t th;                   /* TH_LOW: 50 */
+    int32_t only_stereo;          /* bOnlyStereo */
+    int32_t check_orientation;    /* mbCheckOrientation */
+} qsp_search_tri_in;
+typedef struct {
+    int32_t* match;               /* (n_cand,kf1->bow.n) the target's index, else -1 */
+    int32_t* n_matches;           /* (n_cand) */
+    /* the tests' taps, each may be NULL: as in qsp_search_bow_out */
+    int32_t* match_raw;           /* (n_cand,kf1->bow.n) before the rotation cull */
+    int32_t* dist;                /* (n_cand,kf1->bow.n) bestDist of each source matched before the cull, else -1 */
+    int32_t* hist;                /* (n_cand,30) */
+    int32_t* ind;                 /* (n_cand,3) */
+} qsp_search_tri_out;
+int qsp_search_for_triangulation_batch(int device, const qsp_search_tri_in* in, qsp_search_tri_out* out);
+
 #ifdef __cplusplus
 }
 #endif

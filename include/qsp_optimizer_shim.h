@@ -1213,6 +1213,104 @@ public:
         }
         return QSP_OK;
     }
+
+private:
+    struct TriArrays {                   // what a qsp_tri_frame points into
+        BowArrays bow;
+        std::vector<float> xy, sigma2, scale;
+        std::vector<uint8_t> stereo;
+    };
+    // What SearchForTriangulation reads of a key frame: gather_bow's arrays, the slots WITHOUT a map point (:702 / :725 test the
+    // pointer only, not isBad()), mvKeysUn[i].pt, mvuRight[i] >= 0 and the level's sigma2 and scale factor through the octave.
+    template <typename KF, typename MP>
+    static void gather_tri(KF* pKF, const std::vector<MP*>& vpMP, TriArrays& a, qsp_tri_frame& f) {
+        const size_t n = vpMP.size();
+        gather_bow((int)n, pKF->mFeatVec, pKF->mDescriptors, pKF->mvKeysUn, a.bow, f.bow);
+        a.bow.elig.assign(n + 1, 0);
+        a.xy.assign(2 * n + 1, 0.f);
+        a.sigma2.assign(n + 1, 0.f);
+        a.scale.assign(n + 1, 0.f);
+        a.stereo.assign(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            const auto& kp = pKF->mvKeysUn[i];
+            a.bow.elig[i] = vpMP[i] ? 0 : 1;
+            a.xy[2 * i] = kp.pt.x; a.xy[2 * i + 1] = kp.pt.y;
+            a.stereo[i] = pKF->mvuRight[i] >= 0 ? 1 : 0;
+            a.sigma2[i] = pKF->mvLevelSigma2[kp.octave];
+            a.scale[i] = pKF->mvScaleFactors[kp.octave];
+        }
+        f.bow.eligible = a.bow.elig.data();
+        f.xy = a.xy.data(); f.stereo = a.stereo.data(); f.sigma2 = a.sigma2.data(); f.scale = a.scale.data();
+    }
+
+public:
+    // ORBmatcher::SearchForTriangulation(pKF1, vpKF2[c], vF12[c], vvMatchedPairs[c], bOnlyStereo) (src/ORBmatcher.cc:657-823) for
+    // ALL kept neighbours of LocalMapping::CreateNewMapPoints in one library call: vvMatchedPairs[c] as the reference leaves it
+    // ((idx1, idx2) in ascending idx1), vnMatches[c] its return value.  vF12[c]: the caller's ComputeF12(pKF1, vpKF2[c]), CV_32F
+    // 3x3.  checkOri: the ORBmatcher's constructor argument (false in CreateNewMapPoints).  The map-point slots of every key frame
+    // are read ONCE (GetMapPointMatches()), where the reference reads each under GetMapPoint's lock as it visits it.
+    // Returns the qsp status; on error vvMatchedPairs and vnMatches have not been touched.
+    template <typename KF>
+    static int SearchForTriangulationBatch(KF* pKF1, const std::vector<KF*>& vpKF2, const std::vector<cv::Mat>& vF12, const bool bOnlyStereo,
+                                           const bool checkOri, std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs,
+                                           std::vector<int>& vnMatches) {
+        const size_t nc = vpKF2.size();
+        if (vF12.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::SearchForTriangulationBatch: %zu neighbours, but %zu fundamental matrices\n", nc,
+                         vF12.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { vvMatchedPairs.clear(); vnMatches.clear(); return QSP_OK; }
+        TriArrays a1;
+        std::vector<TriArrays> a2(nc);
+        qsp_tri_frame f1;
+        std::vector<qsp_tri_frame> f2(nc);
+        const auto vpMapPoints1 = pKF1->GetMapPointMatches();
+        const size_t N1 = vpMapPoints1.size();
+        gather_tri(pKF1, vpMapPoints1, a1, f1);
+        std::vector<float> F12(9 * nc), exy(2 * nc);
+        const cv::Mat Cw = pKF1->GetCameraCenter();                                  // :664
+        for (size_t c = 0; c < nc; ++c) {
+            KF* pKF2 = vpKF2[c];
+            const auto vpMapPoints2 = pKF2->GetMapPointMatches();
+            gather_tri(pKF2, vpMapPoints2, a2[c], f2[c]);
+            for (int r = 0; r < 3; ++r)
+                for (int q = 0; q < 3; ++q) F12[9 * c + 3 * r + q] = vF12[c].template at<float>(r, q);
+            // the epipole in the second image (:665-670).  C2 = R2w * Cw + t2w as cv::Mat computes it for CV_32F: each row's products
+            // summed in double and rounded once, the translation added in float32
+            const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+            float C2[3];
+            for (int r = 0; r < 3; ++r) {
+                double s = 0.0;
+                for (int q = 0; q < 3; ++q) s += (double)R2w.template at<float>(r, q) * (double)Cw.template at<float>(q);
+                C2[r] = (float)s + t2w.template at<float>(r);
+            }
+            const float invz = 1.0f / C2[2];
+            exy[2 * c] = pKF2->fx * C2[0] * invz + pKF2->cx;
+            exy[2 * c + 1] = pKF2->fy * C2[1] * invz + pKF2->cy;
+        }
+        qsp_search_tri_in in;
+        in.n_cand = (int32_t)nc; in.kf1 = &f1; in.kf2 = f2.data(); in.F12 = F12.data(); in.exy = exy.data();
+        in.th = 50;                                                              // ORBmatcher::TH_LOW
+        in.only_stereo = bOnlyStereo ? 1 : 0; in.check_orientation = checkOri ? 1 : 0;
+        std::vector<int32_t> match(nc * N1 + 1), n_matches(nc);
+        qsp_search_tri_out out;
+        out.match = match.data(); out.n_matches = n_matches.data();
+        out.match_raw = out.dist = out.hist = out.ind = nullptr;
+        const int rc = qsp_shim::report("qsp_search_for_triangulation_batch",
+                                        qsp_search_for_triangulation_batch(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        vvMatchedPairs.assign(nc, std::vector<std::pair<size_t, size_t>>());
+        vnMatches.assign(nc, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t i1 = 0; i1 < N1; ++i1) {                                 // :812-820
+                const int32_t idx2 = match[c * N1 + i1];
+                if (idx2 >= 0) vvMatchedPairs[c].push_back(std::make_pair(i1, (size_t)idx2));
+            }
+            vnMatches[c] = n_matches[c];
+        }
+        return QSP_OK;
+    }
 };
 
 }  // namespace ORB_SLAM2

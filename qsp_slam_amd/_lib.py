@@ -146,6 +146,19 @@ class SearchBowOut(C.Structure):
                 ("ind", c_int32_p)]
 
 
+class TriFrame(C.Structure):
+    _fields_ = [("bow", BowFrame), ("xy", c_float_p), ("stereo", c_uint8_p), ("sigma2", c_float_p), ("scale", c_float_p)]
+
+
+class SearchTriIn(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("kf1", C.POINTER(TriFrame)), ("kf2", C.POINTER(TriFrame)), ("F12", c_float_p), ("exy", c_float_p),
+                ("th", C.c_int32), ("only_stereo", C.c_int32), ("check_orientation", C.c_int32)]
+
+
+class SearchTriOut(C.Structure):
+    _fields_ = SearchBowOut._fields_
+
+
 SYMBOLS = [
     "qsp_last_error", "qsp_version", "qsp_device_count",
     "qsp_decoder_create", "qsp_decoder_destroy", "qsp_decoder_set_option", "qsp_decoder_get_counter", "qsp_decode_sdf",
@@ -160,7 +173,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -255,6 +268,7 @@ def lib():
                                              C.c_int32, C.c_double] + [c_double_p] * 8
     L.qsp_search_by_sim3_batch.argtypes = [C.c_int, C.POINTER(SearchSim3In), C.POINTER(SearchSim3Out)]
     L.qsp_search_by_bow_batch.argtypes = [C.c_int, C.POINTER(SearchBowIn), C.POINTER(SearchBowOut)]
+    L.qsp_search_for_triangulation_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(SearchTriOut)]
     L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]

@@ -467,6 +467,59 @@ def search_by_bow_batch(shared, cands, *, shared_is_source=True, th=50, th_inclu
     return res
 
 
+def _tri_frame(f, keep, target):
+    """qsp_tri_frame over the arrays of a frame dict (search_for_triangulation_batch): the qsp_bow_frame and the arrays beside it"""
+    o = _lib.TriFrame()
+    o.bow = _bow_frame(f, keep)
+    n = int(o.bow.n)
+    a = dict(xy=_arr(np.reshape(f["xy"], (-1, 2)), np.float32), stereo=_arr(np.asarray(f["stereo"]).astype(bool).reshape(-1), np.uint8))
+    widths = dict(xy=2, stereo=1)
+    if target:
+        a.update(sigma2=_arr(np.reshape(f["sigma2"], -1), np.float32), scale=_arr(np.reshape(f["scale"], -1), np.float32))
+        widths.update(sigma2=1, scale=1)
+        o.sigma2, o.scale = _lib.fptr(a["sigma2"]), _lib.fptr(a["scale"])
+    for key, w in widths.items():
+        if int(np.size(f[key])) != w * n:
+            raise ValueError("search_for_triangulation_batch: %s does not hold %d values per key point" % (key, w))
+    o.xy, o.stereo = _lib.fptr(a["xy"]), _lib.u8ptr(a["stereo"])
+    keep.append(a)
+    return o
+
+
+def search_for_triangulation_batch(shared, cands, F12, exy, th=50, only_stereo=False, check_orientation=False, tap=False, device=0):
+    """ORBmatcher::SearchForTriangulation (reference src/ORBmatcher.cc:657-823) for every covisible neighbour in ONE call
+    (qsp_search_for_triangulation_batch, include/qsp_hip.h).  A frame is the dict of search_by_bow_batch -- desc (n,32) uint8, angle
+    (n,), eligible (n,) (1 = the slot holds no map point; None = every slot), node_id, node_off, feat -- with xy (n,2) and stereo
+    (n,) beside it and, for the neighbours, sigma2 (n,) and scale (n,) gathered through the key point's octave.  `shared` is the
+    current key frame, the source of every neighbour in `cands`; F12 (n_cand,3,3) and exy (n_cand,2) are each neighbour's
+    fundamental matrix and epipole.  Returns one dict per neighbour: match (shared n,) int32 target index or -1, n_matches and, with
+    tap=True, match_raw (before the rotation cull), dist, hist (30,), ind (3,)."""
+    nc = len(cands)
+    if nc == 0:
+        return []
+    keep = []
+    f1 = _tri_frame(shared, keep, False)
+    f2 = (_lib.TriFrame * nc)(*[_tri_frame(c, keep, True) for c in cands])
+    F = _arr(np.reshape(F12, (-1, 9)), np.float32)
+    e = _arr(np.reshape(exy, (-1, 2)), np.float32)
+    if len(F) != nc or len(e) != nc:
+        raise ValueError("search_for_triangulation_batch: F12 and exy hold one entry per neighbour")
+    n1 = int(f1.bow.n)
+    i = _lib.SearchTriIn(nc, C.pointer(f1), f2, _lib.fptr(F), _lib.fptr(e), int(th), 1 if only_stereo else 0, 1 if check_orientation else 0)
+    n_out = max(nc * n1, 1)
+    match, count = np.zeros(n_out, np.int32), np.zeros(nc, np.int32)
+    raw, dist, hist, ind = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32), np.zeros((nc, 30), np.int32), np.zeros((nc, 3), np.int32)
+    o = _lib.SearchTriOut(_lib.i32ptr(match), _lib.i32ptr(count), *([_lib.i32ptr(a) for a in (raw, dist, hist, ind)] if tap else [None] * 4))
+    _lib.check(_lib.lib().qsp_search_for_triangulation_batch(int(device), C.byref(i), C.byref(o)))
+    res = []
+    for c in range(nc):
+        r = dict(match=match[c * n1:(c + 1) * n1].copy(), n_matches=int(count[c]))
+        if tap:
+            r.update(match_raw=raw[c * n1:(c + 1) * n1].copy(), dist=dist[c * n1:(c + 1) * n1].copy(), hist=hist[c].copy(), ind=ind[c].copy())
+        res.append(r)
+    return res
+
+
 def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
                              device=0):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map
