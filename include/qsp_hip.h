@@ -572,7 +572,15 @@ int qsp_pose_optimize(qsp_pose_optimizer* h, int32_t n, const double* K, const d
  * the initial states, the Gauss-Newton iterations run as in qsp_refine_batch_run, one kernel applies the selection rule, and
  * only the kept pose / code / loss per detection come back.  The filters on MapPoint flags (isBad, isOutlier, object_id:
  * :612-617,640-647) are pointer chasing over the map and stay with the caller: the arrays hold the points that passed.
- * Host pointers; ragged arrays are concatenated, *_off has n_det + 1 entries. */
+ * Host pointers; ragged arrays are concatenated, *_off has n_det + 1 entries.
+ * Every count may be 0.  A detection without feature points (fg_off[d + 1] == fg_off[d]) is refined on its background rays alone
+ * and owns no entry of depth_obs; one without map points (pts_off[d + 1] == pts_off[d]) is accepted and comes back as
+ * reconstruct_object gives it for an empty point set: every hypothesis not good with loss 0 (optimizer.py:168-169), so
+ * kept_flip = n_flip - 1 and is_good = 0.
+ * Refusals are QSP_ERR_INVALID: n_det <= 0, a null T_cw / K / T_wo / offset array, offsets that do not start at 0 or decrease,
+ * an n_flip outside 1 .. 64, an observation array that is null while its offsets count rows, a cfg->code_len that is not the
+ * decoder's (and, for the group entry, a null det_class or a class outside the group).  The code refuses before any launch: no
+ * output is written. */
 typedef struct {
     int32_t n_det;
     const float* T_cw;         /* (n_det,4,4) row-major SE3 pose of the detection's key frame (KeyFrame::GetPose)        */

@@ -3,6 +3,7 @@ host-side selection of the Python mirror (reference src/LocalMapping_util.cc:585
 import math
 
 import numpy as np
+import pytest
 
 from oracle import detections_oracle as DO
 from qsp_slam_amd import synth
@@ -69,3 +70,82 @@ def test_keep_rule_cases():
             if (not good[best]) or (good[k] and loss[k] < loss[best]):
                 best = k
         assert DO.keep_rule(list(good), list(loss)) == best
+
+
+# ---- the fixture conditions of tests/detection_cases.py (the GPU side: tests/test_gpu_detections.py) ---------------------------
+
+def test_distinct_intrinsics_give_distinct_inverses_and_rays_that_still_hit_the_object():
+    from tests import detection_cases as dc
+    Ks = [np.asarray(K, np.float32) for K in dc.INTRINSICS]
+    assert all(K[0] != K[1] for K in Ks)
+    for col in range(4):
+        assert len({float(K[col]) for K in Ks}) == 4
+    inv = [DO.eigen_inverse_k(K) for K in Ks]
+    for i in range(4):
+        for j in range(i):
+            # every entry the rays use differs between any two cameras: a kernel reading another detection's K shows in x and in y
+            assert all(inv[i][r, c] != inv[j][r, c] for r, c in ((0, 0), (1, 1), (0, 2), (1, 2)))
+    base = synth.make_detections(11, 4, 700, n_fg=96, n_bg=40, n_kf=2)
+    for d, K in zip(base, Ks):
+        e = dc.with_intrinsics(d, K)
+        assert e["K"].dtype == np.float32 and e["fg_px"].dtype == np.float32 and e["fg_px"].shape == d["fg_px"].shape
+        r0, r1 = DO.assemble(d)[1], DO.assemble(e)[1]
+        assert np.abs(r1 - r0).max() < 2e-6                 # the same rays (float32 pixels of ~600: 3e-5 px / fx each way)
+        if not np.array_equal(K, d["K"]):
+            wrong = DO.assemble(dict(e, K=d["K"]))[1]
+            assert np.abs(wrong - r0)[:96].max() > 1e-2     # and the pixels did move: the old K no longer fits them
+
+
+def test_with_yaw_puts_flip_k_on_the_perturbed_ground_truth():
+    from tests import detection_cases as dc
+    d = synth.make_detections(5, 1, 100, n_fg=16, n_bg=8)[0]
+    for flips, k in ((4, 1), (4, 2), (4, 3), (6, 3)):
+        e = dc.with_yaw(d, k, flips)
+        T = DO.init_poses(e, flips, 2 * math.pi / flips)
+        T0 = DO.init_poses(d, 1, 2 * math.pi / flips)[0]
+        assert np.abs(T[k] - T0).max() < 1e-5
+        assert all(np.abs(T[j] - T0).max() > 0.1 for j in range(flips) if j != k)
+        assert np.array_equal(e["T_wo"][:, 3], d["T_wo"][:, 3])
+
+
+def test_with_counts_and_the_stride_cases():
+    from tests import detection_cases as dc
+    dets = dc.stride_detections()
+    assert [len(d["pts_world"]) for d in dets] == [37, dc.ONE_PASS + 1, 64, 64, dc.ONE_PASS, 37]
+    assert [len(d["fg_px"]) for d in dets] == [12, 12, dc.ONE_PASS + 1, 24, 12, 12]
+    assert [3 * len(d["bg_rays"]) for d in dets] == [12, 12, 24, dc.ONE_PASS + 2, 12, 12]
+    for d in dets:
+        assert len(d["fg_world"]) == len(d["fg_px"])
+        for key in ("pts_world", "fg_px", "fg_world", "bg_rays"):
+            assert d[key].dtype == np.float32 and len(np.unique(d[key], axis=0)) == len(d[key]), key      # no two rows equal
+        assert np.all(d["bg_rays"][:, 2] == 1.0)
+    # grown observations stay on the object: their rays meet their map points to a centimetre
+    big = dets[2]
+    pts, rays, depth = DO.assemble(big)
+    assert np.abs(rays[:dc.ONE_PASS + 1, :2] * depth[:, None] - DO.cv_affine(big["T_cw"], big["fg_world"])[:, :2]).max() < 2e-2
+
+
+
+@pytest.mark.parametrize("name", ["flips4", "flips6"])
+def test_middle_flip_fixtures_keep_flip_k_by_a_loss_gap(name):
+    """under the oracle alone: hypothesis k good, its loss at least 1e-2 (relative) below every other good hypothesis's"""
+    from tests import detection_cases as dc
+    flips, n_iter, _, _, yaws = dc.MIDDLE_FLIP[name]
+    kept = []
+    for d, k in zip(dc.middle_flip_detections(name), yaws):
+        k = k or 0
+        hyps = dc.oracle_hypotheses(d, flips, n_iter)
+        assert dc.middle_flip_holds(hyps, k), (name, k, [(h["is_good"], h["loss"]) for h in hyps])
+        assert DO.keep_rule([h["is_good"] for h in hyps], [h["loss"] for h in hyps]) == k
+        # the two-outcome rule a wrong kernel could follow ("first if good, else last") keeps another one
+        assert k == 0 or hyps[0]["is_good"]
+        kept.append(k)
+    assert any(0 < k < flips - 1 for k in kept)
+
+
+def test_fixture_predicates():
+    from tests import detection_cases as dc
+    h = lambda good, loss=1.0: dict(is_good=good, loss=loss)
+    assert dc.middle_flip_holds([h(True, 1.0), h(True, 0.98), h(False, 0.1)], 1)
+    assert not dc.middle_flip_holds([h(True, 1.0), h(True, 0.995)], 1)
+    assert not dc.middle_flip_holds([h(True, 1.0), h(False, 0.5)], 1)
