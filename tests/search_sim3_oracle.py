@@ -83,19 +83,32 @@ def _target(frame):
                 octave=np.asarray(frame["octave"], np.int64).reshape(-1), desc=np.asarray(frame["desc"], np.uint8).reshape(-1, 32))
 
 
-def one_pass(S, T, cand, direction, pre, flavour, traversal="grid", tgt=None):
+MUTANTS = ("src_pyramid", "cand0_K", "cand0_th", "swap_rows_cols", "no_lower_clamp", "no_upper_clamp", "gate_unclamped")
+
+
+def one_pass(S, T, cand, direction, pre, flavour, traversal="grid", tgt=None, mutant=None, first=None):
     """One direction of SearchBySim3 over the source frame S into the target frame T.  Returns dict(best, dist (n,) int64 with dist
-    -1 where no key point was eligible, knife (n,), reason (n,) and info: one dict per searched slot with what the tests count)."""
+    -1 where no key point was eligible, knife (n,), reason (n,) and info: one dict per searched slot with what the tests count).
+    `mutant` (brute traversal only) makes ONE of the mistakes a kernel or a staging loop could make, so that the tests can show
+    which fixtures notice it: the SOURCE's pyramid (log_scale, n_levels, scale factors) for PredictScale; K or th of `first`, the
+    batch's candidate 0; the target's grid_rows and grid_cols swapped; PredictScale without its lower or its upper clamp (scale
+    factors continued geometrically); the octave gate evaluated with the unclamped level.  The knife-edge distances are the true ones."""
+    assert mutant is None or (mutant in MUTANTS and traversal == "brute")
     F = f32 if flavour == "f32" else f64
     tgt = tgt or _target(T)
     n = int(np.size(S["octave"]))
     M, t = transforms(cand, F)[direction]
-    K = np.asarray(cand["K"], f32).astype(F)
-    th = F(f32(cand.get("th", TH)))
+    K = np.asarray((first if mutant == "cand0_K" else cand)["K"], f32).astype(F)
+    th = F(f32((first if mutant == "cand0_th" else cand).get("th", TH)))
     Rcw, tcw = np.asarray(S["Rcw"], f32).reshape(3, 3), np.asarray(S["tcw"], f32).reshape(3)
     min_x, max_x, min_y, max_y = [F(f32(b)) for b in T["bounds"]]
     cols, rows, w_inv, h_inv = int(T["grid"][0]), int(T["grid"][1]), F(f32(T["grid"][2])), F(f32(T["grid"][3]))
-    sf, n_levels, log_scale = np.asarray(T["scale_factors"], f32).astype(F), int(np.size(T["scale_factors"])), F(f32(T["log_scale"]))
+    P = S if mutant == "src_pyramid" else T
+    sf, n_levels, log_scale = np.asarray(P["scale_factors"], f32).astype(F), int(np.size(P["scale_factors"])), F(f32(P["log_scale"]))
+    filed = tgt["ok"]
+    if mutant == "swap_rows_cols":
+        cols, rows = rows, cols
+        filed = (tgt["cx"] >= 0) & (tgt["cx"] < cols) & (tgt["cy"] >= 0) & (tgt["cy"] < rows)
     kx, ky = tgt["kp"][:, 0].astype(F), tgt["kp"][:, 1].astype(F)
     best, dist = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
     knife, reason, info = np.full(n, np.inf), np.zeros(n, np.int64), {}
@@ -137,8 +150,14 @@ def one_pass(S, T, cand, direction, pre, flavour, traversal="grid", tgt=None):
             ratio = F(f32(S["dist_max"][i])) / d3
             q = np.log(ratio) / log_scale                         # (numpy's float32 log stands in for logf)
             k += [abs(float(q) - e) for e in range(n_levels - 1)]  # ceil(q) clamped to [0, n_levels - 1] changes at 0 .. n_levels - 2
-            level = int(min(max(np.ceil(q), 0), n_levels - 1))
-            r = th * sf[level]
+            level = gate = int(min(max(np.ceil(q), 0), n_levels - 1))
+            if mutant == "no_lower_clamp":
+                level = gate = int(min(np.ceil(q), n_levels - 1))
+            elif mutant == "no_upper_clamp":
+                level = gate = int(max(np.ceil(q), 0))
+            elif mutant == "gate_unclamped":
+                gate = int(np.ceil(q))
+            r = th * (sf[level] if 0 <= level < n_levels else F(np.exp(f64(log_scale)) ** level))
             a_x, b_x, a_y, b_y = ((u - min_x) - r) * w_inv, ((u - min_x) + r) * w_inv, ((v - min_y) - r) * h_inv, ((v - min_y) + r) * h_inv
             lo_x, hi_x, lo_y, hi_y = int(np.floor(a_x)), int(np.ceil(b_x)), int(np.floor(a_y)), int(np.ceil(b_y))
             min_cx, max_cx, min_cy, max_cy = max(0, lo_x), min(cols - 1, hi_x), max(0, lo_y), min(rows - 1, hi_y)
@@ -159,10 +178,10 @@ def one_pass(S, T, cand, direction, pre, flavour, traversal="grid", tgt=None):
                         found += [j for j in tgt["grid"][ix][iy] if in_box[j]]
             found = np.array(found, np.int64)
         else:
-            elig = ok & (tgt["cx"] >= min_cx) & (tgt["cx"] <= max_cx) & (tgt["cy"] >= min_cy) & (tgt["cy"] <= max_cy) & in_box
+            elig = filed & (tgt["cx"] >= min_cx) & (tgt["cx"] <= max_cx) & (tgt["cy"] >= min_cy) & (tgt["cy"] <= max_cy) & in_box
             found = np.nonzero(elig)[0]
         octs = tgt["octave"][found]
-        keep = found[(octs >= level - 1) & (octs <= level)]
+        keep = found[(octs >= gate - 1) & (octs <= gate)]
         inf = dict(level=level, q=float(q), lo_x=lo_x, hi_x=hi_x, lo_y=lo_y, hi_y=hi_y, octaves=sorted(set(int(o) - level for o in octs)),
                    tie=False, tie_same_cx=False, unfiled_in_box=int((in_box & ~ok).sum()))
         info[i] = inf
@@ -192,14 +211,14 @@ def one_pass(S, T, cand, direction, pre, flavour, traversal="grid", tgt=None):
     return dict(best=best, dist=dist, knife=knife, reason=reason, info=info)
 
 
-def search(kf1, cand, flavour, traversal="grid", tgt1=None):
+def search(kf1, cand, flavour, traversal="grid", tgt1=None, mutant=None, first=None):
     """SearchBySim3 of one candidate: both passes, the agreement step (:1307-1323) and the knife-edge distances"""
     kf2 = cand["kf2"]
     n1, n2 = int(np.size(kf1["octave"])), int(np.size(kf2["octave"]))
     pre1 = np.zeros(n1, np.uint8) if cand.get("pre1") is None else np.asarray(cand["pre1"], np.uint8)
     pre2 = np.zeros(n2, np.uint8) if cand.get("pre2") is None else np.asarray(cand["pre2"], np.uint8)
-    a = one_pass(kf1, kf2, cand, 0, pre1, flavour, traversal)
-    b = one_pass(kf2, kf1, cand, 1, pre2, flavour, traversal, tgt=tgt1)
+    a = one_pass(kf1, kf2, cand, 0, pre1, flavour, traversal, mutant=mutant, first=first)
+    b = one_pass(kf2, kf1, cand, 1, pre2, flavour, traversal, tgt=tgt1, mutant=mutant, first=first)
     match = np.full(n1, -1, np.int64)
     for i1 in range(n1):
         j = a["best"][i1]
@@ -507,3 +526,182 @@ def in_band_share(r64, width):
 
 
 MARGINS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "search_sim3_margins.json")
+
+
+# ---- the mixed pool: frames and candidates that differ from each other -----------------------------------------------------
+# POOL's candidates share one pyramid, one camera, one th and one grid size, so an index mistake between source and target, or
+# between candidate c and candidate 0, computes the same there.  Here everything a FrameP or a CandP carries differs between key
+# frame 1 (key_frame_1(): 8 levels at 1.2, 640 x 480 on 64 x 48) and key frame 2, and from one candidate to the next.  The camera
+# of a candidate is FITTED: of the 100 common points seen from key frame 2, the third smallest and third largest normalised
+# coordinates land on `span` (u_lo, u_hi, v_lo, v_hi), so the cameras differ by hundreds of pixels, two points per side fall
+# outside the image, and with span None the extreme ones sit in the first and last filed row and column of the grid
+# (Frame::PosInGrid ROUNDS: the last half cell of an image is never filed, and of a 1 x 1 grid only the top-left quarter is).
+POOL_MIXED = [
+    dict(name="5 levels at 1.5", levels=5, scale=1.5, th=12.0, bounds=BOUNDS_VGA, grid=(64, 48), span=(60.0, 580.0, 50.0, 430.0), seed=21, s12=1.6),
+    dict(name="16 levels at 1.1", levels=16, scale=1.1, th=5.0, bounds=BOUNDS_VGA, grid=(64, 48), span=(4.0, 630.0, 4.0, 470.0), seed=42),
+    dict(name="1 level", levels=1, scale=1.2, th=7.5, bounds=BOUNDS_VGA, grid=(64, 48), span=(150.0, 490.0, 120.0, 360.0), seed=13),
+    dict(name="8 levels at sqrt 2", levels=8, scale=float(np.sqrt(2.0)), th=5.0, bounds=BOUNDS_VGA, grid=(64, 48), span=(100.0, 560.0, 30.0, 450.0), seed=264),
+    dict(name="1 x 1 grid", levels=8, scale=1.2, th=7.5, bounds=BOUNDS_VGA, grid=(1, 1), span=(2.0, 380.0, 2.0, 290.0), seed=15),
+    dict(name="5 x 7 grid", levels=5, scale=1.5, th=12.0, bounds=(0.0, 320.0, 0.0, 240.0), grid=(5, 7), span=None, seed=16, s12=0.8),
+    dict(name="64 x 64 grid", levels=16, scale=1.1, th=5.0, bounds=BOUNDS_VGA, grid=(64, 64), span=None, seed=27),
+    dict(name="bounds off 0", levels=8, scale=float(np.sqrt(2.0)), th=7.5, bounds=(-12.5, 651.25, -8.25, 487.5), grid=(64, 48), span=None, seed=28),
+]
+THS = (5.0, 7.5, 12.0)
+N2_MIXED = 128
+S_GATES = (S_CLAMP0, S_CLAMP0 + 1, S_CLAMPTOP, S_CLAMPTOP + 1)  # sources of key frame 1 whose level is clamped in most pyramids
+I_1X1 = 4
+
+
+def _pixk(K, Y):
+    return np.array([K[0] * Y[0] / Y[2] + K[2], K[1] * Y[1] / Y[2] + K[3]])
+
+
+def _unpixk(K, uv, z):
+    return np.array([(uv[0] - K[2]) / K[0] * z, (uv[1] - K[3]) / K[1] * z, z])
+
+
+def _clamp_level(q, n_levels):
+    return int(min(max(np.ceil(q), 0), n_levels - 1))
+
+
+@functools.lru_cache(maxsize=None)
+def make_mixed(index):
+    """Candidate `index` of POOL_MIXED.  Slot j < 100 of key frame 2: a key point at the projection of common point perm[j] (octave: the
+    level PredictScale gives with key frame 2's pyramid, or one below) and a map point that projects, with this candidate's camera,
+    onto key frame 1's key point perm[j], with dist_max such that the level predicted with key frame 1's pyramid is that key
+    point's octave or one above; where that octave is 0 or 6 every other such point gets log(ratio) / log_scale = -2.5 or 9.4, the
+    two clamps of the pass 2 -> 1.  Then the hand-made key points (no map points) around the projections of sources of key frame 1,
+    recorded under `named`; then unrelated key points up to N2_MIXED."""
+    spec = POOL_MIXED[index]
+    w, k1 = world(), key_frame_1()
+    rng = np.random.default_rng(52000 + spec["seed"])
+    r32 = lambda a: np.asarray(a, f32).astype(f64)
+    s12, R12, t12, R2, t2 = _sim3(spec["seed"])
+    s12, R12, t12, R2, t2 = float(f32(spec.get("s12", s12))), r32(R12), r32(t12), r32(R2), r32(t2)
+    n_levels, scale, th = spec["levels"], f32(spec["scale"]), spec["th"]
+    sf, log_scale = np.array([scale ** i for i in range(n_levels)], f32), f32(np.log(scale))
+    min_x, max_x, min_y, max_y = spec["bounds"]
+    cols, rows = spec["grid"]
+    grid = (cols, rows, f32(cols) / f32(max_x - min_x), f32(rows) / f32(max_y - min_y))
+    cw, ch = (max_x - min_x) / cols, (max_y - min_y) / rows
+    span = spec["span"] or (min_x + 1.0, min_x + (cols - 0.9) * cw, min_y + 1.0, min_y + (rows - 0.9) * ch)
+    Z = np.stack([_to_cam2(s12, R12, t12, w["Y"][i]) for i in range(N1)])      # key frame 1's points in key frame 2's camera
+    assert (Z[:N_COMMON, 2] > 0).all()
+    K = np.zeros(4)
+    for a in (0, 1):
+        xs = np.sort(Z[:N_COMMON, a] / Z[:N_COMMON, 2])
+        K[a] = (span[2 * a + 1] - span[2 * a]) / (xs[-3] - xs[2])
+        K[2 + a] = span[2 * a] - K[a] * xs[2]
+    K = r32(K)
+    c2 = np.stack([_pixk(K, z) for z in Z])
+    q2 = np.log(k1["dist_max"].astype(f64) / np.linalg.norm(Z, axis=1)) / float(log_scale)
+    L2 = [_clamp_level(q, n_levels) for q in q2]
+    rows_, named = [], dict(gates={}, th_in=None, th_out=None, tie=None, clamp2_low=[], clamp2_top=[])
+
+    def add(uv, octave, desc, point=None):
+        rows_.append((np.asarray(uv, f64), int(octave), desc, point))
+        return len(rows_) - 1
+
+    for j, i1 in enumerate(rng.permutation(N_COMMON)):
+        i1 = int(i1)
+        Y1 = _unpixk(K, k1["kp"][i1].astype(f64) + rng.normal(size=2) * 0.5, w["Y"][i1][2])
+        o1 = int(k1["octave"][i1])
+        pt = dict(Z=_to_cam2(s12, R12, t12, Y1), d1=float(np.linalg.norm(Y1)), q=min(o1 + int(rng.integers(0, 2)), N_LEVELS - 1) - 0.5,
+                  desc=_flip(rng, w["desc"][i1], int(rng.integers(0, 12))), wide=False)
+        if o1 == 0 and len(named["clamp2_low"]) < 3:
+            pt.update(q=-2.5, wide=True)
+            named["clamp2_low"].append(j)
+        elif o1 >= N_LEVELS - 2 and len(named["clamp2_top"]) < 3:
+            pt.update(q=9.4, wide=True)
+            named["clamp2_top"].append(j)
+        add(c2[i1] + rng.normal(size=2) * 0.7, max(L2[i1] - int(rng.integers(0, 2)), 0), _flip(rng, w["desc"][i1], int(rng.integers(0, 12))), pt)
+
+    def filed(uv):
+        x, y = (uv[0] - min_x) / cw, (uv[1] - min_y) / ch
+        return 0.0 < x < cols - 0.6 and 0.0 < y < rows - 0.6       # inside the image and short of the half cell that is never filed
+
+    d = lambda s: k1["mp_desc"][s]
+    # the octave gate at the clamped levels: the winner at the predicted level, perfect descriptors one above and two below it
+    for s in S_GATES:
+        L = L2[s]
+        g = dict(q=float(q2[s]), level=L, winner=add(c2[s] + (1.5, -1.0), L, _flip(rng, d(s), 12)), above=None, below=None)
+        if L + 1 < n_levels:
+            g["above"] = add(c2[s] + (-1.0, 1.2), L + 1, d(s).copy())
+        if L - 2 >= 0:
+            g["below"] = add(c2[s] + (0.8, 1.4), L - 2, d(s).copy())
+        named["gates"][s] = g
+    # th: a key point inside the box at this candidate's th and outside it at the next smaller th; a perfect one outside the box
+    # at this th and inside it at the next larger.  Sources: the first special slots whose surroundings are filed.
+    free = [s for s in S_SPECIAL if filed(c2[s] - 13.0 * float(sf[L2[s]])) and filed(c2[s] + 13.0 * float(sf[L2[s]]))]
+    smaller, larger = [t for t in THS if t < th], [t for t in THS if t > th]
+    if smaller:
+        s = free.pop(0)
+        named["th_in"] = (s, add(c2[s] + (0.5 * (smaller[-1] + th) * float(sf[L2[s]]), 0.3), L2[s], _flip(rng, d(s), 6)))
+    if larger:
+        s = free.pop(0)
+        add(c2[s] + (0.5 * (larger[0] + th) * float(sf[L2[s]]), -0.4), L2[s], d(s).copy())
+        named["th_out"] = (s, add(c2[s] + (1.0, 1.0), L2[s], _flip(rng, d(s), 9)))
+    if (cols, rows) == (1, 1):
+        # a tie of two key points 12 pixels apart in x: in this grid both lie in cell (0, 0) and the lower index is first; in a
+        # 64 x 48 grid over the same image the one with the smaller x is
+        s = free.pop(0)
+        a = add(c2[s] + (6.0, -1.0), L2[s], _flip(rng, d(s), 7))
+        named["tie"] = (s, a, add(c2[s] + (-6.0, 1.0), L2[s], _flip(rng, d(s), 7)))
+    while len(rows_) < N2_MIXED:
+        uv = rng.uniform((min_x + 1, min_y + 1), (max_x - 1, max_y - 1))
+        lvl = int(rng.integers(1, N_LEVELS - 1))
+        pt = None if len(rows_) % 3 == 0 else dict(Z=_unpix(uv + rng.normal(size=2) * 3, rng.uniform(3.0, 8.0)), q=lvl - 0.5, wide=False, d1=None,
+                                                   desc=rng.integers(0, 256, 32).astype(np.uint8))
+        add(uv, int(rng.integers(0, n_levels)), rng.integers(0, 256, 32).astype(np.uint8), pt)
+    n2 = len(rows_)
+    fr = dict(bounds=spec["bounds"], grid=grid, log_scale=log_scale, scale_factors=sf, Rcw=R2.astype(f32), tcw=t2.astype(f32), **_mp_fields(n2))
+    kp, octave, desc = np.zeros((n2, 2), f32), np.zeros(n2, np.int32), np.zeros((n2, 32), np.uint8)
+    for j, (uv, o, de, pt) in enumerate(rows_):
+        kp[j], octave[j], desc[j] = uv, o, de
+        if pt is None:
+            fr["has_point"][j] = 0
+            continue
+        _set_point(fr, j, pt["Z"], 0, pt["desc"], R2, t2)
+        d1 = pt["d1"] or float(np.linalg.norm(s12 * (R12 @ pt["Z"]) + t12))     # the distance seen from key frame 1
+        fr["dist_max"][j] = f32(d1 * float(SCALE) ** pt["q"])
+        fr["dist_max_inv"][j], fr["dist_min_inv"][j] = f32(1.2) * fr["dist_max"][j], f32(0.8) * f32(fr["dist_max"][j] / SF[-1])
+        if pt["wide"]:
+            fr["dist_min_inv"][j], fr["dist_max_inv"][j] = f32(0.01), f32(1000.0)
+    fr.update(kp=kp, octave=octave, desc=desc)
+    pre1, pre2 = np.zeros(N1, np.uint8), np.zeros(n2, np.uint8)
+    pre1[5], pre2[3], pre1[9] = 1, 1, 1
+    return dict(kf2=fr, K=K.astype(f32), s12=f32(s12), R12=R12.astype(f32), t12=t12.astype(f32), th=f32(th), pre1=pre1, pre2=pre2,
+                kind="mixed", small=False, named=named, name=spec["name"])
+
+
+@functools.lru_cache(maxsize=None)
+def pool_mixed():
+    """the mixed candidates (inputs only; treat as read-only); all share key_frame_1()"""
+    return [make_mixed(i) for i in range(len(POOL_MIXED))]
+
+
+@functools.lru_cache(maxsize=None)
+def pool_mixed_results(flavour, traversal="grid", mutant=None):
+    return [search(key_frame_1(), c, flavour, traversal, tgt1=target_1(), mutant=mutant, first=pool_mixed()[0]) for c in pool_mixed()]
+
+
+@functools.lru_cache(maxsize=None)
+def pool_mutant_results(mutant):
+    """POOL under a mutant: the brute traversal, float64"""
+    return [search(key_frame_1(), c, "f64", "brute", tgt1=target_1(), mutant=mutant, first=pool()[0]) for c in pool()]
+
+
+@functools.lru_cache(maxsize=None)
+def measured_mixed():
+    """CPU: as measured(), over the mixed pool"""
+    worst = 0.0
+    for a, b in zip(pool_mixed_results("f32"), pool_mixed_results("f64")):
+        for d, diff in zip((1, 2), disagreements(a, b)):
+            if diff.any():
+                worst = max(worst, float(b["knife%d" % d][diff].max()))
+    return worst
+
+
+def band_mixed():
+    """what tests/test_gpu_search_sim3.py leaves undecided on the mixed pool: 4 x its measured band"""
+    return 4 * measured_mixed()

@@ -1,6 +1,7 @@
 // search_caller.cpp -- stand-alone caller of OrbMatcherHip::SearchBySim3Batch over the stand-in map types of this directory and the
 // stub of qsp_search_by_sim3_batch (tests/test_shim_search_sim3.py builds and runs it; never loaded into Python).  The scene is
-// procedural so that the test can restate it: key frame 1 with 12 slots, three candidate key frames of 8, 0 and 10 slots.
+// procedural so that the test can restate it: key frame 1 with 12 slots, three candidate key frames of 8, 0 and 10 slots.  Mode
+// "mixed": every candidate key frame has a pyramid (levels, scale) and a grid (columns, rows) of its own, none of them key frame 1's.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -14,7 +15,12 @@ using namespace ORB_SLAM2;
 
 static const int N1 = 12, N2[3] = {8, 0, 10};
 
-static void make_kf(SearchKeyFrame& kf, int k, int n) {
+static const int MIX_LEVELS[3] = {5, 16, 1}, MIX_COLS[3] = {5, 64, 1}, MIX_ROWS[3] = {7, 64, 1};
+static const float MIX_SCALE[3] = {1.5f, 1.1f, 1.3f}, MIX_LOG[3] = {0.4055f, 0.0953f, 0.2624f};
+
+static void make_kf(SearchKeyFrame& kf, int k, int n, bool mixed = false) {
+    const int levels = mixed ? MIX_LEVELS[k - 2] : 4, cols = mixed ? MIX_COLS[k - 2] : 64, rows = mixed ? MIX_ROWS[k - 2] : 48;
+    const float scale = mixed ? MIX_SCALE[k - 2] : 1.2f;
     kf.mnId = k;
     kf.fx = 500.f + k; kf.fy = 510.f + k; kf.cx = 320.f + 0.5f * k; kf.cy = 240.f + 0.25f * k;
     kf.Tcw = cv::Mat(4, 4, CV_32F);
@@ -25,17 +31,17 @@ static void make_kf(SearchKeyFrame& kf, int k, int n) {
     for (int r = 0; r < 3; ++r) kf.Tcw.at<float>(r, 3) = 0.1f * (r + 1) * k;
     kf.mDescriptors.rows = n;
     for (int j = 0; j < n; ++j) {
-        kf.mvKeysUn.push_back(cv::KeyPoint{{7.f * j + k, 5.f * j + 2.f * k}, j % 4});
+        kf.mvKeysUn.push_back(cv::KeyPoint{{7.f * j + k, 5.f * j + 2.f * k}, j % levels});
         for (int b = 0; b < 32; ++b) kf.mDescriptors.d.push_back((unsigned char)(j * 7 + b * 3 + k));
     }
     kf.mnMinX = -k; kf.mnMaxX = 640 + k; kf.mnMinY = -2 * k; kf.mnMaxY = 480 + k;
-    kf.mnGridCols = 64; kf.mnGridRows = 48;
-    kf.mfGridElementWidthInv = 64.f / (float)(kf.mnMaxX - kf.mnMinX);
-    kf.mfGridElementHeightInv = 48.f / (float)(kf.mnMaxY - kf.mnMinY);
-    kf.mnScaleLevels = 4;
-    kf.mfLogScaleFactor = 0.1823f;
+    kf.mnGridCols = cols; kf.mnGridRows = rows;
+    kf.mfGridElementWidthInv = (float)cols / (float)(kf.mnMaxX - kf.mnMinX);
+    kf.mfGridElementHeightInv = (float)rows / (float)(kf.mnMaxY - kf.mnMinY);
+    kf.mnScaleLevels = levels;
+    kf.mfLogScaleFactor = mixed ? MIX_LOG[k - 2] : 0.1823f;
     float s = 1.f;
-    for (int o = 0; o < 4; ++o) { kf.mvScaleFactors.push_back(s); s *= 1.2f; }
+    for (int o = 0; o < levels; ++o) { kf.mvScaleFactors.push_back(s); s *= scale; }
 }
 static std::vector<std::unique_ptr<SearchMapPoint>> g_points;       // owns every map point of the scene
 static SearchMapPoint* make_mp(int id, int i, float dy) {
@@ -63,7 +69,7 @@ int main(int argc, char** argv) {
     }
     std::vector<SearchKeyFrame*> kfs;
     for (int c = 0; c < 3; ++c) {
-        make_kf(kf2[c], 2 + c, N2[c]);
+        make_kf(kf2[c], 2 + c, N2[c], !std::strcmp(mode, "mixed"));
         for (int j = 0; j < N2[c]; ++j) {
             SearchMapPoint* p = make_mp(100 * (c + 1) + j, j, 0.1f * c);
             p->obs[&kf2[c]] = (size_t)j;

@@ -180,3 +180,57 @@ def test_error_paths_leave_the_outputs_untouched(full):
     assert all(np.array_equal(o[k], fresh[k]) for k in ("best1", "dist1", "best2", "dist2"))
     assert call()[0] == _lib.QSP_OK and not untouched()
     assert np.array_equal(o["best1"][:n1], full[idx[0]]["best1"]) and np.array_equal(o["dist2"][n2[0]:], full[idx[1]]["dist2"])
+
+
+# ---- the mixed pool: every FrameP and CandP field differs between source and target and from one candidate to the next ---------
+@pytest.fixture(scope="module")
+def full_mixed():
+    return run(so.pool_mixed())
+
+
+def test_mixed_pool_equals_the_oracle_outside_its_band(full_mixed):
+    """tests/test_oracle_search_sim3.py shows what a kernel that took the source's pyramid, candidate 0's K or th, rows for cols or
+    an unclamped level would get wrong here (and that POOL lets four of the seven pass)"""
+    width = so.band_mixed()
+    margins.within("search_sim3/mixed/band_f32_vs_f64", so.measured_mixed(), width)
+    worst, n_in_band, n_slots = 0.0, 0, 0
+    for i, (r, g) in enumerate(zip(so.pool_mixed_results("f64"), full_mixed)):
+        n_diff = 0
+        for d in (1, 2):
+            diff = (g["best%d" % d] != r["best%d" % d]) | (g["dist%d" % d] != r["dist%d" % d])
+            n_diff += int(diff.sum())
+            if diff.any():
+                worst = max(worst, float(r["knife%d" % d][diff].max()))
+            n_in_band += int((r["knife%d" % d] < width).sum())
+            n_slots += len(diff)
+        share = so.in_band_share(r, width)
+        print("mixed candidate %d (%s): %d source slots differ from float64, %.4f of the slots inside the band"
+              % (i, so.POOL_MIXED[i]["name"], n_diff, share))
+        assert share <= so.IN_BAND_CAP, (i, share)
+        # the agreement step, wherever both slots of the pair are outside the band
+        sure = r["knife1"] >= width
+        j = r["best1"]
+        sure &= np.where(j >= 0, r["knife2"][np.maximum(j, 0)] >= width, True)
+        assert np.array_equal(g["match12"][sure], r["match12"][sure]), i
+        assert g["n_found"] == int((g["match12"] >= 0).sum())
+        if sure.all():
+            assert g["n_found"] == r["n_found"], (i, g["n_found"], r["n_found"])
+    print("mixed pool: %d of %d source slots inside the band (undecided); largest knife-edge distance of a differing slot %.3e, "
+          "BAND %.3e" % (n_in_band, n_slots, worst, width))
+    margins.within("search_sim3/mixed/in_band_slots", n_in_band, so.IN_BAND_CAP * n_slots)
+    assert margins.within("search_sim3/mixed/slot_edge", worst, width) and (worst < width or worst == 0.0)
+
+
+def test_mixed_candidates_alone_reversed_and_between_the_old_ones(full_mixed):
+    cands, old = so.pool_mixed(), so.pool()
+    for i, c in enumerate(cands):                              # batches of 1: every candidate is candidate 0
+        assert same_bits(run([c])[0], full_mixed[i]), i
+    rev = run(cands[::-1])
+    for i, (r, g) in enumerate(zip(rev[::-1], full_mixed)):
+        assert same_bits(r, g), i
+    woven = []                                                 # old, mixed, old, mixed ...: other frames and other K, th on both sides
+    for i, c in enumerate(cands):
+        woven += [old[i % len(old)], c]
+    res = run(woven)
+    for i in range(len(cands)):
+        assert same_bits(res[2 * i + 1], full_mixed[i]), i

@@ -64,18 +64,22 @@ def run(mode="", **env_extra):
 N1, N2 = 12, (8, 0, 10)
 
 
-def frame(k, n):
+MIX = {2: (5, 7, 5, 1.5, 0.4055), 3: (64, 64, 16, 1.1, 0.0953), 4: (1, 1, 1, 1.3, 0.2624)}   # cols, rows, levels, scale, log_scale
+
+
+def frame(k, n, mixed=False):
+    cols, rows, levels, scale, log_scale = MIX[k] if mixed else (64, 48, 4, 1.2, 0.1823)
     a = 0.1 * k
     R = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]).astype(f32)
     t = np.array([f32(0.1) * f32(r + 1) * f32(k) for r in range(3)], f32)
     sf, s = [], f32(1)
-    for _ in range(4):
+    for _ in range(levels):
         sf.append(s)
-        s = f32(s * f32(1.2))
-    par = [-k, 640 + k, -2 * k, 480 + k, f32(64) / f32(640 + 2 * k), f32(48) / f32(480 + 3 * k), f32(0.1823)]
-    return dict(R=R.reshape(-1), t=t, sf=np.array(sf, f32), par=np.array(par, f32),
+        s = f32(s * f32(scale))
+    par = [-k, 640 + k, -2 * k, 480 + k, f32(cols) / f32(640 + 2 * k), f32(rows) / f32(480 + 3 * k), f32(log_scale)]
+    return dict(R=R.reshape(-1), t=t, sf=np.array(sf, f32), par=np.array(par, f32), shape=(cols, rows, levels),
                 kp=np.array([[f32(7) * f32(j) + f32(k), f32(5) * f32(j) + f32(2) * f32(k)] for j in range(n)], f32).reshape(-1),
-                octave=np.array([j % 4 for j in range(n)]),
+                octave=np.array([j % levels for j in range(n)]),
                 desc=np.array([[(j * 7 + b * 3 + k) % 256 for b in range(32)] for j in range(n)]).reshape(-1))
 
 
@@ -91,9 +95,9 @@ def slots(n, base, dy, null, bad):
     return [(None if j == null else point(base + j, j, dy)) for j in range(n)], [int(j not in (null, bad)) for j in range(n)]
 
 
-def check_frame(got, k, n, pts, has):
-    e = frame(k, n)
-    assert (got["n"], got["cols"], got["rows"], got["n_levels"]) == (n, 64, 48, 4)
+def check_frame(got, k, n, pts, has, mixed=False):
+    e = frame(k, n, mixed)
+    assert (got["n"], got["cols"], got["rows"], got["n_levels"]) == (n,) + e["shape"] and len(got["sf"]) == e["shape"][2]
     for key, want in (("par", e["par"]), ("sf", e["sf"]), ("Rcw", e["R"]), ("tcw", e["t"]), ("kp", e["kp"])):
         assert np.array_equal(got[key], want), (k, key, got[key], want)
     assert list(got["octave"]) == list(e["octave"]) and list(got["desc"]) == list(e["desc"]) and list(got["has"]) == has
@@ -127,6 +131,22 @@ def test_gathered_arrays():
     pre2[6] = 1                                                 # candidate 0: slot 6; the foreign point of slot 7 has no index: pre1 only
     pre2[8 + 9] = 1
     assert list(call["pre1"]) == list(pre1.reshape(-1)) and list(call["pre2"]) == list(pre2)
+
+
+def test_every_frame_is_marshalled_with_its_own_pyramid_and_grid():
+    """mode "mixed": 5 x 7 cells with 5 levels at 1.5, 64 x 64 with 16 at 1.1, 1 x 1 with 1 level, next to key frame 1's 64 x 48
+    with 4 at 1.2 -- each qsp_orb_frame holds its own frame's values, not key frame 1's and not a neighbour's"""
+    res, calls, _ = run("mixed")
+    assert res["status"] == [0] and len(calls) == 1 and len(calls[0]["frames"]) == 4
+    fr = calls[0]["frames"]
+    check_frame(fr[0], 1, N1, *slots(N1, 0, 0.0, 3, 5))
+    for c in range(3):
+        check_frame(fr[1 + c], 2 + c, N2[c], *slots(N2[c], 100 * (c + 1), 0.1 * c, 1, 2), mixed=True)
+    assert [(f["cols"], f["rows"], f["n_levels"]) for f in fr] == [(64, 48, 4), (5, 7, 5), (64, 64, 16), (1, 1, 1)]
+    assert len({float(f["par"][6]) for f in fr}) == 4 and len({float(f["par"][4]) for f in fr}) == 4       # log_scale, width_inv
+    assert np.array_equal(fr[2]["sf"][:3], np.array([1, f32(1.1), f32(1.1) * f32(1.1)], f32))
+    m, found = expected_matches()                              # the write-back does not depend on any of it
+    assert res["matches"] == m and res["found"] == found
 
 
 def expected_matches():
