@@ -1030,6 +1030,70 @@ typedef struct {
 } qsp_search_tri_out;
 int qsp_search_for_triangulation_batch(int device, const qsp_search_tri_in* in, qsp_search_tri_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The MATCH PHASE of ORBmatcher::Fuse for every target key frame in ONE call: the pose overload (src/ORBmatcher.cc:825-975) that
+ * LocalMapping::SearchInNeighbors runs per neighbour and once back into the current key frame, and the Sim3 overload (:977-1100)
+ * that LoopClosing::SearchAndFuse runs per corrected key frame.  Everything up to (bestIdx, bestDist) reads only the point and
+ * the target frame; the map enters afterwards, in the action (GetMapPoint(bestIdx), Replace, AddObservation / AddMapPoint,
+ * vpReplacePoint[iMP] = ...), which the caller replays on the host in the reference's order (OrbMatcherHip::FuseBatch).  One wave
+ * per (target, listed point): one launch.
+ * A target is a qsp_orb_frame, of which kp, octave, desc, the bounds and grid, n_levels, log_scale, scale_factors, Rcw and tcw are
+ * read (the map-point fields are not and may be NULL), and beside it K (fx fy cx cy mbf), the camera centre Ow, th, mvuRight,
+ * mvInvLevelSigma2 and check_reprojection: 1 = the pose overload with its chi-square test (:914-938), 0 = the Sim3 overload, which
+ * has none (for it Rcw = sRcw / scw, tcw = t / scw and Ow = -Rcw^T tcw are the caller's, :986-990).  The map points are ONE pool
+ * shared by all targets; target k searches the pool indices list_idx[list_off[k] .. list_off[k+1]), in that order: the points the
+ * reference would not skip at :846-850 / :1005.  Outputs are per listed pair, in list order.
+ * Per pair, in the reference's float32 arithmetic (matrix rows summed in double and rounded once, t added in float32; 1 / z
+ * rounded to float32 once; u = fx * x + cx as a separate multiply and add; ur = u - mbf * invz; PO = Xw - Ow in float32, cv::norm(PO)
+ * summed and square-rooted in double and rounded once, PO.dot(Pn) summed in double):
+ *   skip when z < 0, when (u, v) is outside [min_x, max_x) x [min_y, max_y), when dist3D < dist_min_inv or dist3D > dist_max_inv,
+ *   when PO.dot(Pn) < 0.5 * dist3D (in double);  level = clamp(ceil(logf(dist_max / dist3D) / log_scale), 0, n_levels - 1) and
+ *   radius = th * scale_factors[level];  a key point is eligible when its own cell (round((x - min_x) * grid_w_inv),
+ *   round((y - min_y) * grid_h_inv)) lies in the grid and in the range KeyFrame::GetFeaturesInArea visits, |kx - u| < radius &&
+ *   |ky - v| < radius (strict), level - 1 <= octave <= level and, with check_reprojection, e2 * inv_level_sigma2[octave] (a
+ *   float32 product; e2 = ex*ex + ey*ey (+ er*er) in float32, left to right) is not > 7.8 in double when u_right >= 0 (zero
+ *   included), else not > 5.99;  the best is the eligible key point of minimum Hamming distance over the 256 bits, ties to the
+ *   first in the reference's traversal order (cell x, cell y, index);  it is kept when the distance is <= 50 (TH_LOW).
+ * The overloads' initial bestDist (256 and INT_MAX) cannot differ under that threshold.
+ * reason names the first gate that ended the pair: 0 matched, 1 z < 0, 2 outside the image, 3 distance limits, 4 viewing angle,
+ * 5 no cell range or no key point in the area (vIndices empty), 6 none of the area's key points eligible, 7 best above TH_LOW
+ * (best_idx -1, best_dist the distance); level is the predicted level, -1 where a gate before it ended the pair.
+ * A pair's outputs have the same bits alone, in any batch and at any list position.  Host pointers.  n_target == 0 or an empty
+ * list is QSP_OK and touches nothing; a target with an empty list or without key points is legal.  Null pointers where data is
+ * required (arrays of a target with n == 0 may be NULL; the tap is two arrays or two NULLs), negative counts, n > 2^26, list_off
+ * that does not start at 0 or decreases, list_idx outside [0, n_point), a key point's octave outside [0, n_levels), n_levels
+ * outside [1, 16], a grid outside 1..64 x 1..64, u_right_off that does not start at 0 or step by target[k].n: QSP_ERR_INVALID.
+ * More than 2^31 - 1 pairs (or key-point slots) in one call: QSP_ERR_UNSUPPORTED.  No output is written unless the call returns
+ * QSP_OK. */
+typedef struct {
+    int32_t n_target;
+    const qsp_orb_frame* target;          /* (n_target) */
+    const float* K;                       /* (n_target,5) fx fy cx cy mbf */
+    const float* Ow;                      /* (n_target,3) GetCameraCenter() / -Rcw^T tcw */
+    const float* th;                      /* (n_target) the reference passes 3.0 (SearchInNeighbors) and 4 (SearchAndFuse) */
+    const int32_t* u_right_off;           /* (n_target+1): target k owns [u_right_off[k], u_right_off[k+1]) of u_right; steps by target[k].n */
+    const float* u_right;                 /* (u_right_off[n_target]) mvuRight */
+    const float* inv_level_sigma2;        /* (n_target,16) mvInvLevelSigma2, the first n_levels read */
+    const uint8_t* check_reprojection;    /* (n_target) 1 = pose overload, 0 = Sim3 overload */
+    int32_t n_point;                      /* the pool */
+    const float* Xw;                      /* (n_point,3) GetWorldPos() */
+    const float* normal;                  /* (n_point,3) GetNormal() */
+    const float* dist_min_inv;            /* (n_point) GetMinDistanceInvariance() */
+    const float* dist_max_inv;            /* (n_point) GetMaxDistanceInvariance() */
+    const float* dist_max;                /* (n_point) mfMaxDistance, what PredictScale divides */
+    const uint8_t* desc;                  /* (n_point,32) GetDescriptor() */
+    const int64_t* list_off;              /* (n_target+1) starts at 0 */
+    const int32_t* list_idx;              /* (list_off[n_target]) pool indices */
+} qsp_fuse_in;
+typedef struct {
+    int32_t* best_idx;                    /* (list_off[n_target]) the target's key point, else -1 */
+    int32_t* best_dist;                   /* (list_off[n_target]) its Hamming distance; -1 where no key point was eligible */
+    /* the tests' tap, both or both NULL */
+    int32_t* reason;                      /* (list_off[n_target]) */
+    int32_t* level;                       /* (list_off[n_target]) */
+} qsp_fuse_out;
+int qsp_fuse_batch(int device, const qsp_fuse_in* in, qsp_fuse_out* out);
+
 #ifdef __cplusplus
 }
 #endif

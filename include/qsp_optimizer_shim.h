@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <list>
 #include <map>
 #include <mutex>
@@ -1309,6 +1310,208 @@ public:
             }
             vnMatches[c] = n_matches[c];
         }
+        return QSP_OK;
+    }
+
+private:
+    struct PoolArrays {                  // the snapshot of the map points all targets of a FuseBatch share
+        std::vector<float> Xw, normal, dmin, dmaxi, dmax;
+        std::vector<uint8_t> desc, ok;   // ok[i]: vpPoints[i] is non-null and not bad
+    };
+    // What Fuse reads of a map point, with the reference's getters; mfMaxDistance as gather() reads it.
+    template <typename MP>
+    static void gather_pool(const std::vector<MP*>& vpPoints, PoolArrays& p) {
+        const size_t n = vpPoints.size();
+        p.Xw.assign(3 * n + 1, 0.f); p.normal.assign(3 * n + 1, 0.f); p.dmin.assign(n + 1, 0.f); p.dmaxi.assign(n + 1, 0.f);
+        p.dmax.assign(n + 1, 0.f); p.desc.assign(32 * n + 1, 0); p.ok.assign(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            MP* pMP = vpPoints[i];
+            if (!pMP || pMP->isBad()) continue;
+            p.ok[i] = 1;
+            const cv::Mat X = pMP->GetWorldPos(), Pn = pMP->GetNormal();
+            for (int r = 0; r < 3; ++r) { p.Xw[3 * i + r] = X.template at<float>(r); p.normal[3 * i + r] = Pn.template at<float>(r); }
+            p.dmin[i] = pMP->GetMinDistanceInvariance();
+            p.dmaxi[i] = pMP->GetMaxDistanceInvariance();
+            p.dmax[i] = p.dmaxi[i] / 1.2f;
+            const auto d = pMP->GetDescriptor();
+            for (int b = 0; b < 32; ++b) p.desc[32 * i + b] = d.template at<unsigned char>(0, b);
+        }
+    }
+
+    // One qsp_fuse_batch over targets gathered by gather() (fr[k].Rcw / tcw already the overload's), lists[k] the pool indices of
+    // target k.  best[k][a]: the key point matched with lists[k][a], or -1.
+    template <typename KF, typename MP>
+    static int fuse_call(const std::vector<KF*>& vpKFs, std::vector<qsp_orb_frame>& fr, const std::vector<float>& Ow, const bool check,
+                         const float th, const std::vector<MP*>& vpPoints, const PoolArrays& p, const std::vector<std::vector<int32_t>>& lists,
+                         std::vector<std::vector<int32_t>>& best) {
+        const size_t nk = vpKFs.size();
+        std::vector<float> K, vth(nk, th), ur, inv(16 * nk, 0.f);
+        std::vector<int32_t> ur_off(1, 0), list_idx;
+        std::vector<int64_t> list_off(1, 0);
+        std::vector<uint8_t> chk(nk, check ? 1 : 0);
+        for (size_t k = 0; k < nk; ++k) {
+            KF* pKF = vpKFs[k];
+            const float kk[5] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf};
+            K.insert(K.end(), kk, kk + 5);
+            ur.insert(ur.end(), pKF->mvuRight.begin(), pKF->mvuRight.begin() + fr[k].n);
+            ur_off.push_back((int32_t)ur.size());
+            for (size_t l = 0; l < pKF->mvInvLevelSigma2.size() && l < 16; ++l) inv[16 * k + l] = pKF->mvInvLevelSigma2[l];
+            list_idx.insert(list_idx.end(), lists[k].begin(), lists[k].end());
+            list_off.push_back((int64_t)list_idx.size());
+        }
+        ur.push_back(0.f); list_idx.push_back(0);                                    // data() of an empty vector may be null
+        qsp_fuse_in in;
+        in.n_target = (int32_t)nk; in.target = fr.data(); in.K = K.data(); in.Ow = Ow.data(); in.th = vth.data();
+        in.u_right_off = ur_off.data(); in.u_right = ur.data(); in.inv_level_sigma2 = inv.data(); in.check_reprojection = chk.data();
+        in.n_point = (int32_t)vpPoints.size(); in.Xw = p.Xw.data(); in.normal = p.normal.data(); in.dist_min_inv = p.dmin.data();
+        in.dist_max_inv = p.dmaxi.data(); in.dist_max = p.dmax.data(); in.desc = p.desc.data();
+        in.list_off = list_off.data(); in.list_idx = list_idx.data();
+        std::vector<int32_t> bi(list_idx.size()), bd(list_idx.size());
+        qsp_fuse_out out;
+        out.best_idx = bi.data(); out.best_dist = bd.data(); out.reason = out.level = nullptr;
+        const int rc = qsp_shim::report("qsp_fuse_batch", qsp_fuse_batch(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        best.assign(nk, std::vector<int32_t>());
+        for (size_t k = 0; k < nk; ++k) best[k].assign(bi.begin() + list_off[k], bi.begin() + list_off[k + 1]);
+        return QSP_OK;
+    }
+
+public:
+    // ORBmatcher::Fuse(vpTargetKFs[k], vpMapPoints, th) (src/ORBmatcher.cc:825-975) for ALL targets of LocalMapping::SearchInNeighbors
+    // in one library call; with one target, the call back into the current key frame (LocalMapping.cc:690).  vnFused[k]: its return
+    // value.  The match phase runs on the device against ONE snapshot of the points (taken here, with the reference's getters); a
+    // target lists the points that are non-null, not bad and not IsInKeyFrame(target).  The action phase (:952-971) is then
+    // replayed here, target by target and point by point in the reference's order, on the LIVE map: isBad() and IsInKeyFrame are
+    // tested again when the pair is visited (an earlier Replace only ever turns a listed pair into a skipped one: it marks the
+    // dying point bad and only adds observations to the survivor), and GetMapPoint(bestIdx) is the slot as it is THEN.
+    // One deviation: a point that survives a Replace gets a new descriptor in the reference (ComputeDistinctiveDescriptors inside
+    // Replace) and later targets match it with that; here they were matched with the snapshot's.  *n_stale counts the pairs visited
+    // for such a point, matched or not; they are not matched again.
+    // Returns the qsp status; on error the map and vnFused have not been touched.
+    template <typename KF, typename MP>
+    static int FuseBatch(const std::vector<KF*>& vpTargetKFs, const std::vector<MP*>& vpMapPoints, const float th, std::vector<int>& vnFused,
+                         int* n_stale = nullptr) {
+        const size_t nk = vpTargetKFs.size();
+        if (nk == 0) { vnFused.clear(); if (n_stale) *n_stale = 0; return QSP_OK; }
+        PoolArrays p;
+        gather_pool(vpMapPoints, p);
+        std::vector<FrameArrays> fa(nk);
+        std::vector<qsp_orb_frame> fr(nk);
+        std::vector<float> Ow(3 * nk);
+        std::vector<std::vector<int32_t>> lists(nk), best;
+        for (size_t k = 0; k < nk; ++k) {
+            KF* pKF = vpTargetKFs[k];
+            gather(pKF, std::vector<MP*>(pKF->mvKeysUn.size(), static_cast<MP*>(NULL)), fa[k], fr[k]);
+            const cv::Mat O = pKF->GetCameraCenter();                                // :836
+            for (int r = 0; r < 3; ++r) Ow[3 * k + r] = O.template at<float>(r);
+            for (size_t i = 0; i < vpMapPoints.size(); ++i)
+                if (p.ok[i] && !vpMapPoints[i]->IsInKeyFrame(pKF)) lists[k].push_back((int32_t)i);               // :846-850
+        }
+        const int rc = fuse_call(vpTargetKFs, fr, Ow, true, th, vpMapPoints, p, lists, best);
+        if (rc != QSP_OK) return rc;
+        vnFused.assign(nk, 0);
+        std::set<MP*> survived;
+        int stale = 0;
+        for (size_t k = 0; k < nk; ++k) {
+            KF* pKF = vpTargetKFs[k];
+            for (size_t a = 0; a < lists[k].size(); ++a) {
+                MP* pMP = vpMapPoints[lists[k][a]];
+                if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;                // :849, live
+                if (survived.count(pMP)) ++stale;
+                const int32_t bestIdx = best[k][a];
+                if (bestIdx < 0) continue;
+                MP* pMPinKF = pKF->GetMapPoint(bestIdx);                             // :954-970
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) {
+                        if (pMPinKF->Observations() > pMP->Observations()) { pMP->Replace(pMPinKF); survived.insert(pMPinKF); }
+                        else { pMPinKF->Replace(pMP); survived.insert(pMP); }
+                    }
+                } else {
+                    pMP->AddObservation(pKF, bestIdx);
+                    pKF->AddMapPoint(pMP, bestIdx);
+                }
+                vnFused[k]++;
+            }
+        }
+        if (n_stale) *n_stale = stale;
+        return QSP_OK;
+    }
+
+    // ORBmatcher::Fuse(vpKFs[k], vScw[k], vpPoints, th, vvpReplacePoints[k]) (src/ORBmatcher.cc:977-1100) for ALL corrected key frames
+    // of LoopClosing::SearchAndFuse in one library call.  vvpReplacePoints[k] comes back as the reference fills a vector of
+    // vpPoints.size() NULLs; the Replace under the map mutex stays the caller's: after_target(k) is called when target k has been
+    // replayed, and the caller puts its block (LoopClosing.cc:612-626) there, so that later targets see it.  Rcw = sRcw / scw,
+    // tcw / scw and Ow = -Rcw.t() * tcw are formed as cv::Mat forms them for CV_32F: the row dot product and the 3x3 products summed
+    // in double and rounded once, the division as a multiplication by 1.0 / scw rounded to float32.  A target lists the points that
+    // are non-null, not bad and not in GetMapPoints() of the target; at replay isBad() and the membership (GetMapPoints() as it is
+    // when the target's turn comes, :993) are tested again and GetMapPoint(bestIdx) is the slot as it is then.  *n_stale counts the
+    // pairs visited for a point that an earlier target of this call named as a replacement (it survives the caller's Replace with
+    // a new descriptor in the reference).  Returns the qsp status; on error nothing has been touched and after_target is not called.
+    template <typename KF, typename MP>
+    static int FuseBatch(const std::vector<KF*>& vpKFs, const std::vector<cv::Mat>& vScw, const std::vector<MP*>& vpPoints, const float th,
+                         std::vector<std::vector<MP*>>& vvpReplacePoints, std::vector<int>& vnFused,
+                         const std::function<void(size_t)>& after_target = std::function<void(size_t)>(), int* n_stale = nullptr) {
+        const size_t nk = vpKFs.size();
+        if (vScw.size() != nk) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::FuseBatch: %zu key frames, but %zu Sim3\n", nk, vScw.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nk == 0) { vvpReplacePoints.clear(); vnFused.clear(); if (n_stale) *n_stale = 0; return QSP_OK; }
+        PoolArrays p;
+        gather_pool(vpPoints, p);
+        std::vector<FrameArrays> fa(nk);
+        std::vector<qsp_orb_frame> fr(nk);
+        std::vector<float> Ow(3 * nk);
+        std::vector<std::vector<int32_t>> lists(nk), best;
+        for (size_t k = 0; k < nk; ++k) {
+            KF* pKF = vpKFs[k];
+            gather(pKF, std::vector<MP*>(pKF->mvKeysUn.size(), static_cast<MP*>(NULL)), fa[k], fr[k]);
+            const cv::Mat& S = vScw[k];                                              // :986-990
+            double dot = 0.0;
+            for (int c = 0; c < 3; ++c) dot += (double)S.template at<float>(0, c) * (double)S.template at<float>(0, c);
+            const float scw = (float)std::sqrt(dot);
+            const float inv = (float)(1.0 / (double)scw);
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) fr[k].Rcw[3 * r + c] = S.template at<float>(r, c) * inv;
+                fr[k].tcw[r] = S.template at<float>(r, 3) * inv;
+            }
+            for (int r = 0; r < 3; ++r) {
+                double s = 0.0;
+                for (int q = 0; q < 3; ++q) s += (double)fr[k].Rcw[3 * q + r] * (double)fr[k].tcw[q];
+                Ow[3 * k + r] = (float)(-s);
+            }
+            const std::set<MP*> spAlreadyFound = pKF->GetMapPoints();                // :993
+            for (size_t i = 0; i < vpPoints.size(); ++i)
+                if (p.ok[i] && !spAlreadyFound.count(vpPoints[i])) lists[k].push_back((int32_t)i);               // :1005
+        }
+        const int rc = fuse_call(vpKFs, fr, Ow, false, th, vpPoints, p, lists, best);
+        if (rc != QSP_OK) return rc;
+        vvpReplacePoints.assign(nk, std::vector<MP*>(vpPoints.size(), static_cast<MP*>(NULL)));
+        vnFused.assign(nk, 0);
+        std::vector<uint8_t> survived(vpPoints.size() + 1, 0);
+        int stale = 0;
+        for (size_t k = 0; k < nk; ++k) {
+            KF* pKF = vpKFs[k];
+            const std::set<MP*> spAlreadyFound = pKF->GetMapPoints();                // live: what Fuse would find when called now
+            for (size_t a = 0; a < lists[k].size(); ++a) {
+                const size_t iMP = (size_t)lists[k][a];
+                MP* pMP = vpPoints[iMP];
+                if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
+                if (survived[iMP]) ++stale;
+                const int32_t bestIdx = best[k][a];
+                if (bestIdx < 0) continue;
+                MP* pMPinKF = pKF->GetMapPoint(bestIdx);                             // :1084-1095
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) { vvpReplacePoints[k][iMP] = pMPinKF; survived[iMP] = 1; }
+                } else {
+                    pMP->AddObservation(pKF, bestIdx);
+                    pKF->AddMapPoint(pMP, bestIdx);
+                }
+                vnFused[k]++;
+            }
+            if (after_target) after_target(k);
+        }
+        if (n_stale) *n_stale = stale;
         return QSP_OK;
     }
 };

@@ -159,6 +159,17 @@ class SearchTriOut(C.Structure):
     _fields_ = SearchBowOut._fields_
 
 
+class FuseIn(C.Structure):
+    _fields_ = [("n_target", C.c_int32), ("target", C.POINTER(OrbFrame)), ("K", c_float_p), ("Ow", c_float_p), ("th", c_float_p),
+                ("u_right_off", c_int32_p), ("u_right", c_float_p), ("inv_level_sigma2", c_float_p), ("check_reprojection", c_uint8_p),
+                ("n_point", C.c_int32), ("Xw", c_float_p), ("normal", c_float_p), ("dist_min_inv", c_float_p), ("dist_max_inv", c_float_p),
+                ("dist_max", c_float_p), ("desc", c_uint8_p), ("list_off", C.POINTER(C.c_int64)), ("list_idx", c_int32_p)]
+
+
+class FuseOut(C.Structure):
+    _fields_ = [("best_idx", c_int32_p), ("best_dist", c_int32_p), ("reason", c_int32_p), ("level", c_int32_p)]
+
+
 SYMBOLS = [
     "qsp_last_error", "qsp_version", "qsp_device_count",
     "qsp_decoder_create", "qsp_decoder_destroy", "qsp_decoder_set_option", "qsp_decoder_get_counter", "qsp_decode_sdf",
@@ -173,7 +184,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_fuse_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -269,6 +280,7 @@ def lib():
     L.qsp_search_by_sim3_batch.argtypes = [C.c_int, C.POINTER(SearchSim3In), C.POINTER(SearchSim3Out)]
     L.qsp_search_by_bow_batch.argtypes = [C.c_int, C.POINTER(SearchBowIn), C.POINTER(SearchBowOut)]
     L.qsp_search_for_triangulation_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(SearchTriOut)]
+    L.qsp_fuse_batch.argtypes = [C.c_int, C.POINTER(FuseIn), C.POINTER(FuseOut)]
     L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]

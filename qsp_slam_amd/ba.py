@@ -520,6 +520,86 @@ def search_for_triangulation_batch(shared, cands, F12, exy, th=50, only_stereo=F
     return res
 
 
+def _fuse_target(f, keep):
+    """qsp_orb_frame over what qsp_fuse_batch reads of a target dict (the map-point fields stay NULL)"""
+    n = int(np.size(f["octave"]))
+    a = dict(kp=_arr(np.reshape(f["kp"], (-1, 2)), np.float32), octave=_arr(np.reshape(f["octave"], -1), np.int32),
+             desc=_arr(np.reshape(f["desc"], (-1, 32)), np.uint8), sf=_arr(np.reshape(f["scale_factors"], -1), np.float32))
+    for key, w in (("kp", 2), ("desc", 32), ("u_right", 1)):
+        if int(np.size(f[key])) != w * n:
+            raise ValueError("fuse_batch: %s does not hold %d values per key point" % (key, w))
+    keep.append(a)
+    o = _lib.OrbFrame()
+    o.n = n
+    o.kp, o.octave, o.desc = _lib.fptr(a["kp"]), _lib.i32ptr(a["octave"]), _lib.u8ptr(a["desc"])
+    o.min_x, o.max_x, o.min_y, o.max_y = [float(v) for v in f["bounds"]]
+    o.grid_cols, o.grid_rows = int(f["grid"][0]), int(f["grid"][1])
+    o.grid_w_inv, o.grid_h_inv = float(f["grid"][2]), float(f["grid"][3])
+    o.n_levels, o.log_scale, o.scale_factors = int(np.size(f["scale_factors"])), float(f["log_scale"]), _lib.fptr(a["sf"])
+    o.Rcw[:] = [float(v) for v in np.reshape(f["Rcw"], 9)]
+    o.tcw[:] = [float(v) for v in np.reshape(f["tcw"], 3)]
+    return o
+
+
+def _fuse_in(targets, pool):
+    """the qsp_fuse_in of fuse_batch, with `keep` (what its pointers point into, by name) and the pairs' offsets per target"""
+    nt = len(targets)
+    keep = []
+    fr = (_lib.OrbFrame * nt)(*[_fuse_target(t, keep) for t in targets])
+    a = dict(K=_arr(np.stack([np.asarray(t["K"], np.float32).reshape(5) for t in targets]), np.float32),
+             Ow=_arr(np.stack([np.asarray(t["Ow"], np.float32).reshape(3) for t in targets]), np.float32),
+             th=_arr([t["th"] for t in targets], np.float32),
+             u_right_off=_arr(np.concatenate([[0], np.cumsum([fr[k].n for k in range(nt)])]), np.int32),
+             u_right=_arr(np.concatenate([np.reshape(t["u_right"], -1) for t in targets] + [np.zeros(1)]), np.float32),
+             inv_level_sigma2=np.zeros((nt, 16), np.float32),
+             check_reprojection=_arr([1 if t["check"] else 0 for t in targets], np.uint8),
+             Xw=_arr(np.reshape(pool["Xw"], (-1, 3)), np.float32), normal=_arr(np.reshape(pool["normal"], (-1, 3)), np.float32),
+             dist_min_inv=_arr(np.reshape(pool["dist_min_inv"], -1), np.float32), dist_max_inv=_arr(np.reshape(pool["dist_max_inv"], -1), np.float32),
+             dist_max=_arr(np.reshape(pool["dist_max"], -1), np.float32), desc=_arr(np.reshape(pool["desc"], (-1, 32)), np.uint8),
+             list_off=_arr(np.concatenate([[0], np.cumsum([np.size(t["list"]) for t in targets])]), np.int64),
+             list_idx=_arr(np.concatenate([np.reshape(t["list"], -1) for t in targets] + [np.zeros(1)]), np.int32))
+    n_point = int(np.size(pool["dist_max"]))
+    for key, w in (("Xw", 3), ("normal", 3), ("dist_min_inv", 1), ("dist_max_inv", 1), ("desc", 32)):
+        if int(np.size(pool[key])) != w * n_point:
+            raise ValueError("fuse_batch: the pool's %s does not hold %d values per point" % (key, w))
+    for k, t in enumerate(targets):
+        s = np.asarray(t["inv_level_sigma2"], np.float32).reshape(-1)
+        if len(s) != fr[k].n_levels or len(s) > 16:
+            raise ValueError("fuse_batch: inv_level_sigma2 holds one value per level, at most 16")
+        a["inv_level_sigma2"][k, :len(s)] = s
+    keep.append(a)
+    i = _lib.FuseIn(nt, fr, _lib.fptr(a["K"]), _lib.fptr(a["Ow"]), _lib.fptr(a["th"]), _lib.i32ptr(a["u_right_off"]), _lib.fptr(a["u_right"]),
+                    _lib.fptr(a["inv_level_sigma2"]), _lib.u8ptr(a["check_reprojection"]), n_point, _lib.fptr(a["Xw"]), _lib.fptr(a["normal"]),
+                    _lib.fptr(a["dist_min_inv"]), _lib.fptr(a["dist_max_inv"]), _lib.fptr(a["dist_max"]), _lib.u8ptr(a["desc"]),
+                    a["list_off"].ctypes.data_as(C.POINTER(C.c_int64)), _lib.i32ptr(a["list_idx"]))
+    return i, keep, a["list_off"]
+
+
+def fuse_batch(targets, pool, tap=False, device=0):
+    """The match phase of both ORBmatcher::Fuse overloads (reference src/ORBmatcher.cc:825-975 and :977-1100) for every target key
+    frame in ONE call (qsp_fuse_batch, include/qsp_hip.h).  `pool`: the map points all targets share, a dict of Xw (n,3), normal
+    (n,3), dist_min_inv, dist_max_inv, dist_max (n,) and desc (n,32) uint8.  `targets`: list of dicts with kp (n,2), octave (n,),
+    desc (n,32) uint8, bounds (min_x, max_x, min_y, max_y), grid (cols, rows, width_inv, height_inv), log_scale, scale_factors
+    (n_levels,), Rcw (3,3), tcw (3,), K (5,) fx fy cx cy mbf, Ow (3,), th, u_right (n,), inv_level_sigma2 (n_levels,), check
+    (True: the pose overload's reprojection test; False: the Sim3 overload) and list: the pool indices the target searches, in
+    order.  Returns one dict per target: best_idx, best_dist (len(list),) int32 (-1 = none) and, with tap=True, reason and level."""
+    nt = len(targets)
+    if nt == 0:
+        return []
+    i, keep, off = _fuse_in(targets, pool)
+    n_pair = int(off[-1])
+    best, dist, why, lvl = (np.full(max(n_pair, 1), -1, np.int32) for _ in range(4))
+    o = _lib.FuseOut(_lib.i32ptr(best), _lib.i32ptr(dist), *([_lib.i32ptr(why), _lib.i32ptr(lvl)] if tap else [None, None]))
+    _lib.check(_lib.lib().qsp_fuse_batch(int(device), C.byref(i), C.byref(o)))
+    res = []
+    for k in range(nt):
+        r = dict(best_idx=best[off[k]:off[k + 1]].copy(), best_dist=dist[off[k]:off[k + 1]].copy())
+        if tap:
+            r.update(reason=why[off[k]:off[k + 1]].copy(), level=lvl[off[k]:off[k + 1]].copy())
+        res.append(r)
+    return res
+
+
 def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
                              device=0):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map
