@@ -1094,6 +1094,81 @@ typedef struct {
 } qsp_fuse_out;
 int qsp_fuse_batch(int device, const qsp_fuse_in* in, qsp_fuse_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The numeric part of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:467-607, KeyFrame::UnprojectStereo src/KeyFrame.cc:
+ * 616-632) for every covisible neighbour in ONE call: qsp_triangulate_batch on a match grid the caller holds, and
+ * qsp_create_new_map_points_batch, which runs qsp_search_for_triangulation_batch's two launches and then the two of the
+ * triangulation in one staging block (one upload, one download; the match grid stays on the device in between).
+ * match is qsp_search_tri_out.match: (n_cand, kf1->n) int32, per slot of key frame 1 the neighbour's index idx2 or -1.  A frame
+ * is a qsp_triangulate_frame: GetRotation, GetTranslation, GetCameraCenter, fx fy cx cy invfx invfy mb mbf and per slot
+ * mvKeysUn[i].pt, mvKeys[i].pt (the DISTORTED point: what UnprojectStereo reads), mvuRight, mvDepth and mvLevelSigma2 /
+ * mvScaleFactors gathered through mvKeysUn[i].octave.  ratio_factor is 1.5f * mfScaleFactor of key frame 1.
+ * Per slot (k, idx1) with idx2 >= 0, one lane, in the reference's arithmetic -- float32 one IEEE operation at a time; a CV_32F
+ * matrix product row (Rwc * xn, Rwc * x3Dc) summed in double and rounded once, the camera centre then added in float32 (the
+ * project's convention for cv::Mat products; whether OpenCV folds UnprojectStereo's product and sum into one rounding is not
+ * verified: INTEGRATION.md lists it under the deviations); Mat::dot
+ * and cv::norm in double, so z = (float)(Rcw.row(2).dot(x3D) + (double)tcw[2]) (x, y alike) and cosParallaxRays =
+ * (float)(dot / (norm1 * norm2)); invz = (float)(1.0 / z); u = fx * x * invz + cx left to right; a float32 quotient correctly
+ * rounded; compares against 5.991 * sigma2, 7.8 * sigma2 and 0.9998 in double; cos(2 * atan2(mb / 2, depth)) with each function
+ * evaluated in double and rounded to float32 (within one ulp of a float libm):
+ *   stereo1 = mvuRight1 >= 0, stereo2 alike; cosParallaxStereo1 is formed when stereo1, cosParallaxStereo2 only when !stereo1 &&
+ *   stereo2 (the reference's `else if`), either is cosParallaxRays + 1 otherwise;
+ *   path 1 (SVD) when cosRays < min(stereo cosines) && cosRays > 0 && (stereo1 || stereo2 || cosRays < 0.9998): A (4x4) is formed
+ *   in float32 (xn[0] * Tcw.row(2) - Tcw.row(0), ...: one multiply and one subtract per entry); the right singular vector v of its
+ *   smallest singular value is computed in FP64 by a one-sided Jacobi iteration (at most 30 sweeps, ended by a sweep without a
+ *   rotation); refused when (float)v[3] == 0, else x3D[i] = (float)(v[i] / v[3]).  OpenCV's float32 SVD is NOT restated bit for
+ *   bit: the FP64 null vector of the same float32 A lies inside the reference's own rounding noise;
+ *   path 2 when stereo1 && cos1 < cos2: x3D = KeyFrame 1's UnprojectStereo(idx1); path 3 when stereo2 && cos2 < cos1: key frame
+ *   2's; mvDepth <= 0 there refuses the pair (reason 10: the reference would go on with an empty Mat); else path 0, reason 2;
+ *   then z1 <= 0, z2 <= 0, the reprojection error in key frame 1 (mono: ex*ex + ey*ey > 5.991 * sigma2; stereo: + er*er > 7.8 *
+ *   sigma2 with u_r = u - mbf * invz) and in key frame 2, where u_r subtracts KEY FRAME 1's mbf (:582, kept), dist1 == 0 ||
+ *   dist2 == 0, and ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor.
+ * accept[k][idx1] = the pair passes every gate.  first[k][idx1] = it passes and no neighbour k' < k has an accepted pair at idx1:
+ * the points the reference creates (an earlier neighbour's point fills the slot, which then no longer matches).  x3D is the
+ * point wherever one was formed, zeros elsewhere; n_new[k] counts first[k].  reason: 0 accepted, 1 no match, 2 low parallax and no
+ * usable stereo, 3 w == 0, 4 z1 <= 0, 5 z2 <= 0, 6 reprojection in key frame 1, 7 in key frame 2, 8 a zero distance, 9 scale
+ * ratio, 10 UnprojectStereo on mvDepth <= 0.  path: 0 none, 1 SVD, 2 / 3 UnprojectStereo of key frame 1 / 2.  cos_rays for every
+ * matched slot; z (z1, z2), err2 (both sums) and ratio_dist hold each value once the pair reached it, else 0.
+ * Non-finite values are not refused: the IEEE compares decide.  A slot's outputs have the same bits alone, in any batch and at
+ * any position; `first` and n_new are defined over the batch.  Host pointers.  n_cand == 0 is QSP_OK and touches nothing.
+ * QSP_ERR_INVALID: null required pointers (arrays of a frame with n == 0 may be NULL; every tap may be NULL), negative sizes, a
+ * match index outside [-1, kf2[k].n); for the chained call also what qsp_search_for_triangulation_batch refuses and a frame whose
+ * key-point count differs between the two inputs.  More than 2^31 - 1 slots (n_cand * kf1->n, or key points) in one call:
+ * QSP_ERR_UNSUPPORTED.  No output is written unless the call returns QSP_OK. */
+typedef struct {
+    int32_t n;                    /* key points */
+    float Rcw[9], tcw[3], Ow[3];  /* GetRotation (row-major), GetTranslation, GetCameraCenter */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    const float* xy_un;           /* (n,2) mvKeysUn[i].pt */
+    const float* xy;              /* (n,2) mvKeys[i].pt */
+    const float* u_right;         /* (n) mvuRight */
+    const float* depth;           /* (n) mvDepth */
+    const float* sigma2;          /* (n) mvLevelSigma2[mvKeysUn[i].octave] */
+    const float* scale;           /* (n) mvScaleFactors[mvKeysUn[i].octave] */
+} qsp_triangulate_frame;
+typedef struct {
+    int32_t n_cand;
+    const qsp_triangulate_frame* kf1;     /* one */
+    const qsp_triangulate_frame* kf2;     /* (n_cand) */
+    float ratio_factor;                   /* 1.5f * kf1's mfScaleFactor */
+} qsp_triangulate_geom;
+typedef struct {
+    uint8_t* accept;              /* (n_cand,kf1->n) */
+    uint8_t* first;               /* (n_cand,kf1->n) */
+    float* x3D;                   /* (n_cand,kf1->n,3) */
+    int32_t* n_new;               /* (n_cand) */
+    /* the tests' taps, each may be NULL */
+    int32_t* reason;              /* (n_cand,kf1->n) */
+    int32_t* path;                /* (n_cand,kf1->n) */
+    float* cos_rays;              /* (n_cand,kf1->n) */
+    float* z;                     /* (n_cand,kf1->n,2) */
+    float* err2;                  /* (n_cand,kf1->n,2) */
+    float* ratio_dist;            /* (n_cand,kf1->n) */
+} qsp_triangulate_out;
+int qsp_triangulate_batch(int device, const qsp_triangulate_geom* geom, const int32_t* match, qsp_triangulate_out* out);
+int qsp_create_new_map_points_batch(int device, const qsp_search_tri_in* in, const qsp_triangulate_geom* geom, qsp_search_tri_out* search_out,
+                                    qsp_triangulate_out* out);
+
 #ifdef __cplusplus
 }
 #endif

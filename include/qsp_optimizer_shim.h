@@ -1244,32 +1244,30 @@ private:
         f.xy = a.xy.data(); f.stereo = a.stereo.data(); f.sigma2 = a.sigma2.data(); f.scale = a.scale.data();
     }
 
-public:
-    // ORBmatcher::SearchForTriangulation(pKF1, vpKF2[c], vF12[c], vvMatchedPairs[c], bOnlyStereo) (src/ORBmatcher.cc:657-823) for
-    // ALL kept neighbours of LocalMapping::CreateNewMapPoints in one library call: vvMatchedPairs[c] as the reference leaves it
-    // ((idx1, idx2) in ascending idx1), vnMatches[c] its return value.  vF12[c]: the caller's ComputeF12(pKF1, vpKF2[c]), CV_32F
-    // 3x3.  checkOri: the ORBmatcher's constructor argument (false in CreateNewMapPoints).  The map-point slots of every key frame
-    // are read ONCE (GetMapPointMatches()), where the reference reads each under GetMapPoint's lock as it visits it.
-    // Returns the qsp status; on error vvMatchedPairs and vnMatches have not been touched.
-    template <typename KF>
-    static int SearchForTriangulationBatch(KF* pKF1, const std::vector<KF*>& vpKF2, const std::vector<cv::Mat>& vF12, const bool bOnlyStereo,
-                                           const bool checkOri, std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs,
-                                           std::vector<int>& vnMatches) {
-        const size_t nc = vpKF2.size();
-        if (vF12.size() != nc) {
-            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::SearchForTriangulationBatch: %zu neighbours, but %zu fundamental matrices\n", nc,
-                         vF12.size());
-            return QSP_ERR_INVALID;
-        }
-        if (nc == 0) { vvMatchedPairs.clear(); vnMatches.clear(); return QSP_OK; }
+    struct SearchTriGather {             // everything a qsp_search_tri_in points into, and the struct itself
         TriArrays a1;
-        std::vector<TriArrays> a2(nc);
+        std::vector<TriArrays> a2;
         qsp_tri_frame f1;
-        std::vector<qsp_tri_frame> f2(nc);
+        std::vector<qsp_tri_frame> f2;
+        std::vector<float> F12, exy;
+        qsp_search_tri_in in;
+        size_t N1 = 0;
+    };
+    // The input of qsp_search_for_triangulation_batch for pKF1 against every vpKF2[c]: the frames, F12 and each neighbour's epipole
+    template <typename KF>
+    static void gather_search_tri(KF* pKF1, const std::vector<KF*>& vpKF2, const std::vector<cv::Mat>& vF12, const bool bOnlyStereo,
+                                  const bool checkOri, SearchTriGather& G) {
+        const size_t nc = vpKF2.size();
+        TriArrays& a1 = G.a1;
+        std::vector<TriArrays>& a2 = G.a2;
+        qsp_tri_frame& f1 = G.f1;
+        std::vector<qsp_tri_frame>& f2 = G.f2;
+        std::vector<float>&F12 = G.F12, &exy = G.exy;
+        a2.resize(nc); f2.resize(nc);
         const auto vpMapPoints1 = pKF1->GetMapPointMatches();
-        const size_t N1 = vpMapPoints1.size();
+        G.N1 = vpMapPoints1.size();
         gather_tri(pKF1, vpMapPoints1, a1, f1);
-        std::vector<float> F12(9 * nc), exy(2 * nc);
+        F12.assign(9 * nc, 0.f); exy.assign(2 * nc, 0.f);
         const cv::Mat Cw = pKF1->GetCameraCenter();                                  // :664
         for (size_t c = 0; c < nc; ++c) {
             KF* pKF2 = vpKF2[c];
@@ -1290,10 +1288,34 @@ public:
             exy[2 * c] = pKF2->fx * C2[0] * invz + pKF2->cx;
             exy[2 * c + 1] = pKF2->fy * C2[1] * invz + pKF2->cy;
         }
-        qsp_search_tri_in in;
+        qsp_search_tri_in& in = G.in;
         in.n_cand = (int32_t)nc; in.kf1 = &f1; in.kf2 = f2.data(); in.F12 = F12.data(); in.exy = exy.data();
         in.th = 50;                                                              // ORBmatcher::TH_LOW
         in.only_stereo = bOnlyStereo ? 1 : 0; in.check_orientation = checkOri ? 1 : 0;
+    }
+
+public:
+    // ORBmatcher::SearchForTriangulation(pKF1, vpKF2[c], vF12[c], vvMatchedPairs[c], bOnlyStereo) (src/ORBmatcher.cc:657-823) for
+    // ALL kept neighbours of LocalMapping::CreateNewMapPoints in one library call: vvMatchedPairs[c] as the reference leaves it
+    // ((idx1, idx2) in ascending idx1), vnMatches[c] its return value.  vF12[c]: the caller's ComputeF12(pKF1, vpKF2[c]), CV_32F
+    // 3x3.  checkOri: the ORBmatcher's constructor argument (false in CreateNewMapPoints).  The map-point slots of every key frame
+    // are read ONCE (GetMapPointMatches()), where the reference reads each under GetMapPoint's lock as it visits it.
+    // Returns the qsp status; on error vvMatchedPairs and vnMatches have not been touched.
+    template <typename KF>
+    static int SearchForTriangulationBatch(KF* pKF1, const std::vector<KF*>& vpKF2, const std::vector<cv::Mat>& vF12, const bool bOnlyStereo,
+                                           const bool checkOri, std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs,
+                                           std::vector<int>& vnMatches) {
+        const size_t nc = vpKF2.size();
+        if (vF12.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::SearchForTriangulationBatch: %zu neighbours, but %zu fundamental matrices\n", nc,
+                         vF12.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { vvMatchedPairs.clear(); vnMatches.clear(); return QSP_OK; }
+        SearchTriGather G;
+        gather_search_tri(pKF1, vpKF2, vF12, bOnlyStereo, checkOri, G);
+        const qsp_search_tri_in& in = G.in;
+        const size_t N1 = G.N1;
         std::vector<int32_t> match(nc * N1 + 1), n_matches(nc);
         qsp_search_tri_out out;
         out.match = match.data(); out.n_matches = n_matches.data();
@@ -1310,6 +1332,148 @@ public:
             }
             vnMatches[c] = n_matches[c];
         }
+        return QSP_OK;
+    }
+
+    struct NewPoint {                    // one map point LocalMapping::CreateNewMapPoints would create
+        size_t k, idx1, idx2;            // the neighbour (index into the kept list), the slot of key frame 1, the neighbour's slot
+        cv::Mat x3D;                     // 3x1 CV_32F
+    };
+
+private:
+    struct GeomArrays {                  // what a qsp_triangulate_frame points into
+        std::vector<float> xy_un, xy, u_right, depth, sigma2, scale;
+    };
+    // What :467-607 and KeyFrame::UnprojectStereo read of a key frame: the pose, the camera, and per slot mvKeysUn[i].pt, the
+    // DISTORTED mvKeys[i].pt, mvuRight, mvDepth and the level's sigma2 and scale factor through mvKeysUn[i].octave.
+    template <typename KF>
+    static void gather_geom(KF* pKF, const size_t n, GeomArrays& a, qsp_triangulate_frame& f) {
+        const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) f.Rcw[3 * r + c] = R.template at<float>(r, c);
+            f.tcw[r] = t.template at<float>(r);
+            f.Ow[r] = Ow.template at<float>(r);
+        }
+        f.fx = pKF->fx; f.fy = pKF->fy; f.cx = pKF->cx; f.cy = pKF->cy; f.invfx = pKF->invfx; f.invfy = pKF->invfy;
+        f.mb = pKF->mb; f.mbf = pKF->mbf;
+        a.xy_un.assign(2 * n + 1, 0.f); a.xy.assign(2 * n + 1, 0.f);
+        a.u_right.assign(n + 1, 0.f); a.depth.assign(n + 1, 0.f); a.sigma2.assign(n + 1, 0.f); a.scale.assign(n + 1, 0.f);
+        for (size_t i = 0; i < n; ++i) {
+            const auto& un = pKF->mvKeysUn[i];
+            a.xy_un[2 * i] = un.pt.x; a.xy_un[2 * i + 1] = un.pt.y;
+            a.xy[2 * i] = pKF->mvKeys[i].pt.x; a.xy[2 * i + 1] = pKF->mvKeys[i].pt.y;
+            a.u_right[i] = pKF->mvuRight[i];
+            a.depth[i] = pKF->mvDepth[i];
+            a.sigma2[i] = pKF->mvLevelSigma2[un.octave];
+            a.scale[i] = pKF->mvScaleFactors[un.octave];
+        }
+        f.n = (int32_t)n;
+        f.xy_un = a.xy_un.data(); f.xy = a.xy.data(); f.u_right = a.u_right.data(); f.depth = a.depth.data();
+        f.sigma2 = a.sigma2.data(); f.scale = a.scale.data();
+    }
+    struct GeomGather {
+        GeomArrays a1;
+        std::vector<GeomArrays> a2;
+        qsp_triangulate_frame f1;
+        std::vector<qsp_triangulate_frame> f2;
+        qsp_triangulate_geom geom;
+    };
+    template <typename KF>
+    static void gather_geometry(KF* pKF1, const std::vector<KF*>& vpKF2, GeomGather& G) {
+        const size_t nc = vpKF2.size();
+        G.a2.resize(nc); G.f2.resize(nc);
+        gather_geom(pKF1, pKF1->mvKeysUn.size(), G.a1, G.f1);
+        for (size_t c = 0; c < nc; ++c) gather_geom(vpKF2[c], vpKF2[c]->mvKeysUn.size(), G.a2[c], G.f2[c]);
+        G.geom.n_cand = (int32_t)nc; G.geom.kf1 = &G.f1; G.geom.kf2 = G.f2.data();
+        G.geom.ratio_factor = 1.5f * pKF1->mfScaleFactor;                        // :408
+    }
+    struct PointOutputs {                // the required outputs of a qsp_triangulate_out; the taps stay NULL
+        std::vector<uint8_t> accept, first;
+        std::vector<float> x3D;
+        std::vector<int32_t> n_new;
+        qsp_triangulate_out out;
+        PointOutputs(size_t nc, size_t N1) : accept(nc * N1 + 1), first(nc * N1 + 1), x3D(3 * nc * N1 + 1), n_new(nc + 1) {
+            out.accept = accept.data(); out.first = first.data(); out.x3D = x3D.data(); out.n_new = n_new.data();
+            out.reason = out.path = nullptr;
+            out.cos_rays = out.z = out.err2 = out.ratio_dist = nullptr;
+        }
+    };
+    // the `first` pairs, neighbour first, then ascending idx1: the order in which the reference creates the points
+    static void list_new_points(const PointOutputs& P, const int32_t* match, size_t nc, size_t N1, std::vector<NewPoint>& vNew) {
+        vNew.clear();
+        for (size_t k = 0; k < nc; ++k)
+            for (size_t i1 = 0; i1 < N1; ++i1) {
+                const size_t s = k * N1 + i1;
+                if (!P.first[s]) continue;
+                NewPoint p;
+                p.k = k; p.idx1 = i1; p.idx2 = (size_t)match[s];
+                p.x3D = cv::Mat(3, 1, CV_32F);
+                for (int r = 0; r < 3; ++r) p.x3D.template at<float>(r) = P.x3D[3 * s + r];
+                vNew.push_back(p);
+            }
+    }
+
+public:
+    // The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:441-607) for ALL kept neighbours in ONE library
+    // call: SearchForTriangulation, then parallax, triangulation, depth, reprojection and scale gates of every match, then the rule
+    // that the first accepted pair of a slot of key frame 1 creates its point.  vNew: the points the reference would create, in its
+    // order (neighbour first, then ascending idx1); the `new MapPoint(x3D, ...)` block (:610-625) stays the caller's.  vnMatches[k]:
+    // what SearchForTriangulation returns for neighbour k.  Arguments as for SearchForTriangulationBatch.
+    // Returns the qsp status; on error vNew and vnMatches have not been touched.
+    template <typename KF>
+    static int CreateNewMapPointsBatch(KF* pKF1, const std::vector<KF*>& vpKept, const std::vector<cv::Mat>& vF12, const bool bOnlyStereo,
+                                       const bool bCheckOrientation, std::vector<NewPoint>& vNew, std::vector<int>& vnMatches) {
+        const size_t nc = vpKept.size();
+        if (vF12.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::CreateNewMapPointsBatch: %zu neighbours, but %zu fundamental matrices\n", nc, vF12.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { vNew.clear(); vnMatches.clear(); return QSP_OK; }
+        SearchTriGather S;
+        gather_search_tri(pKF1, vpKept, vF12, bOnlyStereo, bCheckOrientation, S);
+        GeomGather G;
+        gather_geometry(pKF1, vpKept, G);
+        const size_t N1 = S.N1;
+        std::vector<int32_t> match(nc * N1 + 1), n_matches(nc);
+        qsp_search_tri_out sout;
+        sout.match = match.data(); sout.n_matches = n_matches.data();
+        sout.match_raw = sout.dist = sout.hist = sout.ind = nullptr;
+        PointOutputs P(nc, N1);
+        const int rc = qsp_shim::report("qsp_create_new_map_points_batch",
+                                        qsp_create_new_map_points_batch(OptimizerHip::device(), &S.in, &G.geom, &sout, &P.out));
+        if (rc != QSP_OK) return rc;
+        list_new_points(P, match.data(), nc, N1, vNew);
+        vnMatches.assign(n_matches.begin(), n_matches.end());
+        return QSP_OK;
+    }
+
+    // The same on matches the caller already holds (SearchForTriangulationBatch's vvMatchedIndices): one call of
+    // qsp_triangulate_batch.  A slot of key frame 1 that a neighbour lists twice keeps its last pair.
+    template <typename KF>
+    static int TriangulateBatch(KF* pKF1, const std::vector<KF*>& vpKept, const std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedIndices,
+                                std::vector<NewPoint>& vNew) {
+        const size_t nc = vpKept.size();
+        if (vvMatchedIndices.size() != nc) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::TriangulateBatch: %zu neighbours, but %zu match lists\n", nc, vvMatchedIndices.size());
+            return QSP_ERR_INVALID;
+        }
+        if (nc == 0) { vNew.clear(); return QSP_OK; }
+        GeomGather G;
+        gather_geometry(pKF1, vpKept, G);
+        const size_t N1 = (size_t)G.f1.n;
+        std::vector<int32_t> match(nc * N1 + 1, -1);
+        for (size_t k = 0; k < nc; ++k)
+            for (const auto& m : vvMatchedIndices[k]) {
+                if (m.first >= N1) {
+                    std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::TriangulateBatch: a match names slot %zu of %zu\n", m.first, N1);
+                    return QSP_ERR_INVALID;
+                }
+                match[k * N1 + m.first] = (int32_t)m.second;
+            }
+        PointOutputs P(nc, N1);
+        const int rc = qsp_shim::report("qsp_triangulate_batch", qsp_triangulate_batch(OptimizerHip::device(), &G.geom, match.data(), &P.out));
+        if (rc != QSP_OK) return rc;
+        list_new_points(P, match.data(), nc, N1, vNew);
         return QSP_OK;
     }
 

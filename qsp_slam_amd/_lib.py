@@ -170,6 +170,22 @@ class FuseOut(C.Structure):
     _fields_ = [("best_idx", c_int32_p), ("best_dist", c_int32_p), ("reason", c_int32_p), ("level", c_int32_p)]
 
 
+class TriangulateFrame(C.Structure):
+    _fields_ = [("n", C.c_int32), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
+                ("mb", C.c_float), ("mbf", C.c_float), ("xy_un", c_float_p), ("xy", c_float_p), ("u_right", c_float_p), ("depth", c_float_p),
+                ("sigma2", c_float_p), ("scale", c_float_p)]
+
+
+class TriangulateGeom(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("kf1", C.POINTER(TriangulateFrame)), ("kf2", C.POINTER(TriangulateFrame)), ("ratio_factor", C.c_float)]
+
+
+class TriangulateOut(C.Structure):
+    _fields_ = [("accept", c_uint8_p), ("first", c_uint8_p), ("x3D", c_float_p), ("n_new", c_int32_p), ("reason", c_int32_p), ("path", c_int32_p),
+                ("cos_rays", c_float_p), ("z", c_float_p), ("err2", c_float_p), ("ratio_dist", c_float_p)]
+
+
 SYMBOLS = [
     "qsp_last_error", "qsp_version", "qsp_device_count",
     "qsp_decoder_create", "qsp_decoder_destroy", "qsp_decoder_set_option", "qsp_decoder_get_counter", "qsp_decode_sdf",
@@ -184,7 +200,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_fuse_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_fuse_batch", "qsp_triangulate_batch", "qsp_create_new_map_points_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -281,6 +297,9 @@ def lib():
     L.qsp_search_by_bow_batch.argtypes = [C.c_int, C.POINTER(SearchBowIn), C.POINTER(SearchBowOut)]
     L.qsp_search_for_triangulation_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(SearchTriOut)]
     L.qsp_fuse_batch.argtypes = [C.c_int, C.POINTER(FuseIn), C.POINTER(FuseOut)]
+    L.qsp_triangulate_batch.argtypes = [C.c_int, C.POINTER(TriangulateGeom), c_int32_p, C.POINTER(TriangulateOut)]
+    L.qsp_create_new_map_points_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(TriangulateGeom), C.POINTER(SearchTriOut),
+                                                  C.POINTER(TriangulateOut)]
     L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]

@@ -600,6 +600,119 @@ def fuse_batch(targets, pool, tap=False, device=0):
     return res
 
 
+_TRI_POSE = (("Rcw", 9), ("tcw", 3), ("Ow", 3))
+_TRI_SCALARS = ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")
+_TRI_ARRAYS = (("xy", "xy_un", 2), ("xy_raw", "xy", 2), ("u_right", "u_right", 1), ("depth", "depth", 1), ("sigma2", "sigma2", 1),
+               ("scale", "scale", 1))           # (key of the frame dict, field of qsp_triangulate_frame, values per key point)
+_TRI_TAPS = (("reason", np.int32, 1), ("path", np.int32, 1), ("cos_rays", np.float32, 1), ("z", np.float32, 2), ("err2", np.float32, 2),
+             ("ratio_dist", np.float32, 1))
+
+
+def _triangulate_frame(f, keep):
+    """qsp_triangulate_frame over the geometry of a frame dict (triangulate_batch)"""
+    o = _lib.TriangulateFrame()
+    n = int(np.size(f["u_right"]))
+    o.n = n
+    for key, w in _TRI_POSE:
+        getattr(o, key)[:] = [float(v) for v in np.asarray(f[key], np.float32).reshape(w)]
+    for key in _TRI_SCALARS:
+        setattr(o, key, float(np.float32(f[key])))
+    a = {}
+    for key, field, w in _TRI_ARRAYS:
+        if int(np.size(f[key])) != w * n:
+            raise ValueError("triangulate_batch: %s does not hold %d values per key point" % (key, w))
+        a[key] = _arr(np.reshape(f[key], -1), np.float32)
+        setattr(o, field, _lib.fptr(a[key]))
+    keep.append(a)
+    return o
+
+
+def _triangulate_geom(kf1, kf2s, keep):
+    nc = len(kf2s)
+    f1 = _triangulate_frame(kf1, keep)
+    f2 = (_lib.TriangulateFrame * nc)(*[_triangulate_frame(c, keep) for c in kf2s])
+    keep += [f1, f2]
+    return _lib.TriangulateGeom(nc, C.pointer(f1), f2, float(np.float32(kf1["ratio_factor"])))
+
+
+def _triangulate_out(nc, n1, tap):
+    """the qsp_triangulate_out of one call and the arrays behind it"""
+    n = max(nc * n1, 1)
+    a = dict(accept=np.zeros(n, np.uint8), first=np.zeros(n, np.uint8), x3D=np.zeros(3 * n, np.float32), n_new=np.zeros(max(nc, 1), np.int32))
+    if tap:
+        a.update({key: np.zeros(w * n, dt) for key, dt, w in _TRI_TAPS})
+    o = _lib.TriangulateOut(_lib.u8ptr(a["accept"]), _lib.u8ptr(a["first"]), _lib.fptr(a["x3D"]), _lib.i32ptr(a["n_new"]))
+    if tap:
+        for key, dt, _ in _TRI_TAPS:
+            setattr(o, key, _lib.i32ptr(a[key]) if dt is np.int32 else _lib.fptr(a[key]))
+    return o, a
+
+
+def _triangulate_results(a, nc, n1, tap):
+    res = []
+    for k in range(nc):
+        s = slice(k * n1, (k + 1) * n1)
+        r = dict(accept=a["accept"][s].astype(bool), first=a["first"][s].astype(bool), x3D=a["x3D"].reshape(-1, 3)[s].copy(), n_new=int(a["n_new"][k]))
+        if tap:
+            r.update({key: a[key].reshape((-1, w) if w > 1 else (-1,))[s].copy() for key, _, w in _TRI_TAPS})
+        res.append(r)
+    return res
+
+
+def triangulate_batch(kf1, kf2s, match, tap=False, device=0):
+    """The numeric part of LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:467-607) for every covisible neighbour in
+    ONE call (qsp_triangulate_batch, include/qsp_hip.h).  A frame is a dict of Rcw (3,3), tcw (3,), Ow (3,), fx fy cx cy invfx invfy
+    mb mbf, and per key point xy (n,2) = mvKeysUn.pt (as in search_for_triangulation_batch), xy_raw (n,2) = mvKeys.pt, u_right, depth,
+    sigma2 and scale (n,), the last two
+    gathered through the octave; kf1 also holds ratio_factor = 1.5 * its mfScaleFactor.  `match` (n_cand, n1) int32 is the grid
+    search_for_triangulation_batch returns: per slot of kf1 the neighbour's index or -1.  Returns one dict per neighbour: accept and
+    first (n1,) bool -- first marks the points the reference would create --, x3D (n1,3), n_new and, with tap=True, reason, path,
+    cos_rays, z (n1,2), err2 (n1,2), ratio_dist."""
+    nc = len(kf2s)
+    if nc == 0:
+        return []
+    keep = []
+    g = _triangulate_geom(kf1, kf2s, keep)
+    n1 = int(g.kf1[0].n)
+    if int(np.size(match)) != nc * n1:
+        raise ValueError("triangulate_batch: match holds one entry per neighbour and key point of kf1")
+    m = _arr(np.reshape(match, -1), np.int32)
+    o, a = _triangulate_out(nc, n1, tap)
+    _lib.check(_lib.lib().qsp_triangulate_batch(int(device), C.byref(g), _lib.i32ptr(m), C.byref(o)))
+    return _triangulate_results(a, nc, n1, tap)
+
+
+def create_new_map_points_batch(shared, cands, F12, exy, th=50, only_stereo=False, check_orientation=False, tap=False, device=0):
+    """search_for_triangulation_batch followed by triangulate_batch in ONE call (qsp_create_new_map_points_batch): one upload, four
+    launches, one download; the match grid does not come back to the host in between.  Every frame dict holds what both calls
+    read.  Returns one dict per neighbour with the keys of both."""
+    nc = len(cands)
+    if nc == 0:
+        return []
+    keep = []
+    f1 = _tri_frame(shared, keep, False)
+    f2 = (_lib.TriFrame * nc)(*[_tri_frame(c, keep, True) for c in cands])
+    F = _arr(np.reshape(F12, (-1, 9)), np.float32)
+    e = _arr(np.reshape(exy, (-1, 2)), np.float32)
+    if len(F) != nc or len(e) != nc:
+        raise ValueError("create_new_map_points_batch: F12 and exy hold one entry per neighbour")
+    g = _triangulate_geom(shared, cands, keep)
+    n1 = int(f1.bow.n)
+    i = _lib.SearchTriIn(nc, C.pointer(f1), f2, _lib.fptr(F), _lib.fptr(e), int(th), 1 if only_stereo else 0, 1 if check_orientation else 0)
+    n_out = max(nc * n1, 1)
+    match, count = np.zeros(n_out, np.int32), np.zeros(nc, np.int32)
+    raw, dist, hist, ind = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32), np.zeros((nc, 30), np.int32), np.zeros((nc, 3), np.int32)
+    so = _lib.SearchTriOut(_lib.i32ptr(match), _lib.i32ptr(count), *([_lib.i32ptr(a) for a in (raw, dist, hist, ind)] if tap else [None] * 4))
+    o, a = _triangulate_out(nc, n1, tap)
+    _lib.check(_lib.lib().qsp_create_new_map_points_batch(int(device), C.byref(i), C.byref(g), C.byref(so), C.byref(o)))
+    res = _triangulate_results(a, nc, n1, tap)
+    for c, r in enumerate(res):
+        r.update(match=match[c * n1:(c + 1) * n1].copy(), n_matches=int(count[c]))
+        if tap:
+            r.update(match_raw=raw[c * n1:(c + 1) * n1].copy(), dist=dist[c * n1:(c + 1) * n1].copy(), hist=hist[c].copy(), ind=ind[c].copy())
+    return res
+
+
 def essential_graph_optimize(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, n_iter=20, lambda_init=1e-16, pts=None, pt_ref=None,
                              device=0):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:785-1048) from initializeOptimization() to the corrected map

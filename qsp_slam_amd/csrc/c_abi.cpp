@@ -1,5 +1,5 @@
 // c_abi.cpp -- library-wide C-ABI entry points (version, error text, device count), the buffer cache, and the one-shot batch calls:
-// the object map-point gate, Sim3 RANSAC, SearchBySim3, SearchByBoW, SearchForTriangulation, Fuse, the ellipsoid fits, OptimizeSim3 and the essential graph.  The
+// the object map-point gate, Sim3 RANSAC, SearchBySim3, SearchByBoW, SearchForTriangulation, the triangulation of CreateNewMapPoints, Fuse, the ellipsoid fits, OptimizeSim3 and the essential graph.  The
 // last launches the dense factorisation that ba_solver.hip defines, through dense_chol.hpp; nothing else here is the solver's.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 #include "search_triangulation.hpp"
 #include "sim3_opt.hpp"
 #include "sim3_ransac.hpp"
+#include "triangulate.hpp"
 
 namespace qsp {
 std::string& last_error_ref() {
