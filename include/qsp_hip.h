@@ -1169,6 +1169,100 @@ int qsp_triangulate_batch(int device, const qsp_triangulate_geom* geom, const in
 int qsp_create_new_map_points_batch(int device, const qsp_search_tri_in* in, const qsp_triangulate_geom* geom, qsp_search_tri_out* search_out,
                                     qsp_triangulate_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The tracking thread's projection searches, with the result of the reference's SERIAL loop:
+ *   mode 0, LOCAL: Frame::isInFrustum (src/Frame.cc:306-362) and ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&,
+ *                  th) (src/ORBmatcher.cc:45-129), what Tracking::SearchLocalPoints runs;
+ *   mode 1, LAST:  ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, th, bMono) (:1328-1470), what
+ *                  Tracking::TrackWithMotionModel runs.
+ * Sources are numbered in the reference's loop order.  Source i sees key-point slot idx as taken when slot_blocked[idx] (the slot
+ * held a point with Observations() > 0 before the call) or when an earlier source j < i with src_blocks[j] chose idx -- nothing
+ * else crosses between sources, so the loop is the unique fixed point of choice[i] = match(i; blocked = initial U {choice[j] : j <
+ * i, src_blocks[j]}).  It is iterated in parallel rounds (round 1 with the initial blocks only; round r with claim[idx] = the
+ * smallest blocking j that chose idx in round r - 1, an integer minimum) until a round repeats the choices of the one before:
+ * after round r the sources 0 .. r - 1 hold their serial values, so at most n_src + 1 rounds are needed; n_rounds reports them.
+ * The current frame is a qsp_orb_frame of which kp, octave, desc, the bounds and grid, n_levels, log_scale, scale_factors, Rcw and
+ * tcw are read (the map-point fields are not and may be NULL).
+ * Arithmetic, the reference's float32 one operation at a time: matrix rows summed in double and rounded once, t added in float32;
+ * PO = Xw - Ow in float32, cv::norm(PO) and PO.dot(Pn) in double; compares against double literals in double.
+ * LOCAL, per source with src_valid (the caller folds isBad() and "already matched in this frame" into it):
+ *   Pc = Rcw Xw + tcw; refuse PcZ < 0; invz = 1.0f / PcZ, u = fx * PcX * invz + cx (left to right), v likewise; refuse u < min_x ||
+ *   u > max_x, v likewise (closed at both ends); dist = (float)norm(PO), refuse dist < dist_min_inv || dist > dist_max_inv; viewCos =
+ *   (float)(PO.dot(Pn) / dist), refuse viewCos < view_cos_limit; level = clamp(ceil(logf(dist_max / dist) / log_scale), 0, n_levels -
+ *   1); proj_xr = u - mbf * invz.  These six are outputs (in_view = 0 and the rest 0 for a refused or invalid source).
+ *   r = viewCos > 0.998 ? 2.5f : 4.0f, times th only when th != 1.0; radius = r * scale_factors[level]; the area is
+ *   Frame::GetFeaturesInArea(u, v, radius, level - 1, level): a key point is in it when its own cell (round((x - min_x) *
+ *   grid_w_inv), round((y - min_y) * grid_h_inv)) lies in the grid and in the visited range, level - 1 <= octave <= level and |kx -
+ *   u| < radius && |ky - v| < radius (strict).  Of the area, blocked slots are skipped, and slots with u_right > 0 and |proj_xr -
+ *   u_right| > radius.  Best and second best are the two smallest (Hamming distance, traversal position (cell x, cell y, index))
+ *   of what remains, below 256.  The source is kept when dist <= 100 and not (level_best == level2 && (float)dist > nn_ratio *
+ *   (float)dist2).
+ * LAST, per source with src_valid (a point, and not mvbOutlier):
+ *   x3Dc = Rcw Xw + tcw; invzc = (float)(1.0 / z), refuse invzc < 0; u = fx * xc * invzc + cx; the same closed image test; radius =
+ *   th * scale_factors[src_octave]; with tlc = last_Rcw * (-Rcw^T tcw) + last_tcw: forward (tlc.z > mb && !mono) takes octave >=
+ *   src_octave, backward (-tlc.z > mb && !mono) octave <= src_octave, otherwise src_octave - 1 <= octave <= src_octave + 1; blocked
+ *   slots are skipped, and slots with u_right > 0 and |(u - mbf * invzc) - u_right| > radius.  Best only, kept when <= 100.  With
+ *   check_orientation: rot = src_angle - kp_angle[best], + 360 when negative, bin = round(rot * (1.0f / 30)), 30 becomes 0; the
+ *   30-bin histogram, ComputeThreeMaxima and the nulling of :1447-1467 follow.
+ * Where the reference would run into undefined behaviour or an assert the library does not follow it: a source whose u or v is
+ * NaN (it passes every reference compare and reaches (int)floor(NaN); z == +0 with xc == 0 is one way there), whose dist, viewCos
+ * or predicted level is NaN (dist == 0 among them), or whose radius is NaN ends with reason 6 and matches nothing; an infinite u
+ * or v is outside the image like any other; a Hamming distance of 256 never beats the reference's initial 256; a bin outside [0,
+ * 30) (a NaN or out-of-range angle) is reported as -1 and counted in no bin, so the match stays.
+ * reason: 0 matched, 1 !src_valid, 2 behind the camera, 3 outside the image, 4 distance limits, 5 viewing angle, 6 not finite, 7 no
+ * cell range or no key point in the area, 8 every key point of the area skipped, 9 best above 100, 10 refused by the ratio test.
+ * The action phase is index work on the host: the sources in order write slot_src[choice[i]] = i (the last writer stays) and are
+ * counted; with the orientation check every source of a bin outside the three maxima sets ITS slot to -2 -- also where a later
+ * source had over-written it, as the reference does -- and is subtracted.
+ * No floating-point atomics: a call's outputs have the same bits on every run.  Host pointers.  n_src == 0 is QSP_OK and touches
+ * nothing.  QSP_ERR_INVALID: null required pointers (arrays of a frame with n == 0 may be NULL; the arrays of the other mode and
+ * the taps may be NULL), negative counts, n > 2^26 or n_src > 2^26, n_levels outside [1, 16], a grid outside 1..64 x 1..64, a key point's octave or
+ * (LAST) a valid source's src_octave outside [0, n_levels), an unknown mode.  QSP_ERR_DEVICE with "internal error" in the
+ * text: the rounds did not settle within n_src + 1 (impossible by the argument above: a bug).  No output is written unless the call
+ * returns QSP_OK. */
+typedef struct {
+    int32_t mode;                         /* 0 LOCAL, 1 LAST */
+    const qsp_orb_frame* frame;           /* the current frame */
+    float K[5];                           /* fx fy cx cy mbf */
+    float Ow[3];                          /* mOw (LOCAL) */
+    float mb;                             /* (LAST) */
+    const float* u_right;                 /* (n) mvuRight */
+    const uint8_t* slot_blocked;          /* (n) 1 = mvpMapPoints[idx] && mvpMapPoints[idx]->Observations() > 0 at entry */
+    const float* kp_angle;                /* (n) mvKeysUn[idx].angle; LAST with check_orientation */
+    float th, nn_ratio, view_cos_limit;   /* nn_ratio and view_cos_limit: LOCAL */
+    int32_t check_orientation, mono;      /* LAST */
+    float last_Rcw[9], last_tcw[3];       /* LAST: the last frame's pose */
+    int32_t n_src;
+    const uint8_t* src_valid;             /* (n_src) */
+    const uint8_t* src_blocks;            /* (n_src) 1 = the source's point has Observations() > 0 */
+    const float* Xw;                      /* (n_src,3) GetWorldPos() */
+    const uint8_t* desc;                  /* (n_src,32) GetDescriptor() */
+    const float* normal;                  /* (n_src,3) GetNormal(); LOCAL */
+    const float* dist_min_inv;            /* (n_src) LOCAL */
+    const float* dist_max_inv;            /* (n_src) LOCAL */
+    const float* dist_max;                /* (n_src) mfMaxDistance; LOCAL */
+    const int32_t* src_octave;            /* (n_src) LastFrame.mvKeys[i].octave; LAST */
+    const float* src_angle;               /* (n_src) LastFrame.mvKeysUn[i].angle; LAST with check_orientation */
+} qsp_search_proj_in;
+typedef struct {
+    int32_t* choice;                      /* (n_src) the slot the source's point was written to, else -1 */
+    int32_t* dist;                        /* (n_src) the best distance, -1 where nothing was compared */
+    int32_t* slot_src;                    /* (n) the source whose point the slot holds at the end, -1 untouched, -2 nulled */
+    /* LOCAL: Frame::isInFrustum */
+    uint8_t* in_view;                     /* (n_src) mbTrackInView */
+    float *proj_x, *proj_y, *proj_xr;     /* (n_src) mTrackProjX, mTrackProjY, mTrackProjXR */
+    int32_t* level;                       /* (n_src) mnTrackScaleLevel */
+    float* view_cos;                      /* (n_src) mTrackViewCos */
+    /* the tests' taps, each may be NULL */
+    int32_t* reason;                      /* (n_src) */
+    int32_t *dist2, *level_best, *level2; /* (n_src) LOCAL: -1 where there is none */
+    int32_t* bin;                         /* (n_src) LAST with check_orientation: the histogram bin of a matched source, else -1 */
+    int32_t n_matches;                    /* as the reference counts: over-written writes included, histogram removals subtracted */
+    int32_t hist[30], ind[3];             /* LAST with check_orientation; else 0 and -1 */
+    int32_t n_rounds;
+} qsp_search_proj_out;
+int qsp_search_by_projection(int device, const qsp_search_proj_in* in, qsp_search_proj_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,11 @@
 #include "ObjectDetection.h"
 #endif
 
+#ifndef FRAME_GRID_COLS          // Frame.h of the reference defines both; a build against stand-in types may not
+#define FRAME_GRID_ROWS 48
+#define FRAME_GRID_COLS 64
+#endif
+
 namespace ORB_SLAM2 {
 namespace qsp_shim {
 
@@ -1676,6 +1681,160 @@ public:
             if (after_target) after_target(k);
         }
         if (n_stale) *n_stale = stale;
+        return QSP_OK;
+    }
+
+private:
+    struct ProjFrameArrays { std::vector<float> kp, sf, ur, angle; std::vector<int32_t> octave; std::vector<uint8_t> desc, blocked; };
+    // What both tracking searches read of the CURRENT frame, with the members the reference functions read (Frame.h): mvKeysUn,
+    // mDescriptors, the image bounds and grid, the pyramid, mTcw, fx fy cx cy mbf, mvuRight and, per slot, whether the point it
+    // holds has observations (src/ORBmatcher.cc:87-89 / :1403-1405).
+    template <typename FR>
+    static void gather_proj_frame(FR& F, ProjFrameArrays& a, qsp_orb_frame& f, qsp_search_proj_in& in) {
+        const int n = F.N;
+        a.kp.assign(2 * (size_t)n + 1, 0.f); a.octave.assign((size_t)n + 1, 0); a.desc.assign(32 * (size_t)n + 1, 0);
+        a.ur.assign((size_t)n + 1, 0.f); a.angle.assign((size_t)n + 1, 0.f); a.blocked.assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; ++i) {
+            a.kp[2 * i] = F.mvKeysUn[i].pt.x;
+            a.kp[2 * i + 1] = F.mvKeysUn[i].pt.y;
+            a.octave[i] = F.mvKeysUn[i].octave;
+            a.angle[i] = F.mvKeysUn[i].angle;
+            a.ur[i] = F.mvuRight[i];
+            const auto row = F.mDescriptors.row(i);
+            for (int b = 0; b < 32; ++b) a.desc[32 * (size_t)i + b] = row.template at<unsigned char>(0, b);
+            if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) a.blocked[i] = 1;
+        }
+        a.sf.assign(F.mvScaleFactors.begin(), F.mvScaleFactors.end());
+        a.sf.push_back(0.f);
+        f = qsp_orb_frame();
+        f.n = n;
+        f.kp = a.kp.data(); f.octave = a.octave.data(); f.desc = a.desc.data();
+        f.min_x = (float)F.mnMinX; f.max_x = (float)F.mnMaxX; f.min_y = (float)F.mnMinY; f.max_y = (float)F.mnMaxY;
+        f.grid_cols = FRAME_GRID_COLS; f.grid_rows = FRAME_GRID_ROWS;
+        f.grid_w_inv = F.mfGridElementWidthInv; f.grid_h_inv = F.mfGridElementHeightInv;
+        f.n_levels = F.mnScaleLevels; f.log_scale = F.mfLogScaleFactor; f.scale_factors = a.sf.data();
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) f.Rcw[3 * r + c] = F.mTcw.template at<float>(r, c);
+            f.tcw[r] = F.mTcw.template at<float>(r, 3);
+        }
+        in = qsp_search_proj_in();
+        in.frame = &f;
+        in.K[0] = F.fx; in.K[1] = F.fy; in.K[2] = F.cx; in.K[3] = F.cy; in.K[4] = F.mbf;
+        in.mb = F.mb;
+        in.u_right = a.ur.data(); in.slot_blocked = a.blocked.data(); in.kp_angle = a.angle.data();
+    }
+
+public:
+    // Frame::isInFrustum(pMP, viewCosLimit) for every local map point and ORBmatcher(nnratio).SearchByProjection(F, vpMapPoints, th)
+    // (src/Frame.cc:306-362, src/ORBmatcher.cc:45-129): the second loop of Tracking::SearchLocalPoints and its matcher call, in one
+    // library call with the serial loop's result.  A point is a source when it is non-null, not bad and not already matched in
+    // this frame (mnLastFrameSeen == F.mnId, set by the first loop of SearchLocalPoints, which stays with the caller).  On QSP_OK
+    // every source gets mbTrackInView and, where it is in view, mTrackProjX, mTrackProjXR, mTrackProjY, mnTrackScaleLevel,
+    // mTrackViewCos and IncreaseVisible() (Tracking.cc's `if(isInFrustum) IncreaseVisible`); F.mvpMapPoints[idx] =
+    // vpMapPoints[slot_src[idx]] for every slot the loop wrote; *n_matches is the reference's return value.  Returns the qsp
+    // status; on any other status neither the frame nor a point has been touched.
+    template <typename FR, typename MP>
+    static int SearchLocalPoints(FR& F, const std::vector<MP*>& vpMapPoints, const float th, const float nnratio, int* n_matches = nullptr,
+                                 const float viewCosLimit = 0.5f) {
+        const size_t ns = vpMapPoints.size();
+        if (n_matches) *n_matches = 0;
+        if (ns == 0) return QSP_OK;
+        ProjFrameArrays a;
+        qsp_orb_frame f;
+        qsp_search_proj_in in;
+        gather_proj_frame(F, a, f, in);
+        in.mode = 0; in.th = th; in.nn_ratio = nnratio; in.view_cos_limit = viewCosLimit; in.n_src = (int32_t)ns;
+        const cv::Mat Ow = F.GetCameraCenter();
+        for (int r = 0; r < 3; ++r) in.Ow[r] = Ow.template at<float>(r);
+        std::vector<uint8_t> valid(ns + 1, 0), blocks(ns + 1, 0), desc(32 * ns + 1, 0);
+        std::vector<float> Xw(3 * ns + 1, 0.f), nrm(3 * ns + 1, 0.f), dmin(ns + 1, 0.f), dmaxi(ns + 1, 0.f), dmax(ns + 1, 0.f);
+        for (size_t i = 0; i < ns; ++i) {
+            MP* pMP = vpMapPoints[i];
+            if (!pMP || pMP->mnLastFrameSeen == F.mnId || pMP->isBad()) continue;
+            valid[i] = 1;
+            blocks[i] = pMP->Observations() > 0 ? 1 : 0;
+            const cv::Mat X = pMP->GetWorldPos(), Pn = pMP->GetNormal();
+            for (int r = 0; r < 3; ++r) { Xw[3 * i + r] = X.template at<float>(r); nrm[3 * i + r] = Pn.template at<float>(r); }
+            dmin[i] = pMP->GetMinDistanceInvariance();
+            dmaxi[i] = pMP->GetMaxDistanceInvariance();
+            dmax[i] = dmaxi[i] / 1.2f;                                               // mfMaxDistance is protected, as in gather()
+            const auto d = pMP->GetDescriptor();
+            for (int b = 0; b < 32; ++b) desc[32 * i + b] = d.template at<unsigned char>(0, b);
+        }
+        in.src_valid = valid.data(); in.src_blocks = blocks.data(); in.Xw = Xw.data(); in.desc = desc.data(); in.normal = nrm.data();
+        in.dist_min_inv = dmin.data(); in.dist_max_inv = dmaxi.data(); in.dist_max = dmax.data();
+        std::vector<int32_t> choice(ns + 1), dist(ns + 1), level(ns + 1), slot((size_t)f.n + 1);
+        std::vector<uint8_t> view(ns + 1);
+        std::vector<float> px(ns + 1), py(ns + 1), pxr(ns + 1), vc(ns + 1);
+        qsp_search_proj_out out = qsp_search_proj_out();
+        out.choice = choice.data(); out.dist = dist.data(); out.slot_src = slot.data(); out.in_view = view.data();
+        out.proj_x = px.data(); out.proj_y = py.data(); out.proj_xr = pxr.data(); out.level = level.data(); out.view_cos = vc.data();
+        const int rc = qsp_shim::report("qsp_search_by_projection", qsp_search_by_projection(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        for (size_t i = 0; i < ns; ++i) {
+            if (!valid[i]) continue;
+            MP* pMP = vpMapPoints[i];
+            pMP->mbTrackInView = view[i] != 0;
+            if (!view[i]) continue;
+            pMP->mTrackProjX = px[i]; pMP->mTrackProjXR = pxr[i]; pMP->mTrackProjY = py[i];
+            pMP->mnTrackScaleLevel = level[i]; pMP->mTrackViewCos = vc[i];
+            pMP->IncreaseVisible();
+        }
+        for (int idx = 0; idx < f.n; ++idx)
+            if (slot[idx] >= 0) F.mvpMapPoints[idx] = vpMapPoints[slot[idx]];
+        if (n_matches) *n_matches = out.n_matches;
+        return QSP_OK;
+    }
+
+    // ORBmatcher(nnratio, checkOri).SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1328-1470), what
+    // Tracking::TrackWithMotionModel runs (and again with 2 * th after clearing the slots), in one library call with the serial
+    // loop's result.  Slot i of the last frame is a source when it holds a point and is no outlier; its octave is
+    // LastFrame.mvKeys[i].octave (:1378, the DISTORTED key point) and its angle LastFrame.mvKeysUn[i].angle (:1433).  On QSP_OK
+    // CurrentFrame.mvpMapPoints[idx] = LastFrame.mvpMapPoints[slot_src[idx]] where the loop wrote, NULL where the orientation
+    // check nulled; *n_matches is the reference's return value.  Returns the qsp status; on any other status the frame has not
+    // been touched.
+    template <typename FR>
+    static int SearchByProjection(FR& CurrentFrame, const FR& LastFrame, const float th, const bool bMono, const bool checkOri,
+                                  int* n_matches = nullptr) {
+        const size_t ns = (size_t)LastFrame.N;
+        if (n_matches) *n_matches = 0;
+        if (ns == 0) return QSP_OK;
+        ProjFrameArrays a;
+        qsp_orb_frame f;
+        qsp_search_proj_in in;
+        gather_proj_frame(CurrentFrame, a, f, in);
+        in.mode = 1; in.th = th; in.check_orientation = checkOri ? 1 : 0; in.mono = bMono ? 1 : 0; in.n_src = (int32_t)ns;
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) in.last_Rcw[3 * r + c] = LastFrame.mTcw.template at<float>(r, c);
+            in.last_tcw[r] = LastFrame.mTcw.template at<float>(r, 3);
+        }
+        std::vector<uint8_t> valid(ns + 1, 0), blocks(ns + 1, 0), desc(32 * ns + 1, 0);
+        std::vector<float> Xw(3 * ns + 1, 0.f), angle(ns + 1, 0.f);
+        std::vector<int32_t> octave(ns + 1, 0);
+        for (size_t i = 0; i < ns; ++i) {
+            auto* pMP = LastFrame.mvpMapPoints[i];
+            if (!pMP || LastFrame.mvbOutlier[i]) continue;
+            valid[i] = 1;
+            blocks[i] = pMP->Observations() > 0 ? 1 : 0;
+            const cv::Mat X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; ++r) Xw[3 * i + r] = X.template at<float>(r);
+            const auto d = pMP->GetDescriptor();
+            for (int b = 0; b < 32; ++b) desc[32 * i + b] = d.template at<unsigned char>(0, b);
+            octave[i] = LastFrame.mvKeys[i].octave;
+            angle[i] = LastFrame.mvKeysUn[i].angle;
+        }
+        in.src_valid = valid.data(); in.src_blocks = blocks.data(); in.Xw = Xw.data(); in.desc = desc.data();
+        in.src_octave = octave.data(); in.src_angle = angle.data();
+        std::vector<int32_t> choice(ns + 1), dist(ns + 1), slot((size_t)f.n + 1);
+        qsp_search_proj_out out = qsp_search_proj_out();
+        out.choice = choice.data(); out.dist = dist.data(); out.slot_src = slot.data();
+        const int rc = qsp_shim::report("qsp_search_by_projection", qsp_search_by_projection(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        for (int idx = 0; idx < f.n; ++idx) {
+            if (slot[idx] >= 0) CurrentFrame.mvpMapPoints[idx] = LastFrame.mvpMapPoints[slot[idx]];
+            else if (slot[idx] == -2) CurrentFrame.mvpMapPoints[idx] = nullptr;      // :1462
+        }
+        if (n_matches) *n_matches = out.n_matches;
         return QSP_OK;
     }
 };

@@ -600,6 +600,83 @@ def fuse_batch(targets, pool, tap=False, device=0):
     return res
 
 
+_PROJ_SRC = (("valid", "src_valid", np.uint8, 1), ("blocks", "src_blocks", np.uint8, 1), ("Xw", "Xw", np.float32, 3), ("desc", "desc", np.uint8, 32))
+_PROJ_SRC_MODE = ((("normal", "normal", np.float32, 3), ("dist_min_inv", "dist_min_inv", np.float32, 1), ("dist_max_inv", "dist_max_inv", np.float32, 1),
+                   ("dist_max", "dist_max", np.float32, 1)),
+                  (("octave", "src_octave", np.int32, 1), ("angle", "src_angle", np.float32, 1)))
+_PROJ_PTR = {np.uint8: _lib.u8ptr, np.float32: _lib.fptr, np.int32: _lib.i32ptr}
+_PROJ_OUT = (("choice", np.int32), ("dist", np.int32), ("in_view", np.uint8), ("proj_x", np.float32), ("proj_y", np.float32), ("proj_xr", np.float32),
+             ("level", np.int32), ("view_cos", np.float32), ("reason", np.int32), ("dist2", np.int32), ("level_best", np.int32),
+             ("level2", np.int32), ("bin", np.int32))            # per source; slot_src is per key point
+_PROJ_TAPS = ("reason", "dist2", "level_best", "level2", "bin")
+_PROJ_LOCAL = ("in_view", "proj_x", "proj_y", "proj_xr", "level", "view_cos", "dist2", "level_best", "level2")
+
+
+def _proj_in(frame, sources, mode, th, nn_ratio, view_cos_limit, check_orientation, mono, last_Rcw, last_tcw):
+    """the qsp_search_proj_in of search_by_projection and `keep`: what its pointers point into (the last entry by field name)"""
+    mode = {"local": 0, "last": 1}.get(mode, mode)
+    keep = []
+    fr = _fuse_target(frame, keep)
+    n = int(fr.n)
+    ns = int(np.size(sources["valid"]))
+    a = dict(u_right=_arr(np.append(np.reshape(frame["u_right"], -1), 0), np.float32),
+             slot_blocked=_arr(np.append(np.reshape(frame["slot_blocked"], -1), 0) != 0, np.uint8),
+             kp_angle=_arr(np.append(np.reshape(frame.get("kp_angle", np.zeros(n)), -1), 0), np.float32))
+    for key in ("slot_blocked", "kp_angle"):
+        if len(a[key]) != n + 1:
+            raise ValueError("search_by_projection: %s does not hold one value per key point" % key)
+    for key, field, dt, w in _PROJ_SRC + (_PROJ_SRC_MODE[mode] if mode in (0, 1) else ()):
+        if key == "angle" and key not in sources:
+            continue
+        if int(np.size(sources[key])) != w * ns:
+            raise ValueError("search_by_projection: the sources' %s does not hold %d values per source" % (key, w))
+        a[field] = _arr(np.append(np.reshape(sources[key], -1), np.zeros(w)), dt)
+    keep += [fr, a]
+    i = _lib.SearchProjIn()
+    i.mode, i.frame, i.n_src = int(mode), C.pointer(fr), ns
+    i.K[:] = [float(v) for v in np.reshape(frame["K"], 5)]
+    i.Ow[:] = [float(v) for v in np.reshape(frame.get("Ow", np.zeros(3)), 3)]
+    i.mb = float(frame.get("mb", 0.0))
+    i.th, i.nn_ratio, i.view_cos_limit = float(th), float(nn_ratio), float(view_cos_limit)
+    i.check_orientation, i.mono = int(bool(check_orientation)), int(bool(mono))
+    i.last_Rcw[:] = [float(v) for v in np.reshape(np.eye(3) if last_Rcw is None else last_Rcw, 9)]
+    i.last_tcw[:] = [float(v) for v in np.reshape(np.zeros(3) if last_tcw is None else last_tcw, 3)]
+    for field, arr in a.items():
+        setattr(i, field, _PROJ_PTR[arr.dtype.type](arr))
+    return i, keep
+
+
+def search_by_projection(frame, sources, mode="local", th=1.0, nn_ratio=0.8, view_cos_limit=0.5, check_orientation=True, mono=False,
+                         last_Rcw=None, last_tcw=None, tap=False, device=0):
+    """Tracking's projection searches with the result of the reference's serial loop (qsp_search_by_projection, include/qsp_hip.h):
+    mode "local" is Frame::isInFrustum + ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) (reference
+    src/ORBmatcher.cc:45-129), mode "last" is SearchByProjection(Frame& Current, const Frame& Last, th, bMono) (:1328-1470).
+    `frame`, the current frame: kp (n,2), octave (n,), desc (n,32) uint8, bounds, grid (cols, rows, width_inv, height_inv), log_scale,
+    scale_factors, Rcw, tcw, K (5,) fx fy cx cy mbf, u_right (n,), slot_blocked (n,) and, by mode, Ow (3,) / mb and kp_angle (n,).
+    `sources`, in the reference's loop order: valid, blocks (n_src,), Xw (n_src,3), desc (n_src,32) and, by mode, normal, dist_min_inv,
+    dist_max_inv, dist_max / octave, angle.  Returns a dict: choice, dist (n_src,), slot_src (n,), n_matches, n_rounds; "local" adds
+    in_view, proj_x, proj_y, proj_xr, level, view_cos; "last" adds hist (30,) and ind (3,); tap=True adds reason and, by mode, dist2,
+    level_best, level2 / bin."""
+    i, keep = _proj_in(frame, sources, mode, th, nn_ratio, view_cos_limit, check_orientation, mono, last_Rcw, last_tcw)
+    local = i.mode == 0
+    ns, n = int(i.n_src), int(keep[-2].n)
+    o = _lib.SearchProjOut()
+    res = dict(slot_src=np.full(n + 1, -1, np.int32))
+    o.slot_src = _lib.i32ptr(res["slot_src"])
+    o.ind[:] = [-1, -1, -1]
+    for key, dt in _PROJ_OUT:
+        if (key in _PROJ_TAPS and not tap) or (key in _PROJ_LOCAL and not local) or (key == "bin" and local):
+            continue
+        res[key] = np.zeros(ns + 1, dt) if dt != np.int32 or key == "level" else np.full(ns + 1, -1, np.int32)
+        setattr(o, key, _PROJ_PTR[dt](res[key]))
+    _lib.check(_lib.lib().qsp_search_by_projection(int(device), C.byref(i), C.byref(o)))
+    res = {key: (v[:n] if key == "slot_src" else v[:ns]) for key, v in res.items()}
+    res.update(n_matches=int(o.n_matches), n_rounds=int(o.n_rounds))
+    if not local:
+        res.update(hist=np.array(o.hist[:], np.int32), ind=np.array(o.ind[:], np.int32))
+    return res
+
+
 _TRI_POSE = (("Rcw", 9), ("tcw", 3), ("Ow", 3))
 _TRI_SCALARS = ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")
 _TRI_ARRAYS = (("xy", "xy_un", 2), ("xy_raw", "xy", 2), ("u_right", "u_right", 1), ("depth", "depth", 1), ("sigma2", "sigma2", 1),

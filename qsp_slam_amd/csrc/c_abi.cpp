@@ -1,5 +1,5 @@
 // c_abi.cpp -- library-wide C-ABI entry points (version, error text, device count), the buffer cache, and the one-shot batch calls:
-// the object map-point gate, Sim3 RANSAC, SearchBySim3, SearchByBoW, SearchForTriangulation, the triangulation of CreateNewMapPoints, Fuse, the ellipsoid fits, OptimizeSim3 and the essential graph.  The
+// the object map-point gate, Sim3 RANSAC, SearchBySim3, SearchByBoW, SearchForTriangulation, the triangulation of CreateNewMapPoints, Fuse, tracking's SearchByProjection, the ellipsoid fits, OptimizeSim3 and the essential graph.  The
 // last launches the dense factorisation that ba_solver.hip defines, through dense_chol.hpp; nothing else here is the solver's.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 #include "fuse.hpp"
 #include "object_gate.hpp"
 #include "search_bow.hpp"
+#include "search_projection.hpp"
 #include "search_sim3.hpp"
 #include "search_triangulation.hpp"
 #include "sim3_opt.hpp"
