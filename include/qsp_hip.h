@@ -1263,6 +1263,93 @@ typedef struct {
 } qsp_search_proj_out;
 int qsp_search_by_projection(int device, const qsp_search_proj_in* in, qsp_search_proj_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The two projection searches against a list of map points that fill slots of ONE frame, with the result of the reference's
+ * SERIAL loop:
+ *   mode 0, RELOC: ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th,
+ *                  ORBdist) (src/ORBmatcher.cc:1472-1599), what Tracking::Relocalization runs between two PoseOptimization calls;
+ *   mode 1, SIM3:  ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
+ *                  vector<MapPoint*>& vpMatched, th) (:290-403), what LoopClosing::ComputeSim3 runs on the accepted candidate.
+ * Sources are numbered in the reference's loop order (RELOC: the slots of pKF->GetMapPointMatches(); SIM3: vpPoints, the same
+ * point listed twice being two sources).  Source i sees slot idx as taken when slot_blocked[idx] (the slot was non-null at entry,
+ * whatever its point's observations) or when ANY earlier source chose idx: both loops test the slot for non-null and every
+ * matched source writes its point there.  So this is the fixed point of qsp_search_by_projection with every source blocking,
+ * iterated in the same rounds; and since a later source never chooses a slot an earlier one holds, all choices >= 0 are distinct:
+ * no slot is over-written, and n_matches is their number less the histogram removals.
+ * `frame` is the frame searched: kp, octave, desc, the bounds and grid, n_levels, log_scale, scale_factors, Rcw and tcw are read
+ * (the map-point fields are not and may be NULL).  RELOC: the current frame.  SIM3: pKF, with Rcw = sRcw / scw and tcw = Scw.t /
+ * scw, scw = sqrt(row0 . row0), and Ow = -Rcw^T tcw, decomposed by the caller with the reference's cv::Mat operations.
+ * Arithmetic, the reference's float32 one operation at a time: matrix rows summed in double and rounded once, t added in float32;
+ * PO = Xw - Ow in float32, cv::norm(PO) and PO.dot(Pn) in double; compares against double literals in double; the level is
+ * clamp(ceil(logf(dist_max / dist) / log_scale), 0, n_levels - 1) (MapPoint::PredictScale) as in LOCAL.
+ * RELOC, per source with src_valid (the caller folds null, isBad() and membership of sAlreadyFound into it):
+ *   x3Dc = Rcw Xw + tcw; invzc = (float)(1.0 / z) and NO test of its sign: a point behind the camera that projects inside the image
+ *   is searched and can match; u = fx * xc * invzc + cx (left to right), v likewise; refuse u < min_x || u > max_x, v likewise
+ *   (closed at both ends); dist3D = (float)norm(Xw - Ow), refuse dist3D < dist_min_inv || dist3D > dist_max_inv; no viewing-angle
+ *   test; radius = th * scale_factors[level]; the area is Frame::GetFeaturesInArea(u, v, radius, level - 1, level + 1): a key point
+ *   is in it when its own cell (round((x - min_x) * grid_w_inv), round((y - min_y) * grid_h_inv)) lies in the grid and in the
+ *   visited range, level - 1 <= octave <= level + 1 and |kx - u| < radius && |ky - v| < radius (strict).  Taken slots are skipped.
+ *   The best is the smallest (Hamming distance, cell x, cell y, index) below 256, kept when dist <= orb_dist.  With
+ *   check_orientation: rot = src_angle - kp_angle[best], + 360 when negative, bin = round(rot * (1.0f / 30)), 30 becomes 0; the
+ *   30-bin histogram, ComputeThreeMaxima and the nulling of :1577-1596 follow (slot_src = -2, n_matches reduced).
+ * SIM3, per source with src_valid (!isBad() and not in spAlreadyFound, the non-null entries of vpMatched at entry):
+ *   p3Dc = Rcw Xw + tcw; refuse z < 0.0 (-0.0 passes); invz = 1 / z in float32, x = p3Dc.x * invz, u = fx * x + cx -- another order
+ *   of operations than RELOC's --, v likewise; KeyFrame::IsInImage is half-open: refuse unless u >= min_x && u < max_x && v >= min_y
+ *   && v < max_y (a NaN u or v fails it and is refused here, as in the reference); dist = (float)norm(Xw - Ow), the same limits;
+ *   refuse PO.dot(Pn) < 0.5 * dist, compared in double; radius = th * scale_factors[level]; the area is
+ *   KeyFrame::GetFeaturesInArea(u, v, radius), which has no level filter; of the area, taken slots are skipped, then key points
+ *   with octave < level - 1 || octave > level (these were in the area: when nothing else remains the reason is 8, not 7).  The best
+ *   is the smallest key, kept when dist <= 50 (TH_LOW); orb_dist must say 50.  No orientation check.
+ * No right-image test and no ratio test in either.  th is a float; SIM3's caller passes its int converted, as the reference's
+ * th * mvScaleFactors[level] converts it.
+ * Where the reference would run into undefined behaviour the library follows LOCAL / LAST: a RELOC source whose u or v is NaN (z ==
+ * +0 with xc == 0), a source whose dist or predicted level is NaN, or whose radius is NaN, ends with reason 6 and matches nothing; an
+ * infinite u or v is outside the image like any other; a Hamming distance of 256 never beats the initial 256; a bin outside [0, 30)
+ * is reported as -1 and counted in no bin, so the match stays.
+ * reason: as qsp_search_by_projection's (2 only in SIM3, 5 only in SIM3, 10 never).  level, proj_x, proj_y: the predicted level and
+ * (u, v) of a source that passed every gate (reasons 0, 7, 8, 9), else 0.  slot_src: the source whose point the slot holds at the
+ * end, -1 untouched (slots taken at entry among them), -2 nulled by the histogram (RELOC only).
+ * No floating-point atomics: a call's outputs have the same bits on every run.  Host pointers.  n_src == 0 is QSP_OK and touches
+ * nothing.  QSP_ERR_INVALID: null required pointers (arrays of a frame with n == 0 may be NULL; normal is required in SIM3,
+ * kp_angle and src_angle in RELOC with check_orientation; the taps may be NULL), negative counts, n > 2^26 or n_src > 2^26, n_levels
+ * outside [1, 16], a grid outside 1..64 x 1..64, a key point's octave outside [0, n_levels), an unknown mode, SIM3 with orb_dist !=
+ * 50 or check_orientation != 0.  QSP_ERR_DEVICE with "internal error" in the text: the rounds did not settle within n_src + 1, or a
+ * taken slot was chosen (both impossible by the argument above: a bug).  No output is written unless the call returns QSP_OK. */
+typedef struct {
+    int32_t mode;                         /* 0 RELOC, 1 SIM3 */
+    const qsp_orb_frame* frame;           /* RELOC: the current frame; SIM3: pKF with the decomposed Scw as its pose */
+    float K[4];                           /* fx fy cx cy */
+    float Ow[3];                          /* -Rcw^T tcw */
+    const uint8_t* slot_blocked;          /* (n) 1 = the slot is non-null at entry */
+    const float* kp_angle;                /* (n) mvKeysUn[idx].angle; RELOC with check_orientation */
+    float th;
+    int32_t orb_dist;                     /* RELOC: ORBdist; SIM3: 50 */
+    int32_t check_orientation;            /* RELOC */
+    int32_t n_src;
+    const uint8_t* src_valid;             /* (n_src) */
+    const float* Xw;                      /* (n_src,3) GetWorldPos() */
+    const uint8_t* desc;                  /* (n_src,32) GetDescriptor() */
+    const float* dist_min_inv;            /* (n_src) GetMinDistanceInvariance() */
+    const float* dist_max_inv;            /* (n_src) GetMaxDistanceInvariance() */
+    const float* dist_max;                /* (n_src) mfMaxDistance, what PredictScale divides */
+    const float* normal;                  /* (n_src,3) GetNormal(); SIM3 */
+    const float* src_angle;               /* (n_src) pKF->mvKeysUn[i].angle; RELOC with check_orientation */
+} qsp_search_proj_kf_in;
+typedef struct {
+    int32_t* choice;                      /* (n_src) the slot the source's point was written to, else -1 */
+    int32_t* dist;                        /* (n_src) the best distance, -1 where nothing was compared */
+    int32_t* slot_src;                    /* (n) the source whose point the slot holds at the end, -1 untouched, -2 nulled */
+    /* the tests' taps, each may be NULL */
+    int32_t* reason;                      /* (n_src) */
+    int32_t* level;                       /* (n_src) the predicted level */
+    float *proj_x, *proj_y;               /* (n_src) */
+    int32_t* bin;                         /* (n_src) RELOC with check_orientation: the histogram bin of a matched source, else -1 */
+    int32_t n_matches;                    /* matched sources less the histogram removals */
+    int32_t hist[30], ind[3];             /* RELOC with check_orientation; else 0 and -1 */
+    int32_t n_rounds;
+} qsp_search_proj_kf_out;
+int qsp_search_by_projection_kf(int device, const qsp_search_proj_kf_in* in, qsp_search_proj_kf_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1606,6 +1606,25 @@ public:
         return QSP_OK;
     }
 
+    // Rcw = sRcw / scw, tcw = Scw.t / scw and Ow = -Rcw.t() * tcw (src/ORBmatcher.cc:299-303 and :986-990) as cv::Mat forms them for
+    // CV_32F: the row dot product and the 3x3 products summed in double and rounded once, the division as a multiplication by
+    // 1.0 / scw rounded to float32.
+    static void decompose_scw(const cv::Mat& S, float* Rcw, float* tcw, float* Ow) {
+        double dot = 0.0;
+        for (int c = 0; c < 3; ++c) dot += (double)S.template at<float>(0, c) * (double)S.template at<float>(0, c);
+        const float scw = (float)std::sqrt(dot);
+        const float inv = (float)(1.0 / (double)scw);
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) Rcw[3 * r + c] = S.template at<float>(r, c) * inv;
+            tcw[r] = S.template at<float>(r, 3) * inv;
+        }
+        for (int r = 0; r < 3; ++r) {
+            double s = 0.0;
+            for (int q = 0; q < 3; ++q) s += (double)Rcw[3 * q + r] * (double)tcw[q];
+            Ow[r] = (float)(-s);
+        }
+    }
+
     // ORBmatcher::Fuse(vpKFs[k], vScw[k], vpPoints, th, vvpReplacePoints[k]) (src/ORBmatcher.cc:977-1100) for ALL corrected key frames
     // of LoopClosing::SearchAndFuse in one library call.  vvpReplacePoints[k] comes back as the reference fills a vector of
     // vpPoints.size() NULLs; the Replace under the map mutex stays the caller's: after_target(k) is called when target k has been
@@ -1635,20 +1654,7 @@ public:
         for (size_t k = 0; k < nk; ++k) {
             KF* pKF = vpKFs[k];
             gather(pKF, std::vector<MP*>(pKF->mvKeysUn.size(), static_cast<MP*>(NULL)), fa[k], fr[k]);
-            const cv::Mat& S = vScw[k];                                              // :986-990
-            double dot = 0.0;
-            for (int c = 0; c < 3; ++c) dot += (double)S.template at<float>(0, c) * (double)S.template at<float>(0, c);
-            const float scw = (float)std::sqrt(dot);
-            const float inv = (float)(1.0 / (double)scw);
-            for (int r = 0; r < 3; ++r) {
-                for (int c = 0; c < 3; ++c) fr[k].Rcw[3 * r + c] = S.template at<float>(r, c) * inv;
-                fr[k].tcw[r] = S.template at<float>(r, 3) * inv;
-            }
-            for (int r = 0; r < 3; ++r) {
-                double s = 0.0;
-                for (int q = 0; q < 3; ++q) s += (double)fr[k].Rcw[3 * q + r] * (double)fr[k].tcw[q];
-                Ow[3 * k + r] = (float)(-s);
-            }
+            decompose_scw(vScw[k], fr[k].Rcw, fr[k].tcw, &Ow[3 * k]);                // :986-990
             const std::set<MP*> spAlreadyFound = pKF->GetMapPoints();                // :993
             for (size_t i = 0; i < vpPoints.size(); ++i)
                 if (p.ok[i] && !spAlreadyFound.count(vpPoints[i])) lists[k].push_back((int32_t)i);               // :1005
@@ -1834,6 +1840,109 @@ public:
             if (slot[idx] >= 0) CurrentFrame.mvpMapPoints[idx] = LastFrame.mvpMapPoints[slot[idx]];
             else if (slot[idx] == -2) CurrentFrame.mvpMapPoints[idx] = nullptr;      // :1462
         }
+        if (n_matches) *n_matches = out.n_matches;
+        return QSP_OK;
+    }
+
+    // ORBmatcher(nnratio, checkOri).SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1472-1599),
+    // what Tracking::Relocalization runs twice per surviving candidate between its PoseOptimization calls, in one library call
+    // with the serial loop's result.  Slot i of pKF->GetMapPointMatches() is a source when it holds a point that is not bad and
+    // not in sAlreadyFound; its angle is pKF->mvKeysUn[i].angle (:1562).  A slot of the current frame is taken when it is non-null
+    // (:1541), whatever its point's observations: the frame arrays are those of the tracking searches, slot_blocked is not.  On
+    // QSP_OK CurrentFrame.mvpMapPoints[idx] = vpMPs[slot_src[idx]] where the loop wrote, NULL where the orientation check nulled;
+    // *n_matches is the reference's return value.  Returns the qsp status; on any other status the frame has not been touched.
+    template <typename FR, typename KF, typename MP>
+    static int SearchByProjection(FR& CurrentFrame, KF* pKF, const std::set<MP*>& sAlreadyFound, const float th, const int ORBdist,
+                                  const bool checkOri, int* n_matches = nullptr) {
+        const auto vpMPs = pKF->GetMapPointMatches();
+        const size_t ns = vpMPs.size();
+        if (n_matches) *n_matches = 0;
+        if (ns == 0) return QSP_OK;
+        ProjFrameArrays a;
+        qsp_orb_frame f;
+        qsp_search_proj_in tracking;
+        gather_proj_frame(CurrentFrame, a, f, tracking);
+        for (int i = 0; i < f.n; ++i) a.blocked[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;
+        qsp_search_proj_kf_in in = qsp_search_proj_kf_in();
+        in.mode = 0; in.frame = &f; in.th = th; in.orb_dist = ORBdist; in.check_orientation = checkOri ? 1 : 0; in.n_src = (int32_t)ns;
+        for (int r = 0; r < 4; ++r) in.K[r] = tracking.K[r];
+        for (int r = 0; r < 3; ++r) {                                                // :1478, -Rcw.t() * tcw
+            double s = 0.0;
+            for (int q = 0; q < 3; ++q) s += (double)f.Rcw[3 * q + r] * (double)f.tcw[q];
+            in.Ow[r] = (float)(-s);
+        }
+        in.slot_blocked = a.blocked.data(); in.kp_angle = a.angle.data();
+        std::vector<uint8_t> valid(ns + 1, 0), desc(32 * ns + 1, 0);
+        std::vector<float> Xw(3 * ns + 1, 0.f), dmin(ns + 1, 0.f), dmaxi(ns + 1, 0.f), dmax(ns + 1, 0.f), angle(ns + 1, 0.f);
+        for (size_t i = 0; i < ns; ++i) {
+            MP* pMP = static_cast<MP*>(vpMPs[i]);
+            if (!pMP || pMP->isBad() || sAlreadyFound.count(pMP)) continue;          // :1492-1494
+            valid[i] = 1;
+            const cv::Mat X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; ++r) Xw[3 * i + r] = X.template at<float>(r);
+            dmin[i] = pMP->GetMinDistanceInvariance();
+            dmaxi[i] = pMP->GetMaxDistanceInvariance();
+            dmax[i] = dmaxi[i] / 1.2f;                                               // mfMaxDistance is protected, as in gather()
+            const auto d = pMP->GetDescriptor();
+            for (int b = 0; b < 32; ++b) desc[32 * i + b] = d.template at<unsigned char>(0, b);
+            angle[i] = pKF->mvKeysUn[i].angle;
+        }
+        in.src_valid = valid.data(); in.Xw = Xw.data(); in.desc = desc.data(); in.dist_min_inv = dmin.data(); in.dist_max_inv = dmaxi.data();
+        in.dist_max = dmax.data(); in.src_angle = angle.data();
+        std::vector<int32_t> choice(ns + 1), dist(ns + 1), slot((size_t)f.n + 1);
+        qsp_search_proj_kf_out out = qsp_search_proj_kf_out();
+        out.choice = choice.data(); out.dist = dist.data(); out.slot_src = slot.data();
+        const int rc = qsp_shim::report("qsp_search_by_projection_kf", qsp_search_by_projection_kf(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        for (int idx = 0; idx < f.n; ++idx) {
+            if (slot[idx] >= 0) CurrentFrame.mvpMapPoints[idx] = static_cast<MP*>(vpMPs[slot[idx]]);     // :1557
+            else if (slot[idx] == -2) CurrentFrame.mvpMapPoints[idx] = nullptr;      // :1591
+        }
+        if (n_matches) *n_matches = out.n_matches;
+        return QSP_OK;
+    }
+
+    // ORBmatcher(nnratio, checkOri).SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:290-403), what
+    // LoopClosing::ComputeSim3 runs on the accepted candidate, in one library call with the serial loop's result.  Scw is decomposed
+    // as FuseBatch decomposes it.  A point is a source when it is non-null (the reference would dereference it), not bad and not
+    // among the non-null entries of vpMatched at entry (:306-307); a slot is taken when vpMatched[idx] is non-null (:375).  On
+    // QSP_OK vpMatched[idx] = vpPoints[slot_src[idx]] where the loop wrote; *n_matches is the reference's return value.  Returns
+    // the qsp status; on any other status vpMatched has not been touched.
+    template <typename KF, typename MP>
+    static int SearchByProjection(KF* pKF, const cv::Mat& Scw, const std::vector<MP*>& vpPoints, std::vector<MP*>& vpMatched, const int th,
+                                  int* n_matches = nullptr) {
+        const size_t ns = vpPoints.size();
+        if (n_matches) *n_matches = 0;
+        if (ns == 0) return QSP_OK;
+        FrameArrays fa;
+        qsp_orb_frame f = qsp_orb_frame();
+        gather(pKF, std::vector<MP*>(pKF->mvKeysUn.size(), static_cast<MP*>(NULL)), fa, f);
+        if (vpMatched.size() != (size_t)f.n) {
+            std::fprintf(stderr, "[qsp_hip] OrbMatcherHip::SearchByProjection: %d key points, but %zu entries of vpMatched\n", f.n, vpMatched.size());
+            return QSP_ERR_INVALID;
+        }
+        qsp_search_proj_kf_in in = qsp_search_proj_kf_in();
+        in.mode = 1; in.frame = &f; in.th = (float)th; in.orb_dist = 50; in.check_orientation = 0; in.n_src = (int32_t)ns;
+        in.K[0] = pKF->fx; in.K[1] = pKF->fy; in.K[2] = pKF->cx; in.K[3] = pKF->cy;
+        decompose_scw(Scw, f.Rcw, f.tcw, in.Ow);                                     // :299-303
+        std::set<MP*> spAlreadyFound(vpMatched.begin(), vpMatched.end());            // :306-307
+        spAlreadyFound.erase(static_cast<MP*>(NULL));
+        std::vector<uint8_t> blocked((size_t)f.n + 1, 0);
+        for (int i = 0; i < f.n; ++i) blocked[i] = vpMatched[i] ? 1 : 0;
+        PoolArrays p;
+        gather_pool(vpPoints, p);
+        for (size_t i = 0; i < ns; ++i)
+            if (p.ok[i] && spAlreadyFound.count(vpPoints[i])) p.ok[i] = 0;           // :317
+        in.slot_blocked = blocked.data();
+        in.src_valid = p.ok.data(); in.Xw = p.Xw.data(); in.desc = p.desc.data(); in.dist_min_inv = p.dmin.data();
+        in.dist_max_inv = p.dmaxi.data(); in.dist_max = p.dmax.data(); in.normal = p.normal.data();
+        std::vector<int32_t> choice(ns + 1), dist(ns + 1), slot((size_t)f.n + 1);
+        qsp_search_proj_kf_out out = qsp_search_proj_kf_out();
+        out.choice = choice.data(); out.dist = dist.data(); out.slot_src = slot.data();
+        const int rc = qsp_shim::report("qsp_search_by_projection_kf", qsp_search_by_projection_kf(OptimizerHip::device(), &in, &out));
+        if (rc != QSP_OK) return rc;
+        for (int idx = 0; idx < f.n; ++idx)
+            if (slot[idx] >= 0) vpMatched[idx] = vpPoints[slot[idx]];                // :396
         if (n_matches) *n_matches = out.n_matches;
         return QSP_OK;
     }

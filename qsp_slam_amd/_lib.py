@@ -186,6 +186,20 @@ class SearchProjOut(C.Structure):
                 ("hist", C.c_int32 * 30), ("ind", C.c_int32 * 3), ("n_rounds", C.c_int32)]
 
 
+class SearchProjKfIn(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("frame", C.POINTER(OrbFrame)), ("K", C.c_float * 4), ("Ow", C.c_float * 3),
+                ("slot_blocked", c_uint8_p), ("kp_angle", c_float_p), ("th", C.c_float), ("orb_dist", C.c_int32),
+                ("check_orientation", C.c_int32), ("n_src", C.c_int32), ("src_valid", c_uint8_p), ("Xw", c_float_p), ("desc", c_uint8_p),
+                ("dist_min_inv", c_float_p), ("dist_max_inv", c_float_p), ("dist_max", c_float_p), ("normal", c_float_p),
+                ("src_angle", c_float_p)]
+
+
+class SearchProjKfOut(C.Structure):
+    _fields_ = [("choice", c_int32_p), ("dist", c_int32_p), ("slot_src", c_int32_p), ("reason", c_int32_p), ("level", c_int32_p),
+                ("proj_x", c_float_p), ("proj_y", c_float_p), ("bin", c_int32_p), ("n_matches", C.c_int32),
+                ("hist", C.c_int32 * 30), ("ind", C.c_int32 * 3), ("n_rounds", C.c_int32)]
+
+
 class TriangulateFrame(C.Structure):
     _fields_ = [("n", C.c_int32), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
@@ -216,7 +230,7 @@ SYMBOLS = [
     "qsp_mesh_extractor_create_group", "qsp_mesh_extract_batch_group",
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
-    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_fuse_batch", "qsp_search_by_projection", "qsp_triangulate_batch", "qsp_create_new_map_points_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_fuse_batch", "qsp_search_by_projection", "qsp_search_by_projection_kf", "qsp_triangulate_batch", "qsp_create_new_map_points_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -314,6 +328,7 @@ def lib():
     L.qsp_search_for_triangulation_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(SearchTriOut)]
     L.qsp_fuse_batch.argtypes = [C.c_int, C.POINTER(FuseIn), C.POINTER(FuseOut)]
     L.qsp_search_by_projection.argtypes = [C.c_int, C.POINTER(SearchProjIn), C.POINTER(SearchProjOut)]
+    L.qsp_search_by_projection_kf.argtypes = [C.c_int, C.POINTER(SearchProjKfIn), C.POINTER(SearchProjKfOut)]
     L.qsp_triangulate_batch.argtypes = [C.c_int, C.POINTER(TriangulateGeom), c_int32_p, C.POINTER(TriangulateOut)]
     L.qsp_create_new_map_points_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(TriangulateGeom), C.POINTER(SearchTriOut),
                                                   C.POINTER(TriangulateOut)]

@@ -677,6 +677,85 @@ def search_by_projection(frame, sources, mode="local", th=1.0, nn_ratio=0.8, vie
     return res
 
 
+_PROJ_KF_SRC = (("valid", "src_valid", np.uint8, 1), ("Xw", "Xw", np.float32, 3), ("desc", "desc", np.uint8, 32),
+                ("dist_min_inv", "dist_min_inv", np.float32, 1), ("dist_max_inv", "dist_max_inv", np.float32, 1),
+                ("dist_max", "dist_max", np.float32, 1), ("normal", "normal", np.float32, 3), ("angle", "src_angle", np.float32, 1))
+_PROJ_KF_OUT = (("choice", np.int32), ("dist", np.int32), ("reason", np.int32), ("level", np.int32), ("proj_x", np.float32),
+                ("proj_y", np.float32), ("bin", np.int32))       # per source; slot_src is per key point
+
+
+def decompose_scw(Scw):
+    """(Rcw, tcw, Ow) of a 3x4 (or 4x4) float32 Sim3 `Scw` as ORBmatcher.cc:299-303 decomposes it with cv::Mat operations on CV_32F,
+    the form OrbMatcherHip::FuseBatch and the Sim3 overload of OrbMatcherHip::SearchByProjection use: scw = (float)sqrt(row0 . row0)
+    with the dot product summed in double, Rcw = sRcw / scw and tcw = t / scw as float32 products with (float)(1.0 / scw) (what
+    cv::Mat's division by a scalar is), Ow = -Rcw^T tcw (rows summed in double, rounded once, negated).  Exact divisions where scw is
+    a power of two."""
+    f32, f64 = np.float32, np.float64
+    S = np.asarray(Scw, f32)[:3, :4]
+    r0 = S[0, :3].astype(f64)
+    scw = f32(np.sqrt((r0[0] * r0[0] + r0[1] * r0[1]) + r0[2] * r0[2]))
+    inv = f32(1.0 / f64(scw))
+    R, t = (S[:, :3] * inv).astype(f32), (S[:, 3] * inv).astype(f32)
+    Rt, t64 = R.T.astype(f64), t.astype(f64)
+    Ow = -((Rt[:, 0] * t64[0] + Rt[:, 1] * t64[1]) + Rt[:, 2] * t64[2]).astype(f32)
+    return R, t, Ow
+
+
+def _proj_kf_in(frame, src, mode, th, orb_dist, check_orientation):
+    """the qsp_search_proj_kf_in of search_by_projection_kf and `keep`: what its pointers point into (the last entry by field name)"""
+    mode = {"reloc": 0, "sim3": 1}.get(mode, mode)
+    keep = []
+    n = int(np.size(frame["octave"]))
+    fr = _fuse_target(dict(frame, u_right=np.zeros(n, np.float32)), keep)
+    ns = int(np.size(src["valid"]))
+    a = dict(slot_blocked=_arr(np.append(np.reshape(frame["slot_blocked"], -1), 0) != 0, np.uint8),
+             kp_angle=_arr(np.append(np.reshape(frame.get("kp_angle", np.zeros(n)), -1), 0), np.float32))
+    for key in ("slot_blocked", "kp_angle"):
+        if len(a[key]) != n + 1:
+            raise ValueError("search_by_projection_kf: %s does not hold one value per key point" % key)
+    for key, field, dt, w in _PROJ_KF_SRC:
+        if key in ("normal", "angle") and key not in src:
+            continue
+        if int(np.size(src[key])) != w * ns:
+            raise ValueError("search_by_projection_kf: the sources' %s does not hold %d values per source" % (key, w))
+        a[field] = _arr(np.append(np.reshape(src[key], -1), np.zeros(w)), dt)
+    keep += [fr, a]
+    i = _lib.SearchProjKfIn()
+    i.mode, i.frame, i.n_src = int(mode), C.pointer(fr), ns
+    i.K[:] = [float(v) for v in np.reshape(frame["K"], -1)[:4]]
+    i.Ow[:] = [float(v) for v in np.reshape(frame["Ow"], 3)]
+    i.th, i.orb_dist, i.check_orientation = float(th), int(orb_dist), int(bool(check_orientation))
+    for field, arr in a.items():
+        setattr(i, field, _PROJ_PTR[arr.dtype.type](arr))
+    return i, keep
+
+
+def search_by_projection_kf(frame, src, mode, th, orb_dist=50, check_orientation=False, device=0):
+    """The relocalisation and Sim3 overloads of ORBmatcher::SearchByProjection with the result of the reference's serial loop
+    (qsp_search_by_projection_kf, include/qsp_hip.h): mode "reloc" is SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const
+    set<MapPoint*>& sAlreadyFound, th, ORBdist) (reference src/ORBmatcher.cc:1472-1599), mode "sim3" is SearchByProjection(KeyFrame*
+    pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, th) (:290-403).
+    `frame`, the frame searched: kp (n,2), octave (n,), desc (n,32) uint8, bounds, grid (cols, rows, width_inv, height_inv), log_scale,
+    scale_factors, Rcw, tcw, Ow (for "sim3" the three of decompose_scw), K (at least 4,) fx fy cx cy, slot_blocked (n,) = the slot is
+    non-null at entry and, with check_orientation, kp_angle (n,).  `src`, in the reference's loop order: valid (n_src,), Xw (n_src,3),
+    desc (n_src,32), dist_min_inv, dist_max_inv, dist_max (n_src,) and normal (n_src,3) for "sim3" / angle (n_src,) for "reloc" with
+    check_orientation.  Returns the same kind of dict as search_by_projection: choice, dist (n_src,), slot_src (n,), n_matches,
+    n_rounds, hist (30,), ind (3,) and the taps reason, level, proj_x, proj_y, bin (n_src,)."""
+    i, keep = _proj_kf_in(frame, src, mode, th, orb_dist, check_orientation)
+    ns, n = int(i.n_src), int(keep[-2].n)
+    o = _lib.SearchProjKfOut()
+    res = dict(slot_src=np.full(n + 1, -1, np.int32))
+    o.slot_src = _lib.i32ptr(res["slot_src"])
+    o.ind[:] = [-1, -1, -1]
+    for key, dt in _PROJ_KF_OUT:
+        res[key] = np.zeros(ns + 1, dt) if dt != np.int32 or key == "level" else np.full(ns + 1, -1, np.int32)
+        setattr(o, key, _PROJ_PTR[dt](res[key]))
+    _lib.check(_lib.lib().qsp_search_by_projection_kf(int(device), C.byref(i), C.byref(o)))
+    res = {key: (v[:n] if key == "slot_src" else v[:ns]) for key, v in res.items()}
+    res.update(n_matches=int(o.n_matches), n_rounds=int(o.n_rounds), hist=np.array(o.hist[:], np.int32), ind=np.array(o.ind[:], np.int32))
+    return res
+
+
 _TRI_POSE = (("Rcw", 9), ("tcw", 3), ("Ow", 3))
 _TRI_SCALARS = ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")
 _TRI_ARRAYS = (("xy", "xy_un", 2), ("xy_raw", "xy", 2), ("u_right", "u_right", 1), ("depth", "depth", 1), ("sigma2", "sigma2", 1),

@@ -11,6 +11,7 @@
 #include "object_gate.hpp"
 #include "search_bow.hpp"
 #include "search_projection.hpp"
+#include "search_projection_kf.hpp"
 #include "search_sim3.hpp"
 #include "search_triangulation.hpp"
 #include "sim3_opt.hpp"

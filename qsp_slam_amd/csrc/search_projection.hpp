@@ -36,7 +36,7 @@ namespace proj {
 
 constexpr int HISTO_LENGTH = 30;
 constexpr int32_t NO_CLAIM = 0x7fffffff;
-enum Mode : int32_t { LOCAL = 0, LAST = 1 };
+enum Mode : int32_t { LOCAL = 0, LAST = 1, RELOC = 2, SIM3 = 3 };     // RELOC, SIM3: search_projection_kf.hpp, whose public 0 / 1 map onto them
 enum Reason : int32_t { MATCHED = 0, INVALID_SRC, Z_NEG, OUTSIDE, DISTANCE, ANGLE, NONFINITE, EMPTY, NONE_ELIGIBLE, ABOVE_TH, RATIO };
 
 struct Rec {                          // what k_proj_gate leaves per source for every round
@@ -68,6 +68,8 @@ struct In {
     const float *dist_min_inv, *dist_max_inv, *dist_max;   // [n_src]
     const uint8_t* src_desc;          // [n_src][32], 16-byte aligned
     const int32_t* src_octave;        // [n_src]
+    int32_t accept_th;                // the best is kept when its distance is <= accept_th (LOCAL, LAST: TH_HIGH)
+    int32_t no_right;                 // 1: no right-image test, u_right is not read (RELOC, SIM3)
 };
 
 struct Out {                          // per source
@@ -189,12 +191,16 @@ __global__ __launch_bounds__(256) void k_proj_round(In in, const Rec* __restrict
         if (cx < 0 || cx >= in.cols || cy < 0 || cy >= in.rows) continue;                    // never filed: never found
         if (cx < rc.min_cx || cx > rc.max_cx || cy < rc.min_cy || cy > rc.max_cy) continue;
         const int oct = in.octave[j];
-        if (oct < rc.lvl_min || oct > rc.lvl_max) continue;
+        const bool lvl_out = oct < rc.lvl_min || oct > rc.lvl_max;
+        if (lvl_out && in.mode != SIM3) continue;                    // Frame::GetFeaturesInArea filters the levels itself
         if (!(fabsf(k.x - rc.u) < rc.radius && fabsf(k.y - rc.v) < rc.radius)) continue;
         in_area = true;                                              // vIndices holds it
-        if (in.slot_blocked[j] || claim_prev[j] < i) continue;       // :87-89 / :1403-1405
-        const float kr = in.u_right[j];
-        if (kr > 0 && fabsf(rc.ur - kr) > rc.radius) continue;       // :91-96 / :1407-1413
+        if (in.slot_blocked[j] || claim_prev[j] < i) continue;       // :87-89 / :1403-1405 / :1541 / :375
+        if (lvl_out) continue;                                       // SIM3: KeyFrame::GetFeaturesInArea has no level filter, :380 has
+        if (!in.no_right) {
+            const float kr = in.u_right[j];
+            if (kr > 0 && fabsf(rc.ur - kr) > rc.radius) continue;   // :91-96 / :1407-1413
+        }
         const uint4* d = (const uint4*)(in.desc + 32 * (int64_t)j);
         const unsigned long long hd = (unsigned)(search::popc128(d[0], m0) + search::popc128(d[1], m1));
         if (hd >= 256) continue;                                     // never below the initial bestDist
@@ -217,16 +223,16 @@ __global__ __launch_bounds__(256) void k_proj_round(In in, const Rec* __restrict
             d2 = (int32_t)(k2 >> 40);
             l2 = in.octave[(int32_t)(k2 & idx_mask)];
         }
-        if (d1 > search::TH_HIGH) why = ABOVE_TH;
+        if (d1 > in.accept_th) why = ABOVE_TH;
         else if (in.mode == LOCAL && l1 == l2 && (float)d1 > in.nn_ratio * (float)d2) why = RATIO;   // :120 (no second: levels differ)
         else pick = b;
     }
-    if (in.mode == LAST) { d2 = -1; l1 = -1; l2 = -1; }              // best only
+    if (in.mode != LOCAL) { d2 = -1; l1 = -1; l2 = -1; }             // best only
     // `changed` follows the choice alone: a round with the choices of the one before was computed from the very claims those choices
     // make, so its dist, dist2, levels and reason are already the fixed point's
     if (o.choice[i] != pick) atomicOr(changed, 1);
     o.choice[i] = pick; o.dist[i] = d1; o.reason[i] = why; o.dist2[i] = d2; o.level_best[i] = l1; o.level2[i] = l2;
-    if (pick >= 0 && in.src_blocks[i]) atomicMin(claim_next + pick, (int32_t)i);
+    if (pick >= 0 && (in.mode >= RELOC || in.src_blocks[i])) atomicMin(claim_next + pick, (int32_t)i);   // RELOC, SIM3: every source blocks
 }
 
 // :1433-1439 on the host.  -1: outside the reference's domain (its assert), counted in no bin
@@ -252,6 +258,30 @@ inline void three_maxima_host(const int32_t* hist, int32_t* ind) {
     if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
     else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
     ind[0] = i1; ind[1] = i2; ind[2] = i3;
+}
+
+// The rounds on the host, for both entry points: round 1 sees the initial blocks only, every round reads the 4-byte `changed` word,
+// and the claim tables swap.  claim0 and claim1 hold n int32 each; *n_rounds counts the launches.
+inline int run_rounds(const char* who, const In& k, const Rec* d_rec, int32_t* claim0, int32_t* claim1, int32_t* d_chg, const Out& o,
+                      int32_t* n_rounds_out) {
+    const size_t zn = (size_t)k.n, zs = (size_t)k.n_src;
+    int32_t* claim[2] = {claim0, claim1};
+    if (zn) QSP_HIP(hipMemsetD32Async((hipDeviceptr_t)claim[0], NO_CLAIM, zn, 0));          // round 1: the initial blocks only
+    int32_t n_rounds = 0;
+    for (int32_t changed = 1; changed;) {
+        // a round that still changes a choice after n_src + 1 of them contradicts the induction: a bug, never an input
+        if (n_rounds > k.n_src)
+            return qsp_fail(QSP_ERR_DEVICE, (std::string(who) + ": internal error: the rounds did not reach their fixed point").c_str());
+        if (zn) QSP_HIP(hipMemsetD32Async((hipDeviceptr_t)claim[1], NO_CLAIM, zn, 0));
+        QSP_HIP(hipMemsetAsync(d_chg, 0, 4, 0));
+        hipLaunchKernelGGL(k_proj_round, dim3((unsigned)((zs + 3) / 4)), dim3(256), 0, 0, k, d_rec, claim[0], claim[1], d_chg, o);
+        QSP_HIP(hipGetLastError());
+        QSP_HIP(hipMemcpy(&changed, d_chg, 4, hipMemcpyDeviceToHost));
+        std::swap(claim[0], claim[1]);
+        ++n_rounds;
+    }
+    *n_rounds_out = n_rounds;
+    return QSP_OK;
 }
 
 }  // namespace proj
@@ -323,6 +353,7 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
     for (int l = 0; l < F.n_levels; ++l) k.sf[l] = F.scale_factors[l];
     memcpy(k.R, F.Rcw, sizeof k.R); memcpy(k.t, F.tcw, sizeof k.t); memcpy(k.Ow, in->Ow, sizeof k.Ow); memcpy(k.K, in->K, sizeof k.K);
     k.th = in->th; k.nn_ratio = in->nn_ratio; k.view_cos_limit = in->view_cos_limit;
+    k.accept_th = search::TH_HIGH; k.no_right = 0;
     if (!local) {
         // :1341-1349: twc = -Rcw^T tcw (a product scaled by -1: the double row sum rounded once, then negated), tlc = Rlw twc + tlw
         float twc[3];
@@ -345,23 +376,10 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
     o.proj_x = ptr<float>(d, a_px); o.proj_y = ptr<float>(d, a_py); o.proj_xr = ptr<float>(d, a_pxr); o.view_cos = ptr<float>(d, a_cos);
     o.level = ptr<int32_t>(d, a_lvl);
     proj::Rec* d_rec = ptr<proj::Rec>(d, a_rec);
-    int32_t* claim[2] = {ptr<int32_t>(d, a_c0), ptr<int32_t>(d, a_c1)};
-    int32_t* d_chg = ptr<int32_t>(d, a_chg);
     hipLaunchKernelGGL(proj::k_proj_gate, dim3((unsigned)((zs + 255) / 256)), dim3(256), 0, 0, k, d_rec, o);
     QSP_HIP(hipGetLastError());
-    if (n) QSP_HIP(hipMemsetD32Async((hipDeviceptr_t)claim[0], proj::NO_CLAIM, zn, 0));     // round 1: the initial blocks only
     int32_t n_rounds = 0;
-    for (int32_t changed = 1; changed;) {
-        // a round that still changes a choice after n_src + 1 of them contradicts the induction: a bug, never an input
-        if (n_rounds > ns) return bad(QSP_ERR_DEVICE, "internal error: the rounds did not reach their fixed point");
-        if (n) QSP_HIP(hipMemsetD32Async((hipDeviceptr_t)claim[1], proj::NO_CLAIM, zn, 0));
-        QSP_HIP(hipMemsetAsync(d_chg, 0, 4, 0));
-        hipLaunchKernelGGL(proj::k_proj_round, dim3((unsigned)((zs + 3) / 4)), dim3(256), 0, 0, k, d_rec, claim[0], claim[1], d_chg, o);
-        QSP_HIP(hipGetLastError());
-        QSP_HIP(hipMemcpy(&changed, d_chg, 4, hipMemcpyDeviceToHost));
-        std::swap(claim[0], claim[1]);
-        ++n_rounds;
-    }
+    QSP_TRY(proj::run_rounds(who, k, d_rec, ptr<int32_t>(d, a_c0), ptr<int32_t>(d, a_c1), ptr<int32_t>(d, a_chg), o, &n_rounds));
     QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
     const char* h = down.data();
     // the action phase: the sources in order, the last writer of a slot stays (:123 / :1428)
