@@ -1,16 +1,13 @@
 // fuse.hpp -- the match phase of both ORBmatcher::Fuse overloads (reference src/ORBmatcher.cc:825-975, the pose overload of
 // LocalMapping::SearchInNeighbors, and :977-1100, the Sim3 overload of LoopClosing::SearchAndFuse) for ALL target key frames in one
-// call.  Compiled in c_abi.cpp after search_sim3.hpp, whose rowdot, popc128, key layout and limits it uses as they are; the wave
-// reduction is wave.hpp's.
+// call.  Compiled in c_abi.cpp; the steps it shares with the other matchers are orb_match.hpp's, the wave reduction is wave.hpp's.
 //
 // Everything the reference computes up to (bestIdx, bestDist) reads only the map point (position, normal, distance limits,
 // descriptor) and the target key frame (pose, intrinsics, key points, octaves, mvuRight, descriptors, grid); the map enters
 // afterwards, in the action (GetMapPoint(bestIdx), Replace, AddObservation / AddMapPoint, vpReplacePoint[iMP] = ...), which stays
 // on the host.  So ONE WAVE owns one (target, listed point): all 64 lanes evaluate the point's gates redundantly, then stride
-// over the target's key points.  As in search_sim3.hpp no grid is built: a key point is eligible when its own cell
-// (Frame::PosInGrid) lies inside the grid and inside the range KeyFrame::GetFeaturesInArea visits, and the traversal order --
-// ascending (cell x, cell y, index) -- sits in a 64-bit key under the distance, so one wave min-reduction yields the reference's
-// `dist < bestDist` winner.  The points are a pool shared by all targets; a target lists the pool indices it searches.
+// over the target's key points, each lane keeping the smallest orb::make_key it met, so one wave min-reduction yields the
+// reference's `dist < bestDist` winner.  The points are a pool shared by all targets; a target lists the pool indices it searches.
 //
 // The two overloads differ in three places: the pose overload tests the reprojection error of each key point (:914-938,
 // check = 1), the Sim3 overload does not; the pose overload writes 1 / z in float32 and the Sim3 overload 1.0 / z in double
@@ -24,23 +21,18 @@
 #include <string>
 #include <vector>
 
-#include "search_sim3.hpp"
+#include "orb_match.hpp"
+#include "staging.hpp"
 #include "wave.hpp"
 
 namespace qsp {
 namespace fuse {
 
-constexpr int TH_LOW = 50;
 enum Reason : int32_t { MATCHED = 0, Z_NEG, OUTSIDE, DISTANCE, ANGLE, EMPTY, NONE_ELIGIBLE, ABOVE_TH };
 
 struct TargetP {
-    int32_t off, n;                   // its key-point slots are [off, off + n) of the flat arrays
-    float min_x, max_x, min_y, max_y;
-    int32_t cols, rows;
-    float w_inv, h_inv;
-    int32_t n_levels;
-    float log_scale;
-    float sf[search::MAX_LEVELS], inv_sigma2[search::MAX_LEVELS];
+    orb::GridP g;
+    float inv_sigma2[orb::MAX_LEVELS];
     float R[9], t[3], Ow[3];
     float K[5];                       // fx fy cx cy bf
     float th;
@@ -68,60 +60,44 @@ __global__ __launch_bounds__(256) void k_fuse_best(In in, int64_t n_pair, int32_
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n_pair) return;
-    int lo = 0, hi = in.n_target;                        // the target whose range holds w (empty lists are stepped over)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (in.list_off[mid] <= w) lo = mid; else hi = mid;
-    }
-    const TargetP& T = in.target[lo];
+    const TargetP& T = in.target[orb::owner_of(in.list_off, in.n_target, w)];
+    const orb::GridP& G = T.g;
     const int64_t s = in.list_idx[w];                    // the point in the pool
     int32_t res_best = -1, res_dist = -1, why = fuse::MATCHED, level = -1;
     float u = 0.f, v = 0.f, ur = 0.f, r = 0.f;
-    int min_cx = 0, max_cx = 0, min_cy = 0, max_cy = 0;
+    orb::CellRange cells = {};
     {                                                    // wave-uniform: every lane evaluates the point's gates
         const float* X = in.Xw + 3 * s;
-        float p[3], PO[3];
-        for (int k = 0; k < 3; ++k) p[k] = search::rowdot(T.R + 3 * k, X) + T.t[k];          // Rcw * p3Dw + tcw
+        float p[3], d3;
+        double dot;
+        for (int k = 0; k < 3; ++k) p[k] = orb::rowdot(T.R + 3 * k, X) + T.t[k];             // Rcw * p3Dw + tcw
         const float invz = (float)(1.0 / (double)p[2]);
         const float x = p[0] * invz, y = p[1] * invz;
         u = T.K[0] * x + T.K[2];
         v = T.K[1] * y + T.K[3];
         ur = u - T.K[4] * invz;
-        for (int k = 0; k < 3; ++k) PO[k] = X[k] - T.Ow[k];
-        const float d3 = (float)sqrt(((double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1]) + (double)PO[2] * (double)PO[2]);
-        const float* Pn = in.normal + 3 * s;
-        const double dot = ((double)PO[0] * (double)Pn[0] + (double)PO[1] * (double)Pn[1]) + (double)PO[2] * (double)Pn[2];
+        orb::view_geometry(X, T.Ow, in.normal + 3 * s, &d3, &dot);
         if (p[2] < 0.0f) why = fuse::Z_NEG;              // :856 (a NaN passes here and fails IsInImage)
-        else if (!(u >= T.min_x && u < T.max_x && v >= T.min_y && v < T.max_y)) why = fuse::OUTSIDE;
+        else if (!(u >= G.min_x && u < G.max_x && v >= G.min_y && v < G.max_y)) why = fuse::OUTSIDE;
         else if (d3 < in.dist_min_inv[s] || d3 > in.dist_max_inv[s]) why = fuse::DISTANCE;
         else if (dot < 0.5 * (double)d3) why = fuse::ANGLE;
         else {
-            // MapPoint::PredictScale(dist3D, target key frame), MapPoint.cc:391-406
-            const float ratio = in.dist_max[s] / d3;
-            const float fl = ceilf(logf(ratio) / T.log_scale);
-            level = fl < 0.f ? 0 : (fl >= (float)T.n_levels ? T.n_levels - 1 : (int)fl);
-            r = T.th * T.sf[level];
-            // KeyFrame::GetFeaturesInArea's cell range and early returns, KeyFrame.cc:575-589
-            min_cx = max(0, (int)floorf(((u - T.min_x) - r) * T.w_inv));
-            max_cx = min(T.cols - 1, (int)ceilf(((u - T.min_x) + r) * T.w_inv));
-            min_cy = max(0, (int)floorf(((v - T.min_y) - r) * T.h_inv));
-            max_cy = min(T.rows - 1, (int)ceilf(((v - T.min_y) + r) * T.h_inv));
-            if (min_cx >= T.cols || max_cx < 0 || min_cy >= T.rows || max_cy < 0) why = fuse::EMPTY;
+            level = orb::predict_scale(in.dist_max[s], d3, G.log_scale, G.n_levels);
+            r = T.th * G.sf[level];
+            if (orb::cell_range<false>(G, u, v, r, cells) != orb::CELLS_OK) why = fuse::EMPTY;
         }
     }
     if (why == fuse::MATCHED) {
         const uint4* md = (const uint4*)(in.mp_desc + 32 * s);       // the map point's descriptor: once per wave, 8 dwords
         const uint4 m0 = md[0], m1 = md[1];
-        unsigned long long key = search::NO_KEY;
+        unsigned long long key = orb::NO_KEY;
         bool in_area = false;
-        for (int32_t j = lane; j < T.n; j += 64) {
-            const int64_t g = (int64_t)T.off + j;
+        for (int32_t j = lane; j < G.n; j += 64) {
+            const int64_t g = (int64_t)G.off + j;
             const float2 k = ((const float2*)in.kp)[g];
-            const int cx = (int)roundf((k.x - T.min_x) * T.w_inv);   // Frame::PosInGrid: the cell the key point was filed under
-            const int cy = (int)roundf((k.y - T.min_y) * T.h_inv);
-            if (cx < 0 || cx >= T.cols || cy < 0 || cy >= T.rows) continue;          // never filed: never found
-            if (cx < min_cx || cx > max_cx || cy < min_cy || cy > max_cy) continue;
-            if (!(fabsf(k.x - u) < r && fabsf(k.y - v) < r)) continue;
+            int cx, cy;
+            if (!orb::cell_of(G, k, cx, cy) || !orb::in_range(cells, cx, cy)) continue;
+            if (!orb::in_window(k, u, v, r)) continue;
             in_area = true;                                          // vIndices holds it (:892)
             const int oct = in.octave[g];
             if (oct < level - 1 || oct > level) continue;
@@ -134,15 +110,13 @@ __global__ __launch_bounds__(256) void k_fuse_best(In in, int64_t n_pair, int32_
                     if ((double)(e2 * T.inv_sigma2[oct]) > 7.8) continue;
                 } else if ((double)(e2 * T.inv_sigma2[oct]) > 5.99) continue;
             }
-            const uint4* d = (const uint4*)(in.desc + 32 * g);
-            const unsigned long long hd = (unsigned)(search::popc128(d[0], m0) + search::popc128(d[1], m1));
-            const unsigned long long kk = (hd << 40) | ((unsigned long long)cx << 33) | ((unsigned long long)cy << 26) | (unsigned long long)j;
+            const unsigned long long kk = orb::make_key(orb::hamming256(in.desc + 32 * g, m0, m1), cx, cy, j);
             key = kk < key ? kk : key;
         }
         key = wave_min(key);
-        if (key != search::NO_KEY) {
-            res_dist = (int32_t)(key >> 40);
-            if (res_dist <= TH_LOW) res_best = (int32_t)(key & (unsigned long long)(search::MAX_KEYPOINTS - 1));   // :952 / :1082
+        if (key != orb::NO_KEY) {
+            res_dist = orb::key_dist(key);
+            if (res_dist <= orb::TH_LOW) res_best = orb::key_index(key);                         // :952 / :1082
             else why = fuse::ABOVE_TH;
         } else {
             why = __ballot(in_area) ? fuse::NONE_ELIGIBLE : fuse::EMPTY;
@@ -154,18 +128,6 @@ __global__ __launch_bounds__(256) void k_fuse_best(In in, int64_t n_pair, int32_
         reason[w] = why;
         level_out[w] = level;
     }
-}
-
-static const char* frame_problem(const qsp_orb_frame& f) {
-    if (f.n < 0) return "negative key-point count";
-    if (f.n > search::MAX_KEYPOINTS) return "more than 2^26 key points in a target";
-    if (f.grid_cols < 1 || f.grid_cols > search::MAX_GRID || f.grid_rows < 1 || f.grid_rows > search::MAX_GRID) return "grid outside 1..64 x 1..64";
-    if (f.n_levels < 1 || f.n_levels > search::MAX_LEVELS) return "n_levels outside 1..16";
-    if (!f.scale_factors) return "null scale_factors";
-    if (f.n && (!f.kp || !f.octave || !f.desc)) return "null key-point array";
-    for (int32_t i = 0; i < f.n; ++i)
-        if (f.octave[i] < 0 || f.octave[i] >= f.n_levels) return "a key point's level outside [0, n_levels)";
-    return nullptr;
 }
 
 }  // namespace fuse
@@ -187,7 +149,7 @@ extern "C" int qsp_fuse_batch(int device, const qsp_fuse_in* in, qsp_fuse_out* o
     int64_t n_slot = 0;
     for (int32_t k = 0; k < nt; ++k) {
         if (in->list_off[k + 1] < in->list_off[k]) return bad(QSP_ERR_INVALID, "list_off must not decrease");
-        const char* why = fuse::frame_problem(in->target[k]);
+        const char* why = orb::orb_frame_problem(in->target[k], false);
         if (why) return bad(QSP_ERR_INVALID, std::string("target: ") + why);
         if ((int64_t)in->u_right_off[k + 1] - (int64_t)in->u_right_off[k] != in->target[k].n)
             return bad(QSP_ERR_INVALID, "u_right_off does not step by the key-point count of the target");
@@ -221,14 +183,8 @@ extern "C" int qsp_fuse_batch(int device, const qsp_fuse_in* in, qsp_fuse_out* o
     for (int32_t k = 0; k < nt; ++k) {
         const qsp_orb_frame& F = in->target[k];
         fuse::TargetP& P = tp[k];
-        P.off = (int32_t)slot; P.n = F.n;
-        P.min_x = F.min_x; P.max_x = F.max_x; P.min_y = F.min_y; P.max_y = F.max_y;
-        P.cols = F.grid_cols; P.rows = F.grid_rows; P.w_inv = F.grid_w_inv; P.h_inv = F.grid_h_inv;
-        P.n_levels = F.n_levels; P.log_scale = F.log_scale;
-        for (int l = 0; l < F.n_levels; ++l) {
-            P.sf[l] = F.scale_factors[l];
-            P.inv_sigma2[l] = in->inv_level_sigma2[16 * (size_t)k + l];
-        }
+        orb::fill_grid(P.g, F, slot);
+        for (int l = 0; l < F.n_levels; ++l) P.inv_sigma2[l] = in->inv_level_sigma2[16 * (size_t)k + l];
         memcpy(P.R, F.Rcw, sizeof P.R);
         memcpy(P.t, F.tcw, sizeof P.t);
         memcpy(P.Ow, in->Ow + 3 * (size_t)k, sizeof P.Ow);

@@ -1,6 +1,7 @@
 // search_bow.hpp -- ORBmatcher::SearchByBoW for ALL candidates in one call: the key-frame overload of LoopClosing::ComputeSim3
 // (reference src/ORBmatcher.cc:522-655, shared_is_source = 1) and the frame overload of Tracking::Relocalization (:159-288,
-// shared_is_source = 0).  Compiled in c_abi.cpp; popc128 is search_sim3.hpp's.
+// shared_is_source = 0).  Compiled in c_abi.cpp; the Hamming distance, the two binary searches, rot_bin and three_maxima are
+// orb_match.hpp's.
 //
 // The reference walks the two DBoW2::FeatureVectors in step and, inside a common vocabulary node, matches every source feature
 // against the node's target features, greedily: a target that an earlier source took is gone (vbMatched2[idx2] /
@@ -22,13 +23,12 @@
 #include <string>
 #include <vector>
 
-#include "search_sim3.hpp"
+#include "orb_match.hpp"
 #include "staging.hpp"
 
 namespace qsp {
 namespace bow {
 
-constexpr int HISTO_LENGTH = 30;
 constexpr unsigned NO_POS = 0xffffffffu;
 
 struct FrameB {                        // one per frame: 0 is the shared one, 1 + c the frame of candidate c
@@ -61,23 +61,14 @@ __global__ __launch_bounds__(256) void k_bow_match(In in, int64_t n_work, int32_
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n_work) return;
-    int lo = 0, hi = in.n_cand;                          // the candidate whose range holds w (empty ranges are stepped over)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (in.work_off[mid] <= w) lo = mid; else hi = mid;
-    }
-    const int c = lo;
+    const int c = orb::owner_of(in.work_off, in.n_cand, w);
     const int32_t k = (int32_t)(w - in.work_off[c]);     // the node's place in the source frame's list
     const FrameB S = in.frame[in.shared_is_source ? 0 : 1 + c];
     const FrameB T = in.frame[in.shared_is_source ? 1 + c : 0];
     // the reference's lower_bound walk over the two maps visits exactly the ids both hold
     const int32_t id = in.node_id[S.node_at + k];
     const int32_t* tid = in.node_id + T.node_at;
-    int32_t a = 0, b = T.n_nodes;
-    while (a < b) {
-        const int32_t mid = a + ((b - a) >> 1);
-        if (tid[mid] < id) a = mid + 1; else b = mid;
-    }
+    const int32_t a = orb::lower_bound_id(tid, T.n_nodes, id);
     if (a >= T.n_nodes || tid[a] != id) return;
     const int32_t s0 = in.node_off[S.noff_at + k], s1 = in.node_off[S.noff_at + k + 1];
     const int32_t t0 = in.node_off[T.noff_at + a], nt = in.node_off[T.noff_at + a + 1] - t0;
@@ -98,8 +89,7 @@ __global__ __launch_bounds__(256) void k_bow_match(In in, int64_t n_work, int32_
             const int32_t t = tf[j];
             const int64_t g = (int64_t)T.off + t;
             if (!in.elig[g] || taken[taken_at + t]) continue;
-            const uint4* d = (const uint4*)(in.desc + 32 * g);
-            const int hd = search::popc128(d[0], m0) + search::popc128(d[1], m1);
+            const int hd = orb::hamming256(in.desc + 32 * g, m0, m1);
             if (hd < d1) { d2 = d1; d1 = hd; p1 = (unsigned)j; }       // :586-595
             else if (hd < d2) d2 = hd;
         }
@@ -130,24 +120,12 @@ __global__ __launch_bounds__(256) void k_bow_match(In in, int64_t n_work, int32_
     }
 }
 
-// :607-614 / :238-245.  factor = 1.0f / 30, so rot * factor lies in [0, 12]: only bins 0..12 ever fill and the `bin == 30` wrap
-// never fires (a reference quirk, kept).  -1: an angle pair outside the reference's domain (its assert), counted in no bin.
-__device__ inline int rot_bin(float a_src, float a_tgt) {
-#pragma clang fp contract(off)
-    float rot = a_src - a_tgt;
-    if (rot < 0.0f) rot += 360.0f;
-    const float r = roundf(rot * (1.0f / HISTO_LENGTH));                // half away from zero
-    if (!(r >= 0.0f && r <= (float)HISTO_LENGTH)) return -1;
-    const int bin = (int)r;
-    return bin == HISTO_LENGTH ? 0 : bin;
-}
-
 // one workgroup per candidate
 __global__ __launch_bounds__(256) void k_bow_rot(In in, const int32_t* __restrict__ match_raw, int32_t* __restrict__ match,
                                                  int32_t* __restrict__ n_matches, int32_t* __restrict__ hist_out,
                                                  int32_t* __restrict__ ind_out) {
 #pragma clang fp contract(off)
-    __shared__ int hist[HISTO_LENGTH];
+    __shared__ int hist[orb::HISTO_LENGTH];
     __shared__ int ind[3];
     __shared__ int count;
     const int c = blockIdx.x, tid = threadIdx.x;
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(256) void k_bow_rot(In in, const int32_t* __restric
     const FrameB T = in.frame[in.shared_is_source ? 1 + c : 0];
     int64_t out_at, taken_at;
     cand_places(in, c, &out_at, &taken_at);
-    if (tid < HISTO_LENGTH) hist[tid] = 0;
+    if (tid < orb::HISTO_LENGTH) hist[tid] = 0;
     if (tid < 3) ind[tid] = -1;
     if (tid == 0) count = 0;
     __syncthreads();
@@ -163,29 +141,18 @@ __global__ __launch_bounds__(256) void k_bow_rot(In in, const int32_t* __restric
         for (int32_t i = tid; i < S.n; i += 256) {
             const int32_t m = match_raw[out_at + i];
             if (m < 0) continue;
-            const int bin = rot_bin(in.angle[(int64_t)S.off + i], in.angle[(int64_t)T.off + m]);
+            const int bin = orb::rot_bin(in.angle[(int64_t)S.off + i], in.angle[(int64_t)T.off + m]);
             if (bin >= 0) atomicAdd(&hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {                                   // ComputeThreeMaxima, :1601-1642
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < HISTO_LENGTH; ++i) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
-            ind[0] = i1; ind[1] = i2; ind[2] = i3;
-        }
+        if (tid == 0) orb::three_maxima(hist, ind);
         __syncthreads();
     }
     for (int32_t i = tid; i < S.n; i += 256) {
         const int32_t m = match_raw[out_at + i];
         bool keep = m >= 0;
         if (keep && in.check_ori) {
-            const int bin = rot_bin(in.angle[(int64_t)S.off + i], in.angle[(int64_t)T.off + m]);
+            const int bin = orb::rot_bin(in.angle[(int64_t)S.off + i], in.angle[(int64_t)T.off + m]);
             keep = bin >= 0 && (bin == ind[0] || bin == ind[1] || bin == ind[2]);
         }
         match[out_at + i] = keep ? m : -1;
@@ -193,7 +160,7 @@ __global__ __launch_bounds__(256) void k_bow_rot(In in, const int32_t* __restric
     }
     __syncthreads();
     if (tid == 0) n_matches[c] = count;
-    if (tid < HISTO_LENGTH) hist_out[(int64_t)c * HISTO_LENGTH + tid] = hist[tid];
+    if (tid < orb::HISTO_LENGTH) hist_out[(int64_t)c * orb::HISTO_LENGTH + tid] = hist[tid];
     if (tid < 3) ind_out[(int64_t)c * 3 + tid] = ind[tid];
 }
 
@@ -269,7 +236,7 @@ extern "C" int qsp_search_by_bow_batch(int device, const qsp_search_bow_in* in, 
     const size_t a_taken = L.take<uint8_t>((size_t)n_taken);
     L.begin_down();
     const size_t a_match = L.take<int32_t>(no), a_raw = L.take<int32_t>(no), a_dist = L.take<int32_t>(no), a_count = L.take<int32_t>((size_t)nc),
-                 a_hist = L.take<int32_t>((size_t)nc * bow::HISTO_LENGTH), a_ind = L.take<int32_t>((size_t)nc * 3);
+                 a_hist = L.take<int32_t>((size_t)nc * orb::HISTO_LENGTH), a_ind = L.take<int32_t>((size_t)nc * 3);
     std::vector<char> up, down;
     if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes()))
         return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_bow_batch: out of host memory for the staging buffers");
@@ -331,7 +298,7 @@ extern "C" int qsp_search_by_bow_batch(int device, const qsp_search_bow_in* in, 
         if (out->dist) memcpy(out->dist, h + L.in_down(a_dist), 4 * no);
     }
     memcpy(out->n_matches, h + L.in_down(a_count), 4 * (size_t)nc);
-    if (out->hist) memcpy(out->hist, h + L.in_down(a_hist), 4 * (size_t)nc * bow::HISTO_LENGTH);
+    if (out->hist) memcpy(out->hist, h + L.in_down(a_hist), 4 * (size_t)nc * orb::HISTO_LENGTH);
     if (out->ind) memcpy(out->ind, h + L.in_down(a_ind), 4 * (size_t)nc * 3);
     return QSP_OK;
 }

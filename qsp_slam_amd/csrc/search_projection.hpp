@@ -1,8 +1,7 @@
 // search_projection.hpp -- the tracking thread's two projection searches with the result of the reference's SERIAL loop:
 // LOCAL = Frame::isInFrustum (reference src/Frame.cc:306-362) + ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th)
 // (src/ORBmatcher.cc:45-129), LAST = ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, th, bMono) (:1328-1470).
-// Compiled in c_abi.cpp after search_sim3.hpp and fuse.hpp, whose rowdot, popc128, key layout and limits it uses as they are; the
-// wave reduction is wave.hpp's.
+// Compiled in c_abi.cpp; the steps it shares with the other matchers are orb_match.hpp's.
 //
 // The inner loop of both skips a key-point slot whose map point has observations, and earlier iterations of the same loop write
 // those slots: source i sees slot idx as taken when it was taken at entry (slot_blocked) or when a source j < i whose own point has
@@ -17,8 +16,7 @@
 // k_proj_gate (one lane per source) computes what no round changes: projection, gates, level or octave window, radius, cell range.
 // k_proj_round (one wave per source, four per workgroup; a wave whose source the gates refused leaves at once) strides over the
 // frame's key points as k_fuse_best does and reduces to the two smallest keys.  The action phase (slot table, histogram,
-// ComputeThreeMaxima, nulling) is index work and runs on the host after the download; search_bow.hpp's rot_bin and three-maxima
-// loop are device code inside its kernel, so the host has its own copy below rather than a changed search_bow.hpp.
+// ComputeThreeMaxima, nulling) is index work and runs on the host after the download: Action::run, for both entry points.
 //
 // Every function below evaluates with contraction OFF: the float32 operations of the reference in its order.
 #pragma once
@@ -27,33 +25,26 @@
 #include <string>
 #include <vector>
 
-#include "fuse.hpp"
-#include "search_sim3.hpp"
-#include "wave.hpp"
+#include "orb_match.hpp"
+#include "staging.hpp"
 
 namespace qsp {
 namespace proj {
 
-constexpr int HISTO_LENGTH = 30;
 constexpr int32_t NO_CLAIM = 0x7fffffff;
 enum Mode : int32_t { LOCAL = 0, LAST = 1, RELOC = 2, SIM3 = 3 };     // RELOC, SIM3: search_projection_kf.hpp, whose public 0 / 1 map onto them
 enum Reason : int32_t { MATCHED = 0, INVALID_SRC, Z_NEG, OUTSIDE, DISTANCE, ANGLE, NONFINITE, EMPTY, NONE_ELIGIBLE, ABOVE_TH, RATIO };
 
 struct Rec {                          // what k_proj_gate leaves per source for every round
     float u, v, ur, radius;
-    int32_t min_cx, max_cx, min_cy, max_cy;
+    orb::CellRange cells;
     int32_t lvl_min, lvl_max;         // the octave window, both ends included
     int32_t reason;                   // MATCHED: the rounds search for it
 };
 
 struct In {
-    int32_t mode, n, n_src;
-    float min_x, max_x, min_y, max_y;
-    int32_t cols, rows;
-    float w_inv, h_inv;
-    int32_t n_levels;
-    float log_scale;
-    float sf[search::MAX_LEVELS];
+    orb::GridP g;                     // the frame: its n key points are the arrays below from their start (off = 0)
+    int32_t mode, n_src;
     float R[9], t[3], Ow[3];
     float K[5];                       // fx fy cx cy bf
     float th, nn_ratio, view_cos_limit;
@@ -92,7 +83,7 @@ __global__ __launch_bounds__(256) void k_proj_gate(In in, Rec* __restrict__ rec,
     else {
         const float* X = in.Xw + 3 * i;
         float p[3];
-        for (int k = 0; k < 3; ++k) p[k] = search::rowdot(in.R + 3 * k, X) + in.t[k];        // Rcw * P + tcw
+        for (int k = 0; k < 3; ++k) p[k] = orb::rowdot(in.R + 3 * k, X) + in.t[k];        // Rcw * P + tcw
         float invz;
         if (in.mode == LOCAL) {
             if (p[2] < 0.0f) why = Z_NEG;                            // Frame.cc:320 (-0.0 passes)
@@ -104,53 +95,40 @@ __global__ __launch_bounds__(256) void k_proj_gate(In in, Rec* __restrict__ rec,
         const float u = in.K[0] * p[0] * invz + in.K[2], v = in.K[1] * p[1] * invz + in.K[3];
         rc.u = u; rc.v = v; rc.ur = u - in.K[4] * invz;
         if (why == MATCHED) {
-            if (u < in.min_x || u > in.max_x || v < in.min_y || v > in.max_y) why = OUTSIDE;   // closed at both ends
+            if (u < in.g.min_x || u > in.g.max_x || v < in.g.min_y || v > in.g.max_y) why = OUTSIDE;   // closed at both ends
             else if (u != u || v != v) why = NONFINITE;              // passes every compare above; the reference goes on to floor(NaN)
         }
         float r = 0.f;
         if (why == MATCHED && in.mode == LOCAL) {
-            float PO[3];
-            for (int k = 0; k < 3; ++k) PO[k] = X[k] - in.Ow[k];
-            const float d3 = (float)sqrt(((double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1]) + (double)PO[2] * (double)PO[2]);
-            const float* Pn = in.normal + 3 * i;
-            const double dot = ((double)PO[0] * (double)Pn[0] + (double)PO[1] * (double)Pn[1]) + (double)PO[2] * (double)Pn[2];
+            float d3;
+            double dot;
+            orb::view_geometry(X, in.Ow, in.normal + 3 * i, &d3, &dot);
             view_cos = (float)(dot / (double)d3);
             if (d3 < in.dist_min_inv[i] || d3 > in.dist_max_inv[i]) why = DISTANCE;
             else if (view_cos < in.view_cos_limit) why = ANGLE;
             else {
-                // MapPoint::PredictScale(dist, frame), MapPoint.cc:391-406
-                const float ratio = in.dist_max[i] / d3;
-                const float fl = ceilf(logf(ratio) / in.log_scale);
+                float fl;
+                level = orb::predict_scale(in.dist_max[i], d3, in.g.log_scale, in.g.n_levels, &fl);
                 if (d3 != d3 || view_cos != view_cos || fl != fl) why = NONFINITE;
                 else {
-                    level = fl < 0.f ? 0 : (fl >= (float)in.n_levels ? in.n_levels - 1 : (int)fl);
                     in_view = 1;
                     r = (double)view_cos > 0.998 ? 2.5f : 4.0f;      // RadiusByViewingCos
                     if ((double)in.th != 1.0) r = r * in.th;         // bFactor
-                    r = r * in.sf[level];
+                    r = r * in.g.sf[level];
                     rc.lvl_min = level - 1; rc.lvl_max = level;
                 }
             }
         } else if (why == MATCHED) {
             const int oc = in.src_octave[i];                         // checked on the host: inside [0, n_levels)
-            r = in.th * in.sf[oc];
-            if (in.forward) { rc.lvl_min = oc; rc.lvl_max = search::MAX_LEVELS; }
+            r = in.th * in.g.sf[oc];
+            if (in.forward) { rc.lvl_min = oc; rc.lvl_max = orb::MAX_LEVELS; }
             else if (in.backward) { rc.lvl_min = 0; rc.lvl_max = oc; }
             else { rc.lvl_min = oc - 1; rc.lvl_max = oc + 1; }
         }
         if (why == MATCHED) {
             rc.radius = r;
-            // Frame::GetFeaturesInArea's cell range and early returns, Frame.cc:369-383
-            const float ax = ((u - in.min_x) - r) * in.w_inv, bx = ((u - in.min_x) + r) * in.w_inv;
-            const float ay = ((v - in.min_y) - r) * in.h_inv, by = ((v - in.min_y) + r) * in.h_inv;
-            if (ax != ax || bx != bx || ay != ay || by != by) why = NONFINITE;               // a NaN radius
-            else {
-                rc.min_cx = max(0, (int)floorf(ax));
-                rc.max_cx = min(in.cols - 1, (int)ceilf(bx));
-                rc.min_cy = max(0, (int)floorf(ay));
-                rc.max_cy = min(in.rows - 1, (int)ceilf(by));
-                if (rc.min_cx >= in.cols || rc.max_cx < 0 || rc.min_cy >= in.rows || rc.max_cy < 0) why = EMPTY;
-            }
+            const orb::Cells cr = orb::cell_range<true>(in.g, u, v, r, rc.cells);
+            if (cr != orb::CELLS_OK) why = cr == orb::CELLS_EMPTY ? EMPTY : NONFINITE;       // NONFINITE: a NaN radius
         }
     }
     rc.reason = why;
@@ -182,18 +160,16 @@ __global__ __launch_bounds__(256) void k_proj_round(In in, const Rec* __restrict
     if (rc.reason != MATCHED) return;                                // what k_proj_gate wrote for it stands
     const uint4* md = (const uint4*)(in.src_desc + 32 * i);
     const uint4 m0 = md[0], m1 = md[1];
-    unsigned long long k1 = search::NO_KEY, k2 = search::NO_KEY;
+    unsigned long long k1 = orb::NO_KEY, k2 = orb::NO_KEY;
     bool in_area = false;
-    for (int32_t j = lane; j < in.n; j += 64) {
+    for (int32_t j = lane; j < in.g.n; j += 64) {
         const float2 k = ((const float2*)in.kp)[j];
-        const int cx = (int)roundf((k.x - in.min_x) * in.w_inv);     // Frame::PosInGrid: the cell the key point was filed under
-        const int cy = (int)roundf((k.y - in.min_y) * in.h_inv);
-        if (cx < 0 || cx >= in.cols || cy < 0 || cy >= in.rows) continue;                    // never filed: never found
-        if (cx < rc.min_cx || cx > rc.max_cx || cy < rc.min_cy || cy > rc.max_cy) continue;
+        int cx, cy;
+        if (!orb::cell_of(in.g, k, cx, cy) || !orb::in_range(rc.cells, cx, cy)) continue;
         const int oct = in.octave[j];
         const bool lvl_out = oct < rc.lvl_min || oct > rc.lvl_max;
         if (lvl_out && in.mode != SIM3) continue;                    // Frame::GetFeaturesInArea filters the levels itself
-        if (!(fabsf(k.x - rc.u) < rc.radius && fabsf(k.y - rc.v) < rc.radius)) continue;
+        if (!orb::in_window(k, rc.u, rc.v, rc.radius)) continue;
         in_area = true;                                              // vIndices holds it
         if (in.slot_blocked[j] || claim_prev[j] < i) continue;       // :87-89 / :1403-1405 / :1541 / :375
         if (lvl_out) continue;                                       // SIM3: KeyFrame::GetFeaturesInArea has no level filter, :380 has
@@ -201,10 +177,9 @@ __global__ __launch_bounds__(256) void k_proj_round(In in, const Rec* __restrict
             const float kr = in.u_right[j];
             if (kr > 0 && fabsf(rc.ur - kr) > rc.radius) continue;   // :91-96 / :1407-1413
         }
-        const uint4* d = (const uint4*)(in.desc + 32 * (int64_t)j);
-        const unsigned long long hd = (unsigned)(search::popc128(d[0], m0) + search::popc128(d[1], m1));
+        const int hd = orb::hamming256(in.desc + 32 * (int64_t)j, m0, m1);
         if (hd >= 256) continue;                                     // never below the initial bestDist
-        const unsigned long long kk = (hd << 40) | ((unsigned long long)cx << 33) | ((unsigned long long)cy << 26) | (unsigned long long)j;
+        const unsigned long long kk = orb::make_key(hd, cx, cy, j);
         if (kk < k1) { k2 = k1; k1 = kk; }
         else if (kk < k2) k2 = kk;
     }
@@ -212,16 +187,15 @@ __global__ __launch_bounds__(256) void k_proj_round(In in, const Rec* __restrict
     for (int m = 32; m >= 1; m >>= 1) merge2(k1, k2, __shfl_xor(k1, m, 64), __shfl_xor(k2, m, 64));
     const bool any_area = __ballot(in_area) != 0;
     if (lane != 0) return;
-    const unsigned long long idx_mask = (unsigned long long)(search::MAX_KEYPOINTS - 1);
     int32_t pick = -1, d1 = -1, d2 = -1, l1 = -1, l2 = -1, why = MATCHED;
-    if (k1 == search::NO_KEY) why = any_area ? NONE_ELIGIBLE : EMPTY;
+    if (k1 == orb::NO_KEY) why = any_area ? NONE_ELIGIBLE : EMPTY;
     else {
-        const int32_t b = (int32_t)(k1 & idx_mask);
-        d1 = (int32_t)(k1 >> 40);
+        const int32_t b = orb::key_index(k1);
+        d1 = orb::key_dist(k1);
         l1 = in.octave[b];
-        if (k2 != search::NO_KEY) {
-            d2 = (int32_t)(k2 >> 40);
-            l2 = in.octave[(int32_t)(k2 & idx_mask)];
+        if (k2 != orb::NO_KEY) {
+            d2 = orb::key_dist(k2);
+            l2 = in.octave[orb::key_index(k2)];
         }
         if (d1 > in.accept_th) why = ABOVE_TH;
         else if (in.mode == LOCAL && l1 == l2 && (float)d1 > in.nn_ratio * (float)d2) why = RATIO;   // :120 (no second: levels differ)
@@ -235,36 +209,11 @@ __global__ __launch_bounds__(256) void k_proj_round(In in, const Rec* __restrict
     if (pick >= 0 && (in.mode >= RELOC || in.src_blocks[i])) atomicMin(claim_next + pick, (int32_t)i);   // RELOC, SIM3: every source blocks
 }
 
-// :1433-1439 on the host.  -1: outside the reference's domain (its assert), counted in no bin
-inline int rot_bin_host(float a_src, float a_tgt) {
-    volatile float rot = a_src - a_tgt;                              // (volatile: one float32 operation at a time on any host compiler)
-    if (rot < 0.0f) rot = rot + 360.0f;
-    volatile float scaled = rot * (1.0f / HISTO_LENGTH);
-    const float r = roundf(scaled);                                  // half away from zero
-    if (!(r >= 0.0f && r <= (float)HISTO_LENGTH)) return -1;
-    const int bin = (int)r;
-    return bin == HISTO_LENGTH ? 0 : bin;
-}
-
-// ComputeThreeMaxima, :1601-1642, on bin counts
-inline void three_maxima_host(const int32_t* hist, int32_t* ind) {
-    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int i = 0; i < HISTO_LENGTH; ++i) {
-        const int s = hist[i];
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-        else if (s > max3) { max3 = s; i3 = i; }
-    }
-    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-    else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
-    ind[0] = i1; ind[1] = i2; ind[2] = i3;
-}
-
 // The rounds on the host, for both entry points: round 1 sees the initial blocks only, every round reads the 4-byte `changed` word,
 // and the claim tables swap.  claim0 and claim1 hold n int32 each; *n_rounds counts the launches.
 inline int run_rounds(const char* who, const In& k, const Rec* d_rec, int32_t* claim0, int32_t* claim1, int32_t* d_chg, const Out& o,
                       int32_t* n_rounds_out) {
-    const size_t zn = (size_t)k.n, zs = (size_t)k.n_src;
+    const size_t zn = (size_t)k.g.n, zs = (size_t)k.n_src;
     int32_t* claim[2] = {claim0, claim1};
     if (zn) QSP_HIP(hipMemsetD32Async((hipDeviceptr_t)claim[0], NO_CLAIM, zn, 0));          // round 1: the initial blocks only
     int32_t n_rounds = 0;
@@ -284,6 +233,51 @@ inline int run_rounds(const char* who, const In& k, const Rec* d_rec, int32_t* c
     return QSP_OK;
 }
 
+// The action phase on the host, for both entry points: the sources in order take their slots, the last writer of a slot stays
+// (:123 / :1428); then the orientation check (:1433-1467 / :1562-1596): bins, histogram, three maxima, nulling.
+struct Action {
+    std::vector<int32_t> slot_src, bin;                              // [n], [n_src]
+    int32_t n_matches = 0, hist[orb::HISTO_LENGTH] = {}, ind[3] = {-1, -1, -1};
+
+    bool init(size_t n, size_t n_src) {
+        try { slot_src.assign(n, -1); bin.assign(n_src, -1); } catch (const std::exception&) { return false; }
+        return true;
+    }
+    // ori: the orientation check, over src_angle and kp_angle.  exclusive: every source blocks (RELOC, SIM3), so no two sources hold
+    // one slot and none holds a slot taken at entry.  Returns what went wrong, or null
+    const char* run(const int32_t* choice, bool ori, const float* src_angle, const float* kp_angle, const uint8_t* slot_blocked, bool exclusive) {
+        const int32_t ns = (int32_t)bin.size(), n = (int32_t)slot_src.size();
+        for (int32_t i = 0; i < ns; ++i) {
+            const int32_t c = choice[i];
+            if (c < 0) continue;
+            if (c >= n) return "internal error: a choice outside the frame";
+            if (exclusive && (slot_src[c] != -1 || slot_blocked[c])) return "internal error: a taken slot chosen";
+            slot_src[c] = i;
+            ++n_matches;
+            if (ori) {
+                bin[i] = orb::rot_bin(src_angle[i], kp_angle[c]);
+                if (bin[i] >= 0) ++hist[bin[i]];
+            }
+        }
+        if (ori) {
+            orb::three_maxima(hist, ind);
+            for (int32_t i = 0; i < ns; ++i)
+                if (bin[i] >= 0 && bin[i] != ind[0] && bin[i] != ind[1] && bin[i] != ind[2]) {
+                    slot_src[choice[i]] = -2;                        // also where a later source over-wrote it, as the reference does
+                    --n_matches;
+                }
+        }
+        return nullptr;
+    }
+    template <class O>
+    void give(O* out) const {
+        if (!slot_src.empty()) memcpy(out->slot_src, slot_src.data(), 4 * slot_src.size());
+        out->n_matches = n_matches;
+        memcpy(out->hist, hist, sizeof hist);
+        memcpy(out->ind, ind, sizeof ind);
+    }
+};
+
 }  // namespace proj
 }  // namespace qsp
 
@@ -294,12 +288,12 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
     if (!in) return bad(QSP_ERR_INVALID, "null input");
     if (in->n_src < 0) return bad(QSP_ERR_INVALID, "negative source count");
     if (in->n_src == 0) return QSP_OK;
-    if (in->n_src > search::MAX_KEYPOINTS) return bad(QSP_ERR_INVALID, "more than 2^26 sources");
+    if (in->n_src > orb::MAX_KEYPOINTS) return bad(QSP_ERR_INVALID, "more than 2^26 sources");
     if (in->mode != proj::LOCAL && in->mode != proj::LAST) return bad(QSP_ERR_INVALID, "unknown mode");
     const bool local = in->mode == proj::LOCAL, ori = !local && in->check_orientation;
     if (!in->frame) return bad(QSP_ERR_INVALID, "null frame");
     const qsp_orb_frame& F = *in->frame;
-    const char* why = fuse::frame_problem(F);
+    const char* why = orb::orb_frame_problem(F, false);
     if (why) return bad(QSP_ERR_INVALID, std::string("frame: ") + why);
     if (F.n && (!in->u_right || !in->slot_blocked || (ori && !in->kp_angle))) return bad(QSP_ERR_INVALID, "null key-point array");
     if (!in->src_valid || !in->src_blocks || !in->Xw || !in->desc) return bad(QSP_ERR_INVALID, "null source array");
@@ -331,9 +325,9 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
                  a_l1 = L.take<int32_t>(zs), a_l2 = L.take<int32_t>(zs), a_view = L.take<uint8_t>(zs), a_px = L.take<float>(zs),
                  a_py = L.take<float>(zs), a_pxr = L.take<float>(zs), a_cos = L.take<float>(zs), a_lvl = L.take<int32_t>(zs);
     std::vector<char> up, down;
-    std::vector<int32_t> slot_src, bin;
+    proj::Action act;
     if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes())) return bad(QSP_ERR_INVALID, "out of host memory for the staging buffers");
-    try { slot_src.assign(zn, -1); bin.assign(zs, -1); } catch (const std::exception&) { return bad(QSP_ERR_INVALID, "out of host memory"); }
+    if (!act.init(zn, zs)) return bad(QSP_ERR_INVALID, "out of host memory");
     put(up, a_kp, F.kp, 8 * zn); put(up, a_oct, F.octave, 4 * zn); put(up, a_desc, F.desc, 32 * zn); put(up, a_ur, in->u_right, 4 * zn);
     put(up, a_blk, in->slot_blocked, zn); put(up, a_val, in->src_valid, zs); put(up, a_sblk, in->src_blocks, zs);
     put(up, a_Xw, in->Xw, 12 * zs); put(up, a_sd, in->desc, 32 * zs);
@@ -346,14 +340,11 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
     QSP_TRY(blk.upload(up.data(), L.up_bytes()));
     char* d = blk.data();
     proj::In k = {};
-    k.mode = in->mode; k.n = n; k.n_src = ns;
-    k.min_x = F.min_x; k.max_x = F.max_x; k.min_y = F.min_y; k.max_y = F.max_y;
-    k.cols = F.grid_cols; k.rows = F.grid_rows; k.w_inv = F.grid_w_inv; k.h_inv = F.grid_h_inv;
-    k.n_levels = F.n_levels; k.log_scale = F.log_scale;
-    for (int l = 0; l < F.n_levels; ++l) k.sf[l] = F.scale_factors[l];
+    orb::fill_grid(k.g, F, 0);
+    k.mode = in->mode; k.n_src = ns;
     memcpy(k.R, F.Rcw, sizeof k.R); memcpy(k.t, F.tcw, sizeof k.t); memcpy(k.Ow, in->Ow, sizeof k.Ow); memcpy(k.K, in->K, sizeof k.K);
     k.th = in->th; k.nn_ratio = in->nn_ratio; k.view_cos_limit = in->view_cos_limit;
-    k.accept_th = search::TH_HIGH; k.no_right = 0;
+    k.accept_th = orb::TH_HIGH; k.no_right = 0;
     if (!local) {
         // :1341-1349: twc = -Rcw^T tcw (a product scaled by -1: the double row sum rounded once, then negated), tlc = Rlw twc + tlw
         float twc[3];
@@ -382,32 +373,12 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
     QSP_TRY(proj::run_rounds(who, k, d_rec, ptr<int32_t>(d, a_c0), ptr<int32_t>(d, a_c1), ptr<int32_t>(d, a_chg), o, &n_rounds));
     QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
     const char* h = down.data();
-    // the action phase: the sources in order, the last writer of a slot stays (:123 / :1428)
     const int32_t* choice = ptr<int32_t>(h, L.in_down(a_choice));
-    int32_t n_matches = 0, hist[proj::HISTO_LENGTH] = {}, ind[3] = {-1, -1, -1};
-    for (int32_t i = 0; i < ns; ++i) {
-        const int32_t c = choice[i];
-        if (c < 0) continue;
-        if (c >= n) return bad(QSP_ERR_DEVICE, "internal error: a choice outside the frame");
-        slot_src[c] = i;
-        ++n_matches;
-        if (ori) {
-            bin[i] = proj::rot_bin_host(in->src_angle[i], in->kp_angle[c]);
-            if (bin[i] >= 0) ++hist[bin[i]];
-        }
-    }
-    if (ori) {                                                       // :1447-1467
-        proj::three_maxima_host(hist, ind);
-        for (int32_t i = 0; i < ns; ++i)
-            if (bin[i] >= 0 && bin[i] != ind[0] && bin[i] != ind[1] && bin[i] != ind[2]) {
-                slot_src[choice[i]] = -2;                            // also where a later source over-wrote it, as the reference does
-                --n_matches;
-            }
-    }
+    why = act.run(choice, ori, in->src_angle, in->kp_angle, in->slot_blocked, false);
+    if (why) return bad(QSP_ERR_DEVICE, why);
     // outputs are written only once everything has succeeded
     memcpy(out->choice, choice, 4 * zs);
     memcpy(out->dist, h + L.in_down(a_dist), 4 * zs);
-    if (n) memcpy(out->slot_src, slot_src.data(), 4 * zn);
     if (local) {
         memcpy(out->in_view, h + L.in_down(a_view), zs);
         memcpy(out->proj_x, h + L.in_down(a_px), 4 * zs); memcpy(out->proj_y, h + L.in_down(a_py), 4 * zs);
@@ -418,10 +389,8 @@ extern "C" int qsp_search_by_projection(int device, const qsp_search_proj_in* in
     if (local && out->dist2) memcpy(out->dist2, h + L.in_down(a_d2), 4 * zs);
     if (local && out->level_best) memcpy(out->level_best, h + L.in_down(a_l1), 4 * zs);
     if (local && out->level2) memcpy(out->level2, h + L.in_down(a_l2), 4 * zs);
-    if (ori && out->bin) memcpy(out->bin, bin.data(), 4 * zs);
-    out->n_matches = n_matches;
-    memcpy(out->hist, hist, sizeof hist);
-    memcpy(out->ind, ind, sizeof ind);
+    if (ori && out->bin) memcpy(out->bin, act.bin.data(), 4 * zs);
+    act.give(out);
     out->n_rounds = n_rounds;
     return QSP_OK;
 }

@@ -2,7 +2,7 @@
 // SERIAL loop: RELOC = ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th,
 // ORBdist) (reference src/ORBmatcher.cc:1472-1599, Tracking::Relocalization), SIM3 = SearchByProjection(KeyFrame* pKF, cv::Mat Scw,
 // const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, th) (:290-403, LoopClosing::ComputeSim3).  Compiled in c_abi.cpp
-// after search_projection.hpp, whose Rec, In, Out, k_proj_round, run_rounds, rot_bin_host and three_maxima_host it uses as they are.
+// after search_projection.hpp, whose Rec, In, Out, k_proj_round, run_rounds and Action it uses as they are.
 //
 // Both loops skip a slot that holds ANY point (RELOC: CurrentFrame.mvpMapPoints[i2], SIM3: vpMatched[idx]) and every matched source
 // writes its point there, so every source blocks: the fixed point of search_projection.hpp with src_blocks all ones.  Two sources
@@ -32,12 +32,12 @@ __global__ __launch_bounds__(256) void k_proj_gate_kf(In in, Rec* __restrict__ r
     else {
         const float* X = in.Xw + 3 * i;
         float p[3];
-        for (int k = 0; k < 3; ++k) p[k] = search::rowdot(in.R + 3 * k, X) + in.t[k];        // Rcw * P + tcw
+        for (int k = 0; k < 3; ++k) p[k] = orb::rowdot(in.R + 3 * k, X) + in.t[k];        // Rcw * P + tcw
         float u, v;
         if (in.mode == RELOC) {
             const float invz = (float)(1.0 / (double)p[2]);          // :1502, and no test of its sign
             u = in.K[0] * p[0] * invz + in.K[2]; v = in.K[1] * p[1] * invz + in.K[3];
-            if (u < in.min_x || u > in.max_x || v < in.min_y || v > in.max_y) why = OUTSIDE;  // :1507-1510, closed at both ends
+            if (u < in.g.min_x || u > in.g.max_x || v < in.g.min_y || v > in.g.max_y) why = OUTSIDE;  // :1507-1510, closed at both ends
             else if (u != u || v != v) why = NONFINITE;              // passes every compare above; the reference goes on to floor(NaN)
         } else {
             if (p[2] < 0.0f) why = Z_NEG;                            // :327 (-0.0 passes)
@@ -45,13 +45,12 @@ __global__ __launch_bounds__(256) void k_proj_gate_kf(In in, Rec* __restrict__ r
             const float x = p[0] * invz, y = p[1] * invz;
             u = in.K[0] * x + in.K[2]; v = in.K[1] * y + in.K[3];
             // KeyFrame::IsInImage, half-open; a NaN fails it, as in the reference
-            if (why == MATCHED && !(u >= in.min_x && u < in.max_x && v >= in.min_y && v < in.max_y)) why = OUTSIDE;
+            if (why == MATCHED && !(u >= in.g.min_x && u < in.g.max_x && v >= in.g.min_y && v < in.g.max_y)) why = OUTSIDE;
         }
         rc.u = u; rc.v = v; rc.ur = 0.f;
         if (why == MATCHED) {
             float PO[3];
-            for (int k = 0; k < 3; ++k) PO[k] = X[k] - in.Ow[k];
-            const float d3 = (float)sqrt(((double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1]) + (double)PO[2] * (double)PO[2]);
+            const float d3 = orb::view_geometry(X, in.Ow, PO);
             if (d3 < in.dist_min_inv[i] || d3 > in.dist_max_inv[i]) why = DISTANCE;
             if (why == MATCHED && in.mode == SIM3) {
                 const float* Pn = in.normal + 3 * i;
@@ -59,28 +58,17 @@ __global__ __launch_bounds__(256) void k_proj_gate_kf(In in, Rec* __restrict__ r
                 if (dot < 0.5 * (double)d3) why = ANGLE;             // :354
             }
             if (why == MATCHED) {
-                // MapPoint::PredictScale(dist, frame), MapPoint.cc:374-406
-                const float ratio = in.dist_max[i] / d3;
-                const float fl = ceilf(logf(ratio) / in.log_scale);
+                float fl;
+                level = orb::predict_scale(in.dist_max[i], d3, in.g.log_scale, in.g.n_levels, &fl);
                 if (d3 != d3 || fl != fl) why = NONFINITE;
                 else {
-                    level = fl < 0.f ? 0 : (fl >= (float)in.n_levels ? in.n_levels - 1 : (int)fl);
-                    const float r = in.th * in.sf[level];
+                    const float r = in.th * in.g.sf[level];
                     rc.radius = r;
                     rc.lvl_min = level - 1;
                     rc.lvl_max = in.mode == RELOC ? level + 1 : level;                       // :1528 / :380
-                    // GetFeaturesInArea's cell range and early returns, Frame.cc:369-383 and KeyFrame.cc:575-589
-                    const float ax = ((u - in.min_x) - r) * in.w_inv, bx = ((u - in.min_x) + r) * in.w_inv;
-                    const float ay = ((v - in.min_y) - r) * in.h_inv, by = ((v - in.min_y) + r) * in.h_inv;
-                    if (ax != ax || bx != bx || ay != ay || by != by) why = NONFINITE;       // a NaN radius
-                    else {
-                        gated = true;
-                        rc.min_cx = max(0, (int)floorf(ax));
-                        rc.max_cx = min(in.cols - 1, (int)ceilf(bx));
-                        rc.min_cy = max(0, (int)floorf(ay));
-                        rc.max_cy = min(in.rows - 1, (int)ceilf(by));
-                        if (rc.min_cx >= in.cols || rc.max_cx < 0 || rc.min_cy >= in.rows || rc.max_cy < 0) why = EMPTY;
-                    }
+                    const orb::Cells cr = orb::cell_range<true>(in.g, u, v, r, rc.cells);
+                    gated = cr != orb::CELLS_NONFINITE;                                     // NONFINITE: a NaN radius
+                    if (cr != orb::CELLS_OK) why = gated ? EMPTY : NONFINITE;
                 }
             }
         }
@@ -103,14 +91,14 @@ extern "C" int qsp_search_by_projection_kf(int device, const qsp_search_proj_kf_
     if (!in) return bad(QSP_ERR_INVALID, "null input");
     if (in->n_src < 0) return bad(QSP_ERR_INVALID, "negative source count");
     if (in->n_src == 0) return QSP_OK;
-    if (in->n_src > search::MAX_KEYPOINTS) return bad(QSP_ERR_INVALID, "more than 2^26 sources");
+    if (in->n_src > orb::MAX_KEYPOINTS) return bad(QSP_ERR_INVALID, "more than 2^26 sources");
     if (in->mode != 0 && in->mode != 1) return bad(QSP_ERR_INVALID, "unknown mode");
     const bool reloc = in->mode == 0, ori = reloc && in->check_orientation;
-    if (!reloc && in->orb_dist != fuse::TH_LOW) return bad(QSP_ERR_INVALID, "SIM3 accepts at TH_LOW = 50 only");
+    if (!reloc && in->orb_dist != orb::TH_LOW) return bad(QSP_ERR_INVALID, "SIM3 accepts at TH_LOW = 50 only");
     if (!reloc && in->check_orientation) return bad(QSP_ERR_INVALID, "SIM3 has no orientation check");
     if (!in->frame) return bad(QSP_ERR_INVALID, "null frame");
     const qsp_orb_frame& F = *in->frame;
-    const char* why = fuse::frame_problem(F);
+    const char* why = orb::orb_frame_problem(F, false);
     if (why) return bad(QSP_ERR_INVALID, std::string("frame: ") + why);
     if (F.n && (!in->slot_blocked || (ori && !in->kp_angle))) return bad(QSP_ERR_INVALID, "null key-point array");
     if (!in->src_valid || !in->Xw || !in->desc || !in->dist_min_inv || !in->dist_max_inv || !in->dist_max) return bad(QSP_ERR_INVALID, "null source array");
@@ -134,9 +122,9 @@ extern "C" int qsp_search_by_projection_kf(int device, const qsp_search_proj_kf_
     const size_t a_choice = L.take<int32_t>(zs), a_dist = L.take<int32_t>(zs), a_why = L.take<int32_t>(zs), a_lvl = L.take<int32_t>(zs),
                  a_px = L.take<float>(zs), a_py = L.take<float>(zs);
     std::vector<char> up, down;
-    std::vector<int32_t> slot_src, bin;
+    proj::Action act;
     if (!host_staging(up, L.up_bytes()) || !host_staging(down, L.down_bytes())) return bad(QSP_ERR_INVALID, "out of host memory for the staging buffers");
-    try { slot_src.assign(zn, -1); bin.assign(zs, -1); } catch (const std::exception&) { return bad(QSP_ERR_INVALID, "out of host memory"); }
+    if (!act.init(zn, zs)) return bad(QSP_ERR_INVALID, "out of host memory");
     put(up, a_kp, F.kp, 8 * zn); put(up, a_oct, F.octave, 4 * zn); put(up, a_desc, F.desc, 32 * zn); put(up, a_blk, in->slot_blocked, zn);
     put(up, a_val, in->src_valid, zs); put(up, a_Xw, in->Xw, 12 * zs); put(up, a_sd, in->desc, 32 * zs);
     put(up, a_dmin, in->dist_min_inv, 4 * zs); put(up, a_dmaxi, in->dist_max_inv, 4 * zs); put(up, a_dmax, in->dist_max, 4 * zs);
@@ -146,11 +134,8 @@ extern "C" int qsp_search_by_projection_kf(int device, const qsp_search_proj_kf_
     QSP_TRY(blk.upload(up.data(), L.up_bytes()));
     char* d = blk.data();
     proj::In k = {};
-    k.mode = reloc ? proj::RELOC : proj::SIM3; k.n = n; k.n_src = ns;
-    k.min_x = F.min_x; k.max_x = F.max_x; k.min_y = F.min_y; k.max_y = F.max_y;
-    k.cols = F.grid_cols; k.rows = F.grid_rows; k.w_inv = F.grid_w_inv; k.h_inv = F.grid_h_inv;
-    k.n_levels = F.n_levels; k.log_scale = F.log_scale;
-    for (int l = 0; l < F.n_levels; ++l) k.sf[l] = F.scale_factors[l];
+    orb::fill_grid(k.g, F, 0);
+    k.mode = reloc ? proj::RELOC : proj::SIM3; k.n_src = ns;
     memcpy(k.R, F.Rcw, sizeof k.R); memcpy(k.t, F.tcw, sizeof k.t); memcpy(k.Ow, in->Ow, sizeof k.Ow); memcpy(k.K, in->K, 4 * sizeof(float));
     k.th = in->th;
     k.accept_th = in->orb_dist; k.no_right = 1;
@@ -169,41 +154,18 @@ extern "C" int qsp_search_by_projection_kf(int device, const qsp_search_proj_kf_
     QSP_TRY(proj::run_rounds(who, k, d_rec, ptr<int32_t>(d, a_c0), ptr<int32_t>(d, a_c1), ptr<int32_t>(d, a_chg), o, &n_rounds));
     QSP_TRY(blk.download(down.data(), L.down_begin(), L.down_bytes()));
     const char* h = down.data();
-    // the action phase: every source blocks, so no two sources hold one slot
     const int32_t* choice = ptr<int32_t>(h, L.in_down(a_choice));
-    int32_t n_matches = 0, hist[proj::HISTO_LENGTH] = {}, ind[3] = {-1, -1, -1};
-    for (int32_t i = 0; i < ns; ++i) {
-        const int32_t c = choice[i];
-        if (c < 0) continue;
-        if (c >= n) return bad(QSP_ERR_DEVICE, "internal error: a choice outside the frame");
-        if (slot_src[c] != -1 || in->slot_blocked[c]) return bad(QSP_ERR_DEVICE, "internal error: a taken slot chosen");
-        slot_src[c] = i;
-        ++n_matches;
-        if (ori) {
-            bin[i] = proj::rot_bin_host(in->src_angle[i], in->kp_angle[c]);                 // :1562-1569
-            if (bin[i] >= 0) ++hist[bin[i]];
-        }
-    }
-    if (ori) {                                                       // :1577-1596
-        proj::three_maxima_host(hist, ind);
-        for (int32_t i = 0; i < ns; ++i)
-            if (bin[i] >= 0 && bin[i] != ind[0] && bin[i] != ind[1] && bin[i] != ind[2]) {
-                slot_src[choice[i]] = -2;
-                --n_matches;
-            }
-    }
+    why = act.run(choice, ori, in->src_angle, in->kp_angle, in->slot_blocked, true);     // every source blocks: no two hold one slot
+    if (why) return bad(QSP_ERR_DEVICE, why);
     // outputs are written only once everything has succeeded
     memcpy(out->choice, choice, 4 * zs);
     memcpy(out->dist, h + L.in_down(a_dist), 4 * zs);
-    if (n) memcpy(out->slot_src, slot_src.data(), 4 * zn);
     if (out->reason) memcpy(out->reason, h + L.in_down(a_why), 4 * zs);
     if (out->level) memcpy(out->level, h + L.in_down(a_lvl), 4 * zs);
     if (out->proj_x) memcpy(out->proj_x, h + L.in_down(a_px), 4 * zs);
     if (out->proj_y) memcpy(out->proj_y, h + L.in_down(a_py), 4 * zs);
-    if (out->bin) memcpy(out->bin, bin.data(), 4 * zs);
-    out->n_matches = n_matches;
-    memcpy(out->hist, hist, sizeof hist);
-    memcpy(out->ind, ind, sizeof ind);
+    if (out->bin) memcpy(out->bin, act.bin.data(), 4 * zs);
+    act.give(out);
     out->n_rounds = n_rounds;
     return QSP_OK;
 }

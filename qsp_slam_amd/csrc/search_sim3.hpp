@@ -1,14 +1,12 @@
 // search_sim3.hpp -- ORBmatcher::SearchBySim3 (reference src/ORBmatcher.cc:1102-1326) for ALL loop candidates of a key frame in one
-// call.  Compiled in c_abi.cpp.
+// call.  Compiled in c_abi.cpp; the steps it shares with the other matchers are orb_match.hpp's, the wave reduction is wave.hpp's.
 //
 // The reference runs, per candidate, two serial passes (key frame 1 -> 2 and 2 -> 1): project a map point through the candidate
 // Sim3, walk the target frame's feature grid inside a level-dependent radius (KeyFrame::GetFeaturesInArea, KeyFrame.cc:570-609),
 // keep the Hamming-nearest ORB descriptor, then keep the mutual matches.  Neither pass writes anything the other iterations read,
 // so here ONE WAVE owns one (candidate, direction, source slot): all 64 lanes compute the slot's gates redundantly, then stride
-// over the target frame's key points.  No grid is built: a key point is eligible when its own cell (Frame::PosInGrid,
-// Frame.cc:419-429) lies inside the grid and inside the visited cell range, and the reference's traversal order -- ascending
-// (cell x, cell y, index) -- is carried in a 64-bit key next to the distance, so one wave min-reduction yields the reference's
-// `dist < bestDist` winner.  k_search_sim3_agree gathers the mutual matches and counts them.
+// over the target frame's key points, each lane keeping the smallest orb::make_key it met, so one wave min-reduction yields the
+// reference's `dist < bestDist` winner.  k_search_sim3_agree gathers the mutual matches and counts them.
 //
 // Every function below evaluates with contraction OFF: the float32 operations of the reference in its order.
 #pragma once
@@ -16,25 +14,15 @@
 #include <string>
 #include <vector>
 
+#include "orb_match.hpp"
 #include "staging.hpp"
+#include "wave.hpp"
 
 namespace qsp {
 namespace search {
 
-constexpr int MAX_LEVELS = 16;
-constexpr int MAX_GRID = 64;
-constexpr int MAX_KEYPOINTS = 1 << 26;   // the key keeps the key-point index in 26 bits
-constexpr int TH_HIGH = 100;
-constexpr unsigned long long NO_KEY = ~0ull;
-
 struct FrameP {                       // one per frame: 0 is key frame 1, 1 + c key frame 2 of candidate c
-    int32_t off, n;                   // its key-point slots are [off, off + n) of the flat arrays
-    float min_x, max_x, min_y, max_y;
-    int32_t cols, rows;
-    float w_inv, h_inv;
-    int32_t n_levels;
-    float log_scale;
-    float sf[MAX_LEVELS];
+    orb::GridP g;
     float R[9], t[3];
 };
 
@@ -58,12 +46,6 @@ struct In {
     int32_t n_cand, n1;
 };
 
-// cv::Mat R * X as OpenCV's small-matrix product leaves it: the row product summed in double and rounded to float once
-__device__ inline float rowdot(const float* r, const float* X) {
-#pragma clang fp contract(off)
-    return (float)(((double)r[0] * (double)X[0] + (double)r[1] * (double)X[1]) + (double)r[2] * (double)X[2]);
-}
-
 // :1119-1121.  dir 0 (1 -> 2): M = sR21 = (1.0 / s12) * R12.t() (a double factor, rounded to float32 once), t = -sR21 * t12;
 // dir 1 (2 -> 1): M = sR12 = s12 * R12, t = t12
 __device__ inline void cand_transform(const CandP& C, int dir, float* M, float* t) {
@@ -75,12 +57,8 @@ __device__ inline void cand_transform(const CandP& C, int dir, float* M, float* 
         const double is = 1.0 / (double)C.s12;
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) M[3 * i + j] = (float)(is * (double)C.R12[3 * j + i]);
-        for (int i = 0; i < 3; ++i) t[i] = -rowdot(M + 3 * i, C.t12);
+        for (int i = 0; i < 3; ++i) t[i] = -orb::rowdot(M + 3 * i, C.t12);
     }
-}
-
-__device__ inline int popc128(const uint4& a, const uint4& b) {
-    return __popc(a.x ^ b.x) + __popc(a.y ^ b.y) + __popc(a.z ^ b.z) + __popc(a.w ^ b.w);
 }
 
 // 4 waves per workgroup, one wave per (candidate, direction, source slot)
@@ -90,31 +68,27 @@ __global__ __launch_bounds__(256) void k_search_sim3_best(In in, int64_t n_work,
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n_work) return;
-    int lo = 0, hi = in.n_cand;                          // the candidate whose range holds w (empty ranges are stepped over)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (in.work_off[mid] <= w) lo = mid; else hi = mid;
-    }
-    const int c = lo;
+    const int c = orb::owner_of(in.work_off, in.n_cand, w);
     const int32_t local = (int32_t)(w - in.work_off[c]);
     const int dir = local >= in.n1;
     const int32_t i = dir ? local - in.n1 : local;       // the source slot in its frame
     const FrameP& S = in.frame[dir ? 1 + c : 0];         // source and target frames
-    const FrameP& T = in.frame[dir ? 0 : 1 + c];
+    const orb::GridP& T = in.frame[dir ? 0 : 1 + c].g;
     const CandP& C = in.cand[c];
     const int64_t out_at = dir ? (int64_t)in.off2[c] + i : (int64_t)c * in.n1 + i;
     int32_t* const best = dir ? best2 : best1;
     int32_t* const dist = dir ? dist2 : dist1;
-    const int64_t s = (int64_t)S.off + i;
+    const int64_t s = (int64_t)S.g.off + i;
     int32_t res_best = -1, res_dist = -1;
     bool go = in.has_point[s] && !(dir ? in.pre2[out_at] : in.pre1[out_at]);
     float u = 0.f, v = 0.f, r = 0.f;
-    int level = 0, min_cx = 0, max_cx = 0, min_cy = 0, max_cy = 0;
+    int level = 0;
+    orb::CellRange cells = {};
     if (go) {                                            // wave-uniform: every lane evaluates the slot's gates
         float M[9], tt[3], pc[3], p[3];
         cand_transform(C, dir, M, tt);
-        for (int k = 0; k < 3; ++k) pc[k] = rowdot(S.R + 3 * k, in.Xw + 3 * s) + S.t[k];     // Rcw * p3Dw + tcw
-        for (int k = 0; k < 3; ++k) p[k] = rowdot(M + 3 * k, pc) + tt[k];
+        for (int k = 0; k < 3; ++k) pc[k] = orb::rowdot(S.R + 3 * k, in.Xw + 3 * s) + S.t[k];     // Rcw * p3Dw + tcw
+        for (int k = 0; k < 3; ++k) p[k] = orb::rowdot(M + 3 * k, pc) + tt[k];
         go = !(p[2] < 0.0f);                             // :1163 (a NaN passes here and fails IsInImage)
         const float invz = (float)(1.0 / (double)p[2]);
         const float x = p[0] * invz, y = p[1] * invz;
@@ -124,46 +98,30 @@ __global__ __launch_bounds__(256) void k_search_sim3_best(In in, int64_t n_work,
         const float d3 = (float)sqrt(((double)p[0] * (double)p[0] + (double)p[1] * (double)p[1]) + (double)p[2] * (double)p[2]);
         go = go && !(d3 < in.dist_min_inv[s] || d3 > in.dist_max_inv[s]);
         if (go) {
-            // MapPoint::PredictScale(dist3D, target key frame), MapPoint.cc:391-406: the TARGET's mfLogScaleFactor and mnScaleLevels
-            const float ratio = in.dist_max[s] / d3;
-            const float fl = ceilf(logf(ratio) / T.log_scale);
-            level = fl < 0.f ? 0 : (fl >= (float)T.n_levels ? T.n_levels - 1 : (int)fl);
+            level = orb::predict_scale(in.dist_max[s], d3, T.log_scale, T.n_levels);      // in the TARGET key frame
             r = C.th * T.sf[level];
-            // KeyFrame::GetFeaturesInArea's cell range and early returns, KeyFrame.cc:575-589
-            min_cx = max(0, (int)floorf(((u - T.min_x) - r) * T.w_inv));
-            max_cx = min(T.cols - 1, (int)ceilf(((u - T.min_x) + r) * T.w_inv));
-            min_cy = max(0, (int)floorf(((v - T.min_y) - r) * T.h_inv));
-            max_cy = min(T.rows - 1, (int)ceilf(((v - T.min_y) + r) * T.h_inv));
-            go = !(min_cx >= T.cols || max_cx < 0 || min_cy >= T.rows || max_cy < 0);
+            go = orb::cell_range<false>(T, u, v, r, cells) == orb::CELLS_OK;
         }
     }
     if (go) {
         const uint4* md = (const uint4*)(in.mp_desc + 32 * s);       // the map point's descriptor: once per wave, 8 dwords
         const uint4 m0 = md[0], m1 = md[1];
-        unsigned long long key = NO_KEY;
+        unsigned long long key = orb::NO_KEY;
         for (int32_t j = lane; j < T.n; j += 64) {
             const int64_t g = (int64_t)T.off + j;
             const float2 k = ((const float2*)in.kp)[g];
-            const int cx = (int)roundf((k.x - T.min_x) * T.w_inv);   // Frame::PosInGrid: the cell the key point was filed under
-            const int cy = (int)roundf((k.y - T.min_y) * T.h_inv);
-            if (cx < 0 || cx >= T.cols || cy < 0 || cy >= T.rows) continue;          // never filed: never found
-            if (cx < min_cx || cx > max_cx || cy < min_cy || cy > max_cy) continue;
-            if (!(fabsf(k.x - u) < r && fabsf(k.y - v) < r)) continue;
+            int cx, cy;
+            if (!orb::cell_of(T, k, cx, cy) || !orb::in_range(cells, cx, cy)) continue;
+            if (!orb::in_window(k, u, v, r)) continue;
             const int oct = in.octave[g];
             if (oct < level - 1 || oct > level) continue;
-            const uint4* d = (const uint4*)(in.desc + 32 * g);
-            const unsigned long long hd = (unsigned)(popc128(d[0], m0) + popc128(d[1], m1));
-            const unsigned long long kk = (hd << 40) | ((unsigned long long)cx << 33) | ((unsigned long long)cy << 26) | (unsigned long long)j;
+            const unsigned long long kk = orb::make_key(orb::hamming256(in.desc + 32 * g, m0, m1), cx, cy, j);
             key = kk < key ? kk : key;
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const unsigned long long o = __shfl_xor(key, m, 64);
-            key = o < key ? o : key;
-        }
-        if (key != NO_KEY) {
-            res_dist = (int32_t)(key >> 40);
-            if (res_dist <= TH_HIGH) res_best = (int32_t)(key & (unsigned long long)(MAX_KEYPOINTS - 1));
+        key = wave_min(key);
+        if (key != orb::NO_KEY) {
+            res_dist = orb::key_dist(key);
+            if (res_dist <= orb::TH_HIGH) res_best = orb::key_index(key);
         }
     }
     if (lane == 0) {
@@ -186,20 +144,6 @@ __global__ __launch_bounds__(256) void k_search_sim3_agree(In in, const int32_t*
 }
 
 }  // namespace search
-
-static const char* search_frame_problem(const qsp_orb_frame& f) {
-    if (f.n < 0) return "negative key-point count";
-    if (f.n > search::MAX_KEYPOINTS) return "more than 2^26 key points in a frame";
-    if (f.grid_cols < 1 || f.grid_cols > search::MAX_GRID || f.grid_rows < 1 || f.grid_rows > search::MAX_GRID) return "grid outside 1..64 x 1..64";
-    if (f.n_levels < 1 || f.n_levels > search::MAX_LEVELS) return "n_levels outside 1..16";
-    if (!f.scale_factors) return "null scale_factors";
-    if (f.n && (!f.kp || !f.octave || !f.desc || !f.has_point || !f.Xw || !f.dist_min_inv || !f.dist_max_inv || !f.dist_max || !f.mp_desc))
-        return "null frame array";
-    for (int32_t i = 0; i < f.n; ++i)
-        if (f.octave[i] < 0 || f.octave[i] >= f.n_levels) return "a key point's level outside [0, n_levels)";
-    return nullptr;
-}
-
 }  // namespace qsp
 
 extern "C" int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in, qsp_search_sim3_out* out) {
@@ -213,13 +157,13 @@ extern "C" int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in
     if (!in->kf1 || !in->kf2 || !in->K || !in->s12 || !in->R12 || !in->t12 || !in->th || !in->off2)
         return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: null argument");
     const int32_t nc = in->n_cand;
-    const char* why = search_frame_problem(*in->kf1);
+    const char* why = orb::orb_frame_problem(*in->kf1, true);
     if (why) return qsp_fail(QSP_ERR_INVALID, (std::string("qsp_search_by_sim3_batch: key frame 1: ") + why).c_str());
     const int32_t n1 = in->kf1->n;
     if (in->off2[0] != 0) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: offsets start at 0");
     for (int32_t c = 0; c < nc; ++c) {
         if (in->off2[c + 1] < in->off2[c]) return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: offsets must not decrease");
-        why = search_frame_problem(in->kf2[c]);
+        why = orb::orb_frame_problem(in->kf2[c], true);
         if (why) return qsp_fail(QSP_ERR_INVALID, (std::string("qsp_search_by_sim3_batch: key frame 2: ") + why).c_str());
         if (in->off2[c + 1] - in->off2[c] != in->kf2[c].n)
             return qsp_fail(QSP_ERR_INVALID, "qsp_search_by_sim3_batch: off2 does not step by the key-point count of key frame 2");
@@ -252,11 +196,7 @@ extern "C" int qsp_search_by_sim3_batch(int device, const qsp_search_sim3_in* in
     for (int32_t f = 0; f <= nc; ++f) {
         const qsp_orb_frame& F = f ? in->kf2[f - 1] : *in->kf1;
         search::FrameP& P = fp[f];
-        P.off = (int32_t)slot; P.n = F.n;
-        P.min_x = F.min_x; P.max_x = F.max_x; P.min_y = F.min_y; P.max_y = F.max_y;
-        P.cols = F.grid_cols; P.rows = F.grid_rows; P.w_inv = F.grid_w_inv; P.h_inv = F.grid_h_inv;
-        P.n_levels = F.n_levels; P.log_scale = F.log_scale;
-        for (int l = 0; l < F.n_levels; ++l) P.sf[l] = F.scale_factors[l];
+        orb::fill_grid(P.g, F, slot);
         memcpy(P.R, F.Rcw, sizeof P.R);
         memcpy(P.t, F.tcw, sizeof P.t);
         const size_t n = (size_t)F.n;

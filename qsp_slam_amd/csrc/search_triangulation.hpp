@@ -1,7 +1,7 @@
 // search_triangulation.hpp -- ORBmatcher::SearchForTriangulation (reference src/ORBmatcher.cc:657-823, CheckDistEpipolarLine
 // :140-157) for ALL covisible neighbours of LocalMapping::CreateNewMapPoints in one call.  Compiled in c_abi.cpp after
-// search_bow.hpp, whose frame layout (bow::FrameB, bow::In), host-side CSR check, rot_bin and rotation tail (k_bow_rot) it uses as
-// they are; popc128 is search_sim3.hpp's.
+// search_bow.hpp, whose frame layout (bow::FrameB, bow::In), host-side CSR check and rotation tail (k_bow_rot) it uses as they are;
+// the Hamming distance and the search over node ids are orb_match.hpp's, the wave reduction is wave.hpp's.
 //
 // The reference walks the two DBoW2::FeatureVectors in step and, inside a common node, compares every source without a map point
 // with every target without one.  It declares vbMatched2 and reads it (:725) but never sets it, so there is NO loop-carried state:
@@ -26,12 +26,13 @@
 #include <string>
 #include <vector>
 
+#include "orb_match.hpp"
 #include "search_bow.hpp"
+#include "staging.hpp"
+#include "wave.hpp"
 
 namespace qsp {
 namespace tri {
-
-constexpr unsigned long long NO_KEY = ~0ull;
 
 struct Geo {                           // beside bow::In: indexed by the same slots
     const float* xy;                   // [n_slot][2]
@@ -59,11 +60,7 @@ __global__ __launch_bounds__(256) void k_tri_match(bow::In in, Geo g, int64_t n_
     // the reference's lower_bound walk over the two maps visits exactly the ids both hold
     const int32_t id = in.node_id[S.node_at + lo];
     const int32_t* tid = in.node_id + T.node_at;
-    int32_t a = 0, b = T.n_nodes;
-    while (a < b) {
-        const int32_t mid = a + ((b - a) >> 1);
-        if (tid[mid] < id) a = mid + 1; else b = mid;
-    }
+    const int32_t a = orb::lower_bound_id(tid, T.n_nodes, id);
     if (a >= T.n_nodes || tid[a] != id) return;
     const int32_t t0 = in.node_off[T.noff_at + a], nt = in.node_off[T.noff_at + a + 1] - t0;
     if (nt == 0) return;
@@ -84,15 +81,14 @@ __global__ __launch_bounds__(256) void k_tri_match(bow::In in, Geo g, int64_t n_
     const float den = la * la + lb * lb;
     const float ex = g.exy[2 * (int64_t)c], ey = g.exy[2 * (int64_t)c + 1];
     int best = in.th;                                    // :715
-    unsigned long long key = NO_KEY;
+    unsigned long long key = orb::NO_KEY;
     for (int32_t j = lane; j < nt; j += 64) {
         const int32_t t = tf[j];
         const int64_t gt = (int64_t)T.off + t;
         if (!in.elig[gt]) continue;                      // :725
         const bool stereo2 = g.stereo[gt] != 0;
         if (g.only_stereo && !stereo2) continue;         // :730
-        const uint4* d = (const uint4*)(in.desc + 32 * gt);
-        const int hd = search::popc128(d[0], m0) + search::popc128(d[1], m1);
+        const int hd = orb::hamming256(in.desc + 32 * gt, m0, m1);
         if (hd > in.th || hd > best) continue;           // :738, `best` being this lane's own
         const float x2 = g.xy[2 * gt], y2 = g.xy[2 * gt + 1];
         if (!stereo1 && !stereo2) {                      // :743-749
@@ -108,13 +104,8 @@ __global__ __launch_bounds__(256) void k_tri_match(bow::In in, Geo g, int64_t n_
         best = hd;
         key = ((unsigned long long)(unsigned)hd << 32) | (0xffffffffu - (unsigned)j);
     }
-    // the smallest distance, and of equal distances the LAST list position
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const unsigned long long ok = __shfl_xor(key, m, 64);
-        key = ok < key ? ok : key;
-    }
-    if (key == NO_KEY) return;
+    key = wave_min(key);                                 // the smallest distance, and of equal distances the LAST list position
+    if (key == orb::NO_KEY) return;
     if (lane == 0) {
         const int64_t at = (int64_t)c * in.n0 + i;
         match_raw[at] = tf[0xffffffffu - (unsigned)key];
@@ -177,7 +168,7 @@ struct SearchPlan {
     void take_down(StagingLayout& L) {
         const size_t no = (size_t)n_grid;
         a_match = L.take<int32_t>(no); a_raw = L.take<int32_t>(no); a_dist = L.take<int32_t>(no); a_count = L.take<int32_t>((size_t)nc);
-        a_hist = L.take<int32_t>((size_t)nc * bow::HISTO_LENGTH); a_ind = L.take<int32_t>((size_t)nc * 3);
+        a_hist = L.take<int32_t>((size_t)nc * orb::HISTO_LENGTH); a_ind = L.take<int32_t>((size_t)nc * 3);
     }
     void pack(std::vector<char>& up) const {
         bow::FrameB* fp = ptr<bow::FrameB>(up.data(), a_frame);
@@ -242,7 +233,7 @@ struct SearchPlan {
             if (out->dist) memcpy(out->dist, h + L.in_down(a_dist), 4 * no);
         }
         memcpy(out->n_matches, h + L.in_down(a_count), 4 * (size_t)nc);
-        if (out->hist) memcpy(out->hist, h + L.in_down(a_hist), 4 * (size_t)nc * bow::HISTO_LENGTH);
+        if (out->hist) memcpy(out->hist, h + L.in_down(a_hist), 4 * (size_t)nc * orb::HISTO_LENGTH);
         if (out->ind) memcpy(out->ind, h + L.in_down(a_ind), 4 * (size_t)nc * 3);
     }
 };

@@ -10,7 +10,7 @@
 // early end), which costs a few hundred FP64 operations per lane in a call that is bound by its launches and copies.
 //
 // Arithmetic.  Float32 one IEEE operation at a time (contraction OFF) in the reference's order.  A CV_32F matrix product row is
-// summed in double and rounded once (rowdot, as in search_sim3.hpp; a vector added to the product is added in float32, as fuse.hpp
+// summed in double and rounded once (as orb_match.hpp's rowdot does; a vector added to the product is added in float32, as fuse.hpp
 // does for Rcw * p + tcw -- NOT verified against OpenCV, where UnprojectStereo's `R * x3Dc + t` may fold into one gemm and round
 // once: a known possible deviation of at most one ulp of a coordinate, listed in INTEGRATION.md).  Mat::dot and cv::norm return
 // double: `Rcw.row(2).dot(x3Dt) + tcw.at<float>(2)` is a double sum rounded to float32 on assignment, and
