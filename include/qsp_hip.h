@@ -1350,6 +1350,114 @@ typedef struct {
 } qsp_search_proj_kf_out;
 int qsp_search_by_projection_kf(int device, const qsp_search_proj_kf_in* in, qsp_search_proj_kf_out* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Place recognition: KeyFrameDatabase::DetectLoopCandidates / DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:76-197,
+ * :199-309) and the minimum-score loop of LoopClosing::DetectLoop (src/LoopClosing.cc:131-148) against a key-frame database that
+ * is RESIDENT on the device.  L1Scoring::score is Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68.
+ *
+ * A qsp_place_db holds, per key frame it knows (a SLOT): the DBoW2::BowVector (word ids int32 strictly ascending, values double,
+ * in one growing arena), whether the key frame is LISTED (= in the reference's inverted file) with its list sequence number (the
+ * order of the add() calls), and the reference's per-key-frame query state: loop stamp / word count / score (mnLoopQuery,
+ * mnLoopWords, mLoopScore) and the same three for relocalisation.  The scores persist from query to query as the members do.
+ *
+ *   put(kf_id, n, word, value, listed)  makes a key frame known; listed = 1 also appends it to the inverted order (add()).  n == 0
+ *                                       is legal.  An id that was erased may be put again: it is a new key frame.
+ *   list(kf_id)                         KeyFrameDatabase::add for a known, unlisted key frame.
+ *   erase(kf_id)                        KeyFrameDatabase::erase: forgets the key frame; unknown id: QSP_OK, nothing happens.  The slot
+ *                                       stays as a hole until clear() (no compaction); size() reports the holes.
+ *   clear()                             forgets everything; the handle then behaves like a fresh one.
+ *   query / accumulate                  below.  put, list, erase and clear end the life of the last query of either mode:
+ *                                       accumulate after them is QSP_ERR_INVALID.
+ *
+ * qsp_place_db_query -- the map-sized part (:81-139 / :203-253), every rule as the reference has it:
+ *   - SHARING.  A listed key frame shares with the query when the two word lists intersect; its common-word count is the size
+ *     of the intersection.  LOOP: a key frame named in `excluded` (pKF->GetConnectedKeyFrames(); unknown ids are ignored) is
+ *     neither pushed nor stamped (:93-101).  RELOC ignores `excluded`.
+ *   - ORDER of lKFsSharingWords.  The reference finds key frames walking the query's words ascending and each word's list in
+ *     add() order: that is ascending (first common word, list sequence number), and that key is what the device sorts by.
+ *   - minCommonWords = (int)((float)maxCommonWords * 0.8f), a float32 product, truncated.  Scored: common words > minCommonWords.
+ *   - SCORE.  Sum in double, in ascending word order over the common words, of fabs(vi - wi) - fabs(vi) - fabs(wi) (vi the
+ *     query's value, wi the key frame's), then -sum / 2.0, then converted to float.  The float is what is stored and compared.
+ *   - LOOP keeps a scored key frame in lScoreAndMatch when si >= minScore; RELOC keeps every scored one.
+ *   - LOOP's minScore is in->min_score, or, with n_ref > 0, DetectLoop's: 1.0f, then (float)score(query, ref) for each ref in
+ *     order, keeping the smaller (`score < minScore`).  Every ref must be known (listed or not); the shim leaves bad ones out.
+ *   Outputs: n_sharing, max_common, min_common, min_score_used (RELOC: 0), n_match and lScoreAndMatch as (match_id, match_score)
+ *   in the reference's order; the taps give id, common-word count and first common word per sharing key frame in order.  Every
+ *   output array needs room for `listed` entries (qsp_place_db_size); the first n_match / n_sharing are written.
+ *
+ * qsp_place_db_accumulate -- the covisibility pass (:144-196 / :258-308) over the lScoreAndMatch the last query of that mode
+ * returned, on the device against the resident per-slot state.  The caller gives GetBestCovisibilityKeyFrames(10) of each entry
+ * in CSR form (nbr_off (n+1), nbr_id), in the reference's order; a neighbour id that is unknown or erased is "not of this query".
+ *   - LOOP: a neighbour counts when this query stamped it and its common words are > minCommonWords; bestAccScore starts at
+ *     minScore.  RELOC: a neighbour counts when this query stamped it, EVEN IF IT WAS NOT SCORED in this query -- its score is
+ *     then the one left by the last query that scored it (:273-281); bestAccScore starts at 0.
+ *   - accScore += score in float32 in neighbour order; the best key frame changes on a strict `>`; minScoreToRetain =
+ *     0.75f * bestAccScore; an entry is retained when its accumulated score is strictly greater; the candidates are the retained
+ *     entries' best key frames, first occurrence kept.
+ *   Outputs: n_cand and cand_id (room for n), taps acc_score (n) and best_id (n).
+ *
+ * DEVIATIONS, all three on purpose:
+ *   1. The reference never initialises mRelocScore; here it starts at 0.0f (so does the loop score).
+ *   2. The reference stamps with the querying frame's mnId, so two queries with the same id would double-count the words; here
+ *      every call is a new query.
+ *   3. mnRelocQuery / mnLoopQuery start at 0 in the reference, so a query by frame id 0 never finds a key frame it has not
+ *      stamped before; not reproduced.
+ *
+ * Host pointers.  No output is written unless the call returns QSP_OK, and a refused put / list leaves the database as it was.
+ * A query that is refused (QSP_ERR_INVALID / _UNSUPPORTED) leaves the resident state as it was too.  A query that fails LATER, with
+ * QSP_ERR_DEVICE or out of host memory after its kernels were launched, writes no output either, but the stamps, word counts and
+ * scores of its mode on the device may already be those of the failed query (a later RELOC query can then read such a score as the
+ * stale one); the last query of that mode is dead, so accumulate is refused until the next successful query.
+ * SIZE.  No count is capped, but the order and the accumulate kernel are ONE workgroup each, taking entries 1024 at a time, and the
+ * ranking is quadratic in the number of sharing key frames: that part is serial on one compute unit (about 3 ms at 5000 sharing
+ * key frames, profiles/place_db.txt).
+ * QSP_ERR_INVALID: null required pointers (arrays of n == 0 entries may be NULL), negative sizes, an unknown mode, words that are
+ * negative or not strictly ascending, values that are not finite, a kf_id put twice, listing an unknown or already listed id, an
+ * unknown ref_id, a min_score that is NaN, nbr_off that does not start at 0 or decreases, and accumulate called with ids that are
+ * not the last query's lScoreAndMatch of that mode.  More than 2^31 - 1 words or slots: QSP_ERR_UNSUPPORTED.
+ * words_hint / slots_hint of create: the initial capacities (0: 1 Mi words, 1024 slots); both grow by doubling. */
+typedef struct qsp_place_db qsp_place_db;
+enum { QSP_PLACE_LOOP = 0, QSP_PLACE_RELOC = 1 };
+typedef struct {
+    int32_t mode;                 /* QSP_PLACE_LOOP / QSP_PLACE_RELOC */
+    int32_t n;                    /* the query's mBowVec.size() */
+    const int32_t* word;          /* (n) strictly ascending */
+    const double* value;          /* (n) */
+    int32_t n_excluded;           /* LOOP */
+    const int64_t* excluded;      /* (n_excluded) ids of the connected key frames */
+    float min_score;              /* LOOP with n_ref == 0 */
+    int32_t n_ref;                /* LOOP: > 0 computes DetectLoop's minimum score from these */
+    const int64_t* ref_id;        /* (n_ref) */
+} qsp_place_query_in;
+typedef struct {
+    int32_t n_sharing, max_common, min_common, n_match;
+    float min_score_used;
+    int64_t* match_id;            /* (listed) lScoreAndMatch: the key frames ... */
+    float* match_score;           /* (listed) ... and their scores */
+    /* the tests' taps, each may be NULL: lKFsSharingWords in order */
+    int64_t* sharing_id;          /* (listed) */
+    int32_t* sharing_common;      /* (listed) */
+    int32_t* sharing_first;       /* (listed) the first common word */
+} qsp_place_query_out;
+typedef struct {
+    int32_t n_cand;
+    int64_t* cand_id;             /* (n) */
+    /* the tests' taps, each may be NULL */
+    float* acc_score;             /* (n) */
+    int64_t* best_id;             /* (n) */
+} qsp_place_acc_out;
+int qsp_place_db_create(int device, int64_t words_hint, int32_t slots_hint, qsp_place_db** db);
+void qsp_place_db_destroy(qsp_place_db* db);
+int qsp_place_db_put(qsp_place_db* db, int64_t kf_id, int32_t n, const int32_t* word, const double* value, int32_t listed);
+int qsp_place_db_list(qsp_place_db* db, int64_t kf_id);
+int qsp_place_db_erase(qsp_place_db* db, int64_t kf_id);
+int qsp_place_db_clear(qsp_place_db* db);
+/* each may be NULL; device_bytes: what the handle holds on the device */
+int qsp_place_db_size(qsp_place_db* db, int32_t* known, int32_t* listed, int32_t* dead_slots, int64_t* device_bytes);
+int qsp_place_db_query(qsp_place_db* db, const qsp_place_query_in* in, qsp_place_query_out* out);
+int qsp_place_db_accumulate(qsp_place_db* db, int32_t mode, int32_t n, const int64_t* id, const int32_t* nbr_off, const int64_t* nbr_id,
+                            qsp_place_acc_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1948,5 +1948,132 @@ public:
     }
 };
 
+// KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc) on the device: add / erase / clear keep a resident
+// qsp_place_db in step with the map, and the Detect* members are ONE query and ONE accumulate call each (include/qsp_hip.h, the
+// place-recognition block, which also lists the three deviations).  A template on the key-frame type; it reads mnId, mBowVec (a
+// std::map: words ascending), GetConnectedKeyFrames(), GetVectorCovisibleKeyFrames(), isBad() and
+// GetBestCovisibilityKeyFrames(10).  No vocabulary is needed: the inverted file is gone.  The one-argument DetectLoopCandidates
+// computes the minimum score of LoopClosing::DetectLoop (src/LoopClosing.cc:131-148) in the same call; a covisible key frame that
+// the database has not seen yet (it is still in the loop-closing queue) is made known, unlisted, first.
+// A failed library call is logged like every other one of this header and leaves the caller with an EMPTY candidate list (for
+// DetectLoop: "no loop", for Relocalization: "not relocalised"); there is nothing else to fall back to.
+template <typename KF>
+class KeyFrameDatabaseHip {
+public:
+    KeyFrameDatabaseHip() {}
+    KeyFrameDatabaseHip(const KeyFrameDatabaseHip&) = delete;
+    KeyFrameDatabaseHip& operator=(const KeyFrameDatabaseHip&) = delete;
+    ~KeyFrameDatabaseHip() { if (db_) qsp_place_db_destroy(db_); }
+
+    int add(KF* pKF) {                                                               // :40-46
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (int rc = open()) return rc;
+        const int64_t id = (int64_t)pKF->mnId;
+        if (listed_.count(id)) return QSP_OK;                                        // the reference's add cannot fail: a repeat is a no-op
+        const int rc = known_.count(id) ? qsp_shim::report("qsp_place_db_list", qsp_place_db_list(db_, id)) : put(pKF, 1);
+        if (rc == QSP_OK) listed_.insert(id);
+        return rc;
+    }
+    int erase(KF* pKF) {                                                             // :48-67
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (!db_) return QSP_OK;
+        const int rc = qsp_shim::report("qsp_place_db_erase", qsp_place_db_erase(db_, (int64_t)pKF->mnId));
+        if (rc == QSP_OK) { known_.erase((int64_t)pKF->mnId); listed_.erase((int64_t)pKF->mnId); }
+        return rc;
+    }
+    int clear() {                                                                    // :69-73
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (!db_) return QSP_OK;
+        const int rc = qsp_shim::report("qsp_place_db_clear", qsp_place_db_clear(db_));
+        if (rc == QSP_OK) { known_.clear(); listed_.clear(); }
+        return rc;
+    }
+
+    std::vector<KF*> DetectLoopCandidates(KF* pKF, float minScore) { return detect(QSP_PLACE_LOOP, pKF->mBowVec, pKF, minScore, false); }
+    // LoopClosing::DetectLoop's minScore over the non-bad covisible key frames, then DetectLoopCandidates with it
+    std::vector<KF*> DetectLoopCandidates(KF* pKF) { return detect(QSP_PLACE_LOOP, pKF->mBowVec, pKF, 1.0f, true); }
+    template <typename FR>
+    std::vector<KF*> DetectRelocalizationCandidates(FR* F) { return detect(QSP_PLACE_RELOC, F->mBowVec, static_cast<KF*>(nullptr), 0.f, false); }
+
+private:
+    int open() {
+        if (db_) return QSP_OK;
+        return qsp_shim::report("qsp_place_db_create", qsp_place_db_create(OptimizerHip::device(), 0, 0, &db_));
+    }
+    template <typename BV>
+    static void gather(const BV& bowVec, std::vector<int32_t>& word, std::vector<double>& value) {
+        for (const auto& kv : bowVec) {                                              // a std::map: ascending words
+            word.push_back((int32_t)kv.first);
+            value.push_back((double)kv.second);
+        }
+        word.push_back(0);                                                           // data() of an empty vector may be null
+        value.push_back(0.0);
+    }
+    int put(KF* pKF, const int listed) {
+        std::vector<int32_t> word;
+        std::vector<double> value;
+        gather(pKF->mBowVec, word, value);
+        const int rc = qsp_shim::report("qsp_place_db_put", qsp_place_db_put(db_, (int64_t)pKF->mnId, (int32_t)word.size() - 1, word.data(),
+                                                                           value.data(), listed));
+        if (rc == QSP_OK) known_[(int64_t)pKF->mnId] = pKF;
+        return rc;
+    }
+    template <typename BV>
+    std::vector<KF*> detect(const int32_t mode, const BV& bowVec, KF* pKF, const float minScore, const bool refs) {
+        std::unique_lock<std::mutex> lock(mMutex);
+        std::vector<KF*> none;
+        if (open() != QSP_OK) return none;
+        std::vector<int32_t> word;
+        std::vector<double> value;
+        gather(bowVec, word, value);
+        std::vector<int64_t> excluded, ref;
+        if (pKF) {
+            for (KF* c : pKF->GetConnectedKeyFrames()) excluded.push_back((int64_t)c->mnId);        // :78, :96
+            if (refs) {
+                for (KF* c : pKF->GetVectorCovisibleKeyFrames()) {                                   // LoopClosing.cc:134-148
+                    if (c->isBad()) continue;
+                    if (!known_.count((int64_t)c->mnId) && put(c, 0) != QSP_OK) return none;
+                    ref.push_back((int64_t)c->mnId);
+                }
+            }
+        }
+        int32_t listed = 0;
+        if (qsp_shim::report("qsp_place_db_size", qsp_place_db_size(db_, nullptr, &listed, nullptr, nullptr)) != QSP_OK) return none;
+        std::vector<int64_t> match_id((size_t)listed + 1);
+        std::vector<float> match_score((size_t)listed + 1);
+        qsp_place_query_in in = qsp_place_query_in();
+        in.mode = mode; in.n = (int32_t)word.size() - 1; in.word = word.data(); in.value = value.data();
+        in.n_excluded = (int32_t)excluded.size(); excluded.push_back(0); in.excluded = excluded.data();
+        in.min_score = minScore;
+        in.n_ref = (int32_t)ref.size(); ref.push_back(0); in.ref_id = ref.data();
+        qsp_place_query_out out = qsp_place_query_out();
+        out.match_id = match_id.data(); out.match_score = match_score.data();
+        if (qsp_shim::report("qsp_place_db_query", qsp_place_db_query(db_, &in, &out)) != QSP_OK) return none;
+        const size_t n = (size_t)out.n_match;
+        if (n == 0) return none;                                                                    // :141 / :255
+        std::vector<int32_t> nbr_off(1, 0);
+        std::vector<int64_t> nbr_id;
+        for (size_t i = 0; i < n; ++i) {                                                            // :151 / :265, only for the entries
+            for (KF* nb : known_.at(match_id[i])->GetBestCovisibilityKeyFrames(10)) nbr_id.push_back((int64_t)nb->mnId);
+            nbr_off.push_back((int32_t)nbr_id.size());
+        }
+        nbr_id.push_back(0);
+        std::vector<int64_t> cand(n + 1);
+        qsp_place_acc_out acc = qsp_place_acc_out();
+        acc.cand_id = cand.data();
+        if (qsp_shim::report("qsp_place_db_accumulate", qsp_place_db_accumulate(db_, mode, (int32_t)n, match_id.data(), nbr_off.data(),
+                                                                                 nbr_id.data(), &acc)) != QSP_OK) return none;
+        std::vector<KF*> vpCandidates;
+        vpCandidates.reserve((size_t)acc.n_cand);
+        for (int32_t i = 0; i < acc.n_cand; ++i) vpCandidates.push_back(known_.at(cand[i]));
+        return vpCandidates;
+    }
+
+    qsp_place_db* db_ = nullptr;
+    std::map<int64_t, KF*> known_;
+    std::set<int64_t> listed_;
+    std::mutex mMutex;
+};
+
 }  // namespace ORB_SLAM2
 #endif  // QSP_OPTIMIZER_SHIM_H

@@ -146,6 +146,21 @@ class SearchBowOut(C.Structure):
                 ("ind", c_int32_p)]
 
 
+class PlaceQueryIn(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("n", C.c_int32), ("word", c_int32_p), ("value", c_double_p), ("n_excluded", C.c_int32),
+                ("excluded", c_int64_p), ("min_score", C.c_float), ("n_ref", C.c_int32), ("ref_id", c_int64_p)]
+
+
+class PlaceQueryOut(C.Structure):
+    _fields_ = [("n_sharing", C.c_int32), ("max_common", C.c_int32), ("min_common", C.c_int32), ("n_match", C.c_int32),
+                ("min_score_used", C.c_float), ("match_id", c_int64_p), ("match_score", c_float_p), ("sharing_id", c_int64_p),
+                ("sharing_common", c_int32_p), ("sharing_first", c_int32_p)]
+
+
+class PlaceAccOut(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("cand_id", c_int64_p), ("acc_score", c_float_p), ("best_id", c_int64_p)]
+
+
 class TriFrame(C.Structure):
     _fields_ = [("bow", BowFrame), ("xy", c_float_p), ("stereo", c_uint8_p), ("sigma2", c_float_p), ("scale", c_float_p)]
 
@@ -231,6 +246,8 @@ SYMBOLS = [
     "qsp_mc_tables",
     "qsp_pose_optimizer_create", "qsp_pose_optimizer_destroy", "qsp_pose_optimize", "qsp_ellipsoid_fit_planes", "qsp_ellipsoid_fit_prior",
     "qsp_sim3_optimize_batch", "qsp_sim3_ransac_batch", "qsp_search_by_sim3_batch", "qsp_search_by_bow_batch", "qsp_search_for_triangulation_batch", "qsp_fuse_batch", "qsp_search_by_projection", "qsp_search_by_projection_kf", "qsp_triangulate_batch", "qsp_create_new_map_points_batch", "qsp_essential_graph_optimize", "qsp_essential_graph_stages", "qsp_object_gates",
+    "qsp_place_db_create", "qsp_place_db_destroy", "qsp_place_db_put", "qsp_place_db_list", "qsp_place_db_erase", "qsp_place_db_clear",
+    "qsp_place_db_size", "qsp_place_db_query", "qsp_place_db_accumulate",
     "qsp_ba_create", "qsp_ba_destroy", "qsp_ba_set_levels", "qsp_ba_optimize", "qsp_ba_local_joint",
     "qsp_ba_set_state", "qsp_ba_get_state", "qsp_ba_get_edges", "qsp_ba_get_index", "qsp_ba_profile", "qsp_ba_set_shard", "qsp_ba_set_deterministic",
     "qsp_ba_set_shard_rccl", "qsp_ba_set_option", "qsp_ba_release_caches", "qsp_comm_unique_id", "qsp_comm_create", "qsp_comm_adopt", "qsp_comm_destroy", "qsp_comm_nccl", "qsp_comm_stub_counts",
@@ -333,6 +350,16 @@ def lib():
     L.qsp_create_new_map_points_batch.argtypes = [C.c_int, C.POINTER(SearchTriIn), C.POINTER(TriangulateGeom), C.POINTER(SearchTriOut),
                                                   C.POINTER(TriangulateOut)]
     L.qsp_object_gates.argtypes = [C.c_int, C.POINTER(ObjectGateIn), C.POINTER(ObjectGateOut)]
+    L.qsp_place_db_create.argtypes = [C.c_int, C.c_int64, C.c_int32, C.POINTER(vp)]
+    L.qsp_place_db_destroy.argtypes = [vp]
+    L.qsp_place_db_destroy.restype = None
+    L.qsp_place_db_put.argtypes = [vp, C.c_int64, C.c_int32, c_int32_p, c_double_p, C.c_int32]
+    L.qsp_place_db_list.argtypes = [vp, C.c_int64]
+    L.qsp_place_db_erase.argtypes = [vp, C.c_int64]
+    L.qsp_place_db_clear.argtypes = [vp]
+    L.qsp_place_db_size.argtypes = [vp, c_int32_p, c_int32_p, c_int32_p, c_int64_p]
+    L.qsp_place_db_query.argtypes = [vp, C.POINTER(PlaceQueryIn), C.POINTER(PlaceQueryOut)]
+    L.qsp_place_db_accumulate.argtypes = [vp, C.c_int32, C.c_int32, c_int64_p, c_int32_p, c_int64_p, C.POINTER(PlaceAccOut)]
     L.qsp_ba_create.argtypes = [C.POINTER(BaScene), C.c_int, C.POINTER(vp)]
     L.qsp_ba_destroy.argtypes = [vp]
     L.qsp_ba_destroy.restype = None

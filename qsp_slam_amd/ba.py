@@ -921,3 +921,109 @@ def essential_graph_stages(sim3, fixed, edge_v0, edge_v1, meas, fix_scale, lam, 
         float(lam), *[_lib.dptr(a) for a in (E, chi, J, H, b, x, St, info)]))
     return dict(E=E, chi=chi, J=J, H=H, b=b, x=x, sim3_trial=St, chi2=float(info[0]), max_diag=float(info[1]), chi2_trial=float(info[2]),
                 scale=float(info[3]), failed=float(info[4]), dim=int(info[5]), nb=int(info[6]))
+
+
+class PlaceDatabase(object):
+    """The key-frame database of place recognition, resident on the device (qsp_place_db, include/qsp_hip.h): the BoW vectors of
+    every known key frame, which of them are listed (KeyFrameDatabase::add) in which order, and the reference's per-key-frame
+    query state.  query() is KeyFrameDatabase::DetectLoopCandidates / DetectRelocalizationCandidates up to lScoreAndMatch
+    (reference src/KeyFrameDatabase.cc:81-139 / :203-253), with DetectLoop's minimum score (src/LoopClosing.cc:131-148) when
+    `ref_ids` is given; accumulate() is the covisibility pass over it (:144-196 / :258-308).  Bit for bit and in the reference's
+    order.  words_hint / slots_hint: the initial capacities (they grow by doubling)."""
+    LOOP, RELOC = 0, 1
+
+    def __init__(self, device=0, words_hint=0, slots_hint=0):
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().qsp_place_db_create(int(device), int(words_hint), int(slots_hint), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _lib.lib().qsp_place_db_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _bow(words, values, who):
+        if int(np.size(words)) != int(np.size(values)):
+            raise ValueError("%s: one value per word" % who)
+        return _arr(np.reshape(words, -1), np.int32), _arr(np.reshape(values, -1), np.float64), int(np.size(words))
+
+    def put(self, kf_id, words, values, listed=True):
+        w, v, n = self._bow(words, values, "PlaceDatabase.put")
+        _lib.check(_lib.lib().qsp_place_db_put(self._h, int(kf_id), n, _lib.i32ptr(w), _lib.dptr(v), 1 if listed else 0))
+
+    def list(self, kf_id):
+        _lib.check(_lib.lib().qsp_place_db_list(self._h, int(kf_id)))
+
+    def erase(self, kf_id):
+        _lib.check(_lib.lib().qsp_place_db_erase(self._h, int(kf_id)))
+
+    def clear(self):
+        _lib.check(_lib.lib().qsp_place_db_clear(self._h))
+
+    def size(self):
+        """dict(known, listed, dead_slots, device_bytes)"""
+        k, l, d, b = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        _lib.check(_lib.lib().qsp_place_db_size(self._h, C.byref(k), C.byref(l), C.byref(d), C.byref(b)))
+        return dict(known=k.value, listed=l.value, dead_slots=d.value, device_bytes=b.value)
+
+    def query(self, mode, words, values, *, excluded=(), min_score=0.0, ref_ids=None, tap=True):
+        """One query.  LOOP: `excluded` are the ids of the connected key frames; the minimum score is `min_score`, or computed from
+        `ref_ids` (a non-empty list of known ids) as DetectLoop does.  Returns dict(n_sharing, max_common, min_common,
+        min_score_used, match_id, match_score) -- lScoreAndMatch in the reference's order -- and, with tap, sharing_id,
+        sharing_common, sharing_first: lKFsSharingWords in order."""
+        w, v, n = self._bow(words, values, "PlaceDatabase.query")
+        ex = _arr(np.reshape(np.asarray(excluded, np.int64), -1), np.int64)
+        n_ex = int(np.size(excluded))
+        n_ref = 0 if ref_ids is None else int(np.size(ref_ids))
+        rf = _arr(np.reshape(np.asarray(ref_ids if n_ref else [], np.int64), -1), np.int64)
+        cap = max(self.size()["listed"], 1)
+        mid, ms = np.zeros(cap, np.int64), np.zeros(cap, np.float32)
+        sid, sc, sf = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        i = _lib.PlaceQueryIn(int(mode), n, _lib.i32ptr(w), _lib.dptr(v), n_ex, _lib.i64ptr(ex), float(min_score), n_ref, _lib.i64ptr(rf))
+        o = _lib.PlaceQueryOut(0, 0, 0, 0, 0.0, _lib.i64ptr(mid), _lib.fptr(ms), _lib.i64ptr(sid) if tap else None,
+                               _lib.i32ptr(sc) if tap else None, _lib.i32ptr(sf) if tap else None)
+        _lib.check(_lib.lib().qsp_place_db_query(self._h, C.byref(i), C.byref(o)))
+        r = dict(n_sharing=int(o.n_sharing), max_common=int(o.max_common), min_common=int(o.min_common),
+                 min_score_used=np.float32(o.min_score_used), match_id=mid[:o.n_match].copy(), match_score=ms[:o.n_match].copy())
+        if tap:
+            r.update(sharing_id=sid[:o.n_sharing].copy(), sharing_common=sc[:o.n_sharing].copy(), sharing_first=sf[:o.n_sharing].copy())
+        return r
+
+    def accumulate(self, mode, ids, neighbours):
+        """The covisibility pass over the `match_id` the last query of `mode` returned.  neighbours: per entry the ids of
+        GetBestCovisibilityKeyFrames(10), in order (a list of lists, or a callable id -> list).  Returns dict(cand_id, acc_score,
+        best_id)."""
+        n = int(np.size(ids))
+        ids = _arr(np.reshape(np.asarray(ids, np.int64), -1), np.int64)
+        nb = [list(neighbours(int(k))) for k in ids[:n]] if callable(neighbours) else [list(x) for x in neighbours]
+        if len(nb) != n:
+            raise ValueError("PlaceDatabase.accumulate: one neighbour list per entry")
+        off = np.zeros(n + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in nb])
+        flat = _arr(np.array([k for x in nb for k in x], np.int64), np.int64)
+        cand, acc, best = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int64)
+        o = _lib.PlaceAccOut(0, _lib.i64ptr(cand), _lib.fptr(acc), _lib.i64ptr(best))
+        _lib.check(_lib.lib().qsp_place_db_accumulate(self._h, int(mode), n, _lib.i64ptr(ids), _lib.i32ptr(off), _lib.i64ptr(flat),
+                                                      C.byref(o)))
+        return dict(cand_id=cand[:o.n_cand].copy(), acc_score=acc[:n].copy(), best_id=best[:n].copy())
+
+    def _detect(self, mode, words, values, neighbours, **kw):
+        q = self.query(mode, words, values, **kw)
+        nb = neighbours if callable(neighbours) else [neighbours[int(k)] for k in q["match_id"]]
+        q.update(self.accumulate(mode, q["match_id"], nb))
+        return q
+
+    def detect_loop_candidates(self, words, values, neighbours, *, excluded=(), min_score=0.0, ref_ids=None):
+        """KeyFrameDatabase::DetectLoopCandidates: query + accumulate.  neighbours: a callable id -> ids of
+        GetBestCovisibilityKeyFrames(10), or a table (dict) of them.  The candidates are `cand_id` of the returned dict."""
+        return self._detect(self.LOOP, words, values, neighbours, excluded=excluded, min_score=min_score, ref_ids=ref_ids)
+
+    def detect_relocalization_candidates(self, words, values, neighbours):
+        """KeyFrameDatabase::DetectRelocalizationCandidates: query + accumulate, as detect_loop_candidates."""
+        return self._detect(self.RELOC, words, values, neighbours)

@@ -9,6 +9,7 @@
 #include "essential_graph.hpp"
 #include "fuse.hpp"
 #include "object_gate.hpp"
+#include "place_db.hpp"
 #include "search_bow.hpp"
 #include "search_projection.hpp"
 #include "search_projection_kf.hpp"
